@@ -9,18 +9,24 @@ owns its own 256 problems (weak scaling, no data-path collective); the only RCCL
 result gather after the timed region.
 
     python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR   # + DIR/scores.npy: the last timed step's scores
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full   # + every secondary leg below
     python bench.py --gpus 8 --steps 20 --warmup 5          # no launcher: bench.py starts its own 8 ranks (self_launch)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \\
         --master-port P bench.py --gpus N --steps K --warmup W
 
-`value` is timed with the per-stage HIP events switched OFF; the stage split and the roofline kernel's launch time come
-from a second loop of the same K steps with the events on (`config.ms_per_step_with_stage_events`).  Every run also times
-a STRONG-scaling leg (`config.strong_leg`: a fixed set of --strong-leg problems split over the ranks) next to the weak
-headline, so one driver sweep over N = 1, 2, 4, 8 yields both curves.  At N = 1 the default command also times the two
-bf16 shapes of BASELINE configs[2] / [4] (`config.other_configs_gpu`), the PCIe-inclusive, dense-output, bf16x3 and
-single-graph legs, the planner leg (host loop on ONE core + device planner) and the CPU baseline; at N > 1 only what a
-scaling line needs.  `config.whole_forward` separates CREDITED work (reference-formulation FLOPs / step time: not a
-utilisation, may exceed 1) from EXECUTED work (counter-measured MFMA FLOPs per step, profiles/kernel_mfma.json).
+A plain run sets up, runs W warm-up and K timed steps, writes the outputs of the last timed step if --dump-outputs is
+given and prints the result line: `value`, `ms_per_step` and the workload, nothing else.
+
+With --full, `value` is timed the same way (per-stage HIP events switched OFF); the stage split and the roofline kernel's
+launch time come from a second loop of the same K steps with the events on (`config.ms_per_step_with_stage_events`).  A
+--full run also times a STRONG-scaling leg (`config.strong_leg`: a fixed set of --strong-leg problems split over the
+ranks) next to the weak headline, so one driver sweep over N = 1, 2, 4, 8 yields both curves, and times the result
+gather.  At N = 1 it also times the two bf16 shapes of BASELINE configs[2] / [4] (`config.other_configs_gpu`), the
+PCIe-inclusive, dense-output, bf16x3 and single-graph legs, the planner leg (host loop on ONE core + device planner) and
+the CPU baseline; at N > 1 only what a scaling line needs.  `config.whole_forward` separates CREDITED work
+(reference-formulation FLOPs / step time: not a utilisation, may exceed 1) from EXECUTED work (counter-measured MFMA
+FLOPs per step, profiles/kernel_mfma.json).
 torch's intra-op pool is capped at the container's CPU quota (gnnmp.hostenv): uncapped it gets the process throttled.
 """
 import argparse
@@ -300,6 +306,24 @@ def whole_forward_block(wkey, flops_step, bytes_step, step_s, is_bf16):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, limit_bytes=DUMP_LIMIT_BYTES):
+    """--dump-outputs: every array of `arrays` (name -> tensor) as out_dir/<name>.npy in float32.  When they hold more than
+    `limit_bytes` together, each keeps a share of the budget in proportion to its size, as a sample of its flattened
+    elements at positions drawn by a fixed seed (sorted), so that the same arguments write the same positions every run."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    flat = {name: t.detach().float().cpu().numpy() for name, t in arrays.items()}
+    total = sum(a.nbytes for a in flat.values())
+    for name, a in flat.items():
+        if total > limit_bytes:
+            keep = a.size * limit_bytes // total
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+
+
 OTHER_CONFIGS = (      # (key, env, nodes, k1, problems per batch, MFMA operand mode): the bf16 shapes of BASELINE configs[2] and [4] (str2name.py:46-64)
     ('cfg2_kuka7_N2000_k10_bf16', 'kuka7', 2000, 10, 64, 'bf16'),
     ('cfg4_kuka14_N5000_k16_bf16', 'kuka14', 5000, 16, 32, 'bf16'))
@@ -453,8 +477,15 @@ def self_launch(n_gpus):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
-    ap.add_argument('--steps', type=int, default=20)
+    ap.add_argument('--steps', type=int, default=20, help='timed steps (>= 1)')
     ap.add_argument('--warmup', type=int, default=5)
+    ap.add_argument('--full', action='store_true',
+                    help='also run everything besides the headline steps: the stage-profiled loop and roofline, the strong, '
+                         'PCIe-inclusive, dense-output, in-flight, bf16x3, single-graph, other-configs and planner legs, the '
+                         'CPU baseline and the timed result gather.  Without it the options of those legs have no effect')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='after the timed steps, write the per-edge scores of the last timed step to DIR/scores.npy (float32; '
+                         'DIR/scores_rank<r>.npy per rank when N > 1); at most 64 MB in all, a fixed seeded sample beyond that')
     ap.add_argument('--graphs', type=int, default=256, help='graphs per GPU per step')
     ap.add_argument('--strong', type=int, default=0, metavar='N_TOTAL',
                     help='strong scaling: a FIXED set of N_TOTAL problems (seeds 1234 .. 1234 + N_TOTAL - 1) split over the '
@@ -494,6 +525,8 @@ def main():
                     help='start the ranks, connect them (init_process_group + one all_reduce), print one JSON line and exit without '
                          'running the workload (tests the launcher on a box without GPUs: GNNMP_BENCH_BACKEND=gloo)')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit('bench.py: --steps must be >= 1 and --warmup >= 0')
 
     have_launcher = 'RANK' in os.environ and 'WORLD_SIZE' in os.environ
     if args.gpus > 1 and not have_launcher:
@@ -518,6 +551,12 @@ def main():
         args.pcie_steps = args.dense_steps = args.bf16x3_steps = args.inflight_steps = args.other_configs_steps = 0
         if rank != 0:
             args.single_steps = 0
+    if not args.full:
+        # a plain run does only what `value` needs: no secondary leg (the stage-profiled loop, the self-checks and the result
+        # gather are skipped below)
+        args.pcie_steps = args.dense_steps = args.bf16x3_steps = args.inflight_steps = args.other_configs_steps = 0
+        args.single_steps = args.planner_problems = args.strong_leg = 0
+        args.no_cpu_baseline = True
     if args.strong > 0 and args.strong < world:
         # every rank sees the same arguments and leaves together (a rank bailing out alone would leave the others in a collective)
         raise SystemExit('bench.py: --strong %d is fewer problems than ranks (%d)' % (args.strong, world))
@@ -606,26 +645,31 @@ def main():
 
     # `value`: W warm-up steps, K timed steps, per-stage events OFF
     elapsed, scores = timed(batch, args.warmup, args.steps)
-    # the same K steps once more with the per-stage HIP events on (12 events per step on the forward's own stream): stage split
-    # and the roofline kernel's launch time; its step time is reported next to `ms_per_step`, never as `value`
-    model.profile(dev, True)
-    elapsed_prof, _ = timed(batch, 1, args.steps)
-    prof = model.profile_read(dev)
-    model.profile(dev, False)
-    for k_ in prof:                       # the warm-up step of the profiled loop is in the sums: scale to the K timed steps
-        prof[k_] = (prof[k_][0] * args.steps / (args.steps + 1), prof[k_][1] * args.steps // (args.steps + 1))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {'scores' if world == 1 else 'scores_rank%d' % rank: scores},
+                     DUMP_LIMIT_BYTES // world)
+    if args.full:
+        # the same K steps once more with the per-stage HIP events on (12 events per step on the forward's own stream): stage
+        # split and the roofline kernel's launch time; its step time is reported next to `ms_per_step`, never as `value`
+        model.profile(dev, True)
+        elapsed_prof, _ = timed(batch, 1, args.steps)
+        prof = model.profile_read(dev)
+        model.profile(dev, False)
+        for k_ in prof:                       # the warm-up step of the profiled loop is in the sums: scale to the K timed steps
+            prof[k_] = (prof[k_][0] * args.steps / (args.steps + 1), prof[k_][1] * args.steps // (args.steps + 1))
     # multi-GPU self-checks (they also run with one rank under GNNMP_BENCH_FORCE_DIST=1): how many ranks the collective
-    # library really connected (an all_reduce of ones), every rank's own step time (min / max show imbalance; `value` uses
-    # the MAX), the job's total graph count
+    # library really connected (an all_reduce of ones, --full), every rank's own step time (min / max show imbalance;
+    # `value` uses the MAX), the job's total graph count
     ranks_seen = 1
-    if use_dist:
+    if use_dist and args.full:
         ones = torch.ones(1, dtype=torch.float64, device=cdev)
         dist.all_reduce(ones, op=dist.ReduceOp.SUM)
         ranks_seen = int(round(float(ones.item())))
     rank_s, total_graphs = over_ranks(elapsed, G)
     rank_ms = [x / args.steps * 1e3 for x in rank_s]
     elapsed = max(rank_s)
-    elapsed_prof = max(over_ranks(elapsed_prof, G)[0])
+    if args.full:
+        elapsed_prof = max(over_ranks(elapsed_prof, G)[0])
 
     # strong-scaling leg of the same run: a FIXED set of --strong-leg problems (seeds 5000 + i) split over the ranks by
     # shard_range; whole-set rate = N_TOTAL * steps / the slowest rank's time.  One driver sweep over N then gives both curves.
@@ -771,10 +815,10 @@ def main():
 
     # final result gather (the only collective of the job): per-rank edge scores -> every rank
     # It is timed on its own (barrier + sync on both sides, median of --gather-reps, max over ranks) and NEVER enters `value`:
-    # no rank needs another rank's scores to make progress.
-    checksum = float(scores.double().sum().item())
+    # no rank needs another rank's scores to make progress.  (--full)
+    checksum = float(scores.double().sum().item()) if args.full else None
     gather_ms = None
-    if use_dist:
+    if use_dist and args.full:
         from gnnmp.dist import gather_variable
         gsrc = scores if backend == 'nccl' else scores.cpu()   # gloo gathers host tensors
         parts = gather_variable(gsrc)                      # one padded buffer, all_gather_into_tensor (RCCL); also the warm-up
@@ -795,11 +839,6 @@ def main():
         Ns = [int(g['v'].shape[0]) for g in graphs]
         Es = [int(g['edge_index'].shape[1]) for g in graphs]
         Os = [g['obstacles'].reshape(-1, e['S']).shape[0] for g in graphs]
-        flops_batch = sum(algorithmic_flops(n, m, o, e['C'], e['d'], e['S'], args.loop) for n, m, o in zip(Ns, Es, Os))
-        bytes_batch = sum(algorithmic_bytes(n, m, o, e['C'], e['S']) for n, m, o in zip(Ns, Es, Os))
-        roof, stage_roof = roofline_blocks(args, e, G, prof, Ns, Es, Os)
-        is_bf16 = args.mlp_dtype == 'bf16'
-        mfma_peak = PEAK_BF16_TFLOPS if is_bf16 else PEAK_FP32_TFLOPS
         shape = (args.env, args.nodes, args.k1, args.mlp_dtype)
         cfg_name = 'BASELINE configs[1]' if shape == ('maze2', 1000, 8, 'fp32') and G == 256 \
             else ('BASELINE configs[2] shape' if shape == ('kuka7', 2000, 10, 'bf16')
@@ -807,7 +846,6 @@ def main():
                         else ('BASELINE configs[0] shape, batched' if shape == ('maze2', 200, 6, 'fp32') else 'custom workload')))
         ms_step = elapsed / args.steps * 1e3
         value = total_graphs * args.steps / elapsed          # whole job: the graphs ALL ranks scored per step / the slowest rank's time
-        stages = {k: round(v[0] / max(args.steps, 1), 4) for k, v in prof.items()}
         res = {
             'metric': 'RGG graphs/sec (GNN explorer forward), %d-node k=%d' % (args.nodes, args.k1),
             'value': round(value, 2), 'unit': 'graphs/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
@@ -824,32 +862,42 @@ def main():
                                 'torch_threads_used': host_threads},
                        'parallelism': 'problem-sharded x%d (%s)' % (world, 'fixed set of %d problems split by shard_range' % args.strong
                                                                   if args.strong > 0 else '%d problems per GPU' % G),
-                       # multi-GPU self-checks: ranks the collective library connected, every rank's own ms per step, the result
-                       # gather timed on its own (not part of `value`)
-                       'ranks_seen': ranks_seen,
+                       # every rank's own ms per step (min / max show imbalance; `value` uses the max)
                        'rank_ms_per_step': {'min': round(min(rank_ms), 4), 'max': round(max(rank_ms), 4),
                                             'all': [round(x, 4) for x in rank_ms]},
                        'collective_backend': (backend if use_dist else None),
-                       'ms_per_step_with_stage_events': round(elapsed_prof / args.steps * 1e3, 4),
-                       'timing': '`value` / `ms_per_step`: %d steps with the per-stage HIP events OFF; stage_ms_per_step, stage_roofline and '
-                                 'roofline.launch_ms: a second loop of the same %d steps with the events on' % (args.steps, args.steps),
-                       'strong_leg': strong_leg,
-                       'gather_ms': gather_ms,
-                       'gather': None if gather_ms is None else 'per-edge scores of every rank -> every rank: two all_gather_into_tensor '
-                                 'calls (lengths, one padded payload of %d floats per rank), median of %d, max over ranks; outside the '
-                                 'timed region' % (int(scores.numel()), max(args.gather_reps, 1)),
-                       # rank 0's share of the job against the peaks of ONE GPU (rank 0's FLOPs / bytes over the job's step time)
-                       'whole_forward': whole_forward_block('%s N=%d k1=%d graphs=%d %s' % (args.env, args.nodes, args.k1, G, args.mlp_dtype),
-                                                            flops_batch, bytes_batch, elapsed / args.steps, is_bf16),
-                       'stage_ms_per_step': stages, 'stage_roofline': stage_roof, 'result_checksum': checksum,
-                       'pcie_inclusive_graphs_per_s_per_gpu': None if e2e is None else round(e2e, 1),
-                       'pcie_inclusive_one_batch_at_a_time': None if e2e_serial is None else round(e2e_serial, 1),
-                       'dense_output_graphs_per_s_per_gpu': None if dense_rate is None else round(dense_rate, 1),
-                       'batches_in_flight_graphs_per_s_per_gpu': None if inflight_rate is None else {'depth': max(2, args.inflight_depth), 'graphs_per_s': round(inflight_rate, 1)},
-                       'bf16x3_mode_graphs_per_s_per_gpu': None if x3_rate is None else round(x3_rate, 1),
-                       'single_graph_us': single_us},
-            'roofline': roof,
+                       'timing': '`value` / `ms_per_step`: %d steps after %d warm-up steps, per-stage HIP events off; the stage split, '
+                                 'roofline and secondary legs are in a --full run' % (args.steps, args.warmup)},
         }
+        if args.full:
+            flops_batch = sum(algorithmic_flops(n, m, o, e['C'], e['d'], e['S'], args.loop) for n, m, o in zip(Ns, Es, Os))
+            bytes_batch = sum(algorithmic_bytes(n, m, o, e['C'], e['S']) for n, m, o in zip(Ns, Es, Os))
+            roof, stage_roof = roofline_blocks(args, e, G, prof, Ns, Es, Os)
+            is_bf16 = args.mlp_dtype == 'bf16'
+            stages = {k: round(v[0] / max(args.steps, 1), 4) for k, v in prof.items()}
+            res['config'].update({
+                # multi-GPU self-checks: ranks the collective library connected, the result gather timed on its own (not part
+                # of `value`)
+                'ranks_seen': ranks_seen,
+                'ms_per_step_with_stage_events': round(elapsed_prof / args.steps * 1e3, 4),
+                'timing': '`value` / `ms_per_step`: %d steps with the per-stage HIP events OFF; stage_ms_per_step, stage_roofline and '
+                          'roofline.launch_ms: a second loop of the same %d steps with the events on' % (args.steps, args.steps),
+                'strong_leg': strong_leg,
+                'gather_ms': gather_ms,
+                'gather': None if gather_ms is None else 'per-edge scores of every rank -> every rank: two all_gather_into_tensor '
+                          'calls (lengths, one padded payload of %d floats per rank), median of %d, max over ranks; outside the '
+                          'timed region' % (int(scores.numel()), max(args.gather_reps, 1)),
+                # rank 0's share of the job against the peaks of ONE GPU (rank 0's FLOPs / bytes over the job's step time)
+                'whole_forward': whole_forward_block('%s N=%d k1=%d graphs=%d %s' % (args.env, args.nodes, args.k1, G, args.mlp_dtype),
+                                                     flops_batch, bytes_batch, elapsed / args.steps, is_bf16),
+                'stage_ms_per_step': stages, 'stage_roofline': stage_roof, 'result_checksum': checksum,
+                'pcie_inclusive_graphs_per_s_per_gpu': None if e2e is None else round(e2e, 1),
+                'pcie_inclusive_one_batch_at_a_time': None if e2e_serial is None else round(e2e_serial, 1),
+                'dense_output_graphs_per_s_per_gpu': None if dense_rate is None else round(dense_rate, 1),
+                'batches_in_flight_graphs_per_s_per_gpu': None if inflight_rate is None else {'depth': max(2, args.inflight_depth), 'graphs_per_s': round(inflight_rate, 1)},
+                'bf16x3_mode_graphs_per_s_per_gpu': None if x3_rate is None else round(x3_rate, 1),
+                'single_graph_us': single_us})
+            res['roofline'] = roof
         if world == 1 and args.other_configs_steps > 0 and args.strong == 0 and (args.env, args.nodes, args.k1, args.mlp_dtype, args.graphs) == ('maze2', 1000, 8, 'fp32', 256):
             del batch
             torch.cuda.empty_cache()

@@ -44,3 +44,21 @@ def test_other_configs_are_the_baseline_bf16_shapes():
     assert '2000-node k=10' in base[2] and 'bf16' in base[2] and '5000-node k=16' in base[4] and 'bf16' in base[4]
     got = {(env, n, k, dt) for _, env, n, k, _, dt in bench.OTHER_CONFIGS}
     assert got == {('kuka7', 2000, 10, 'bf16'), ('kuka14', 5000, 16, 'bf16')}
+
+
+def test_dump_outputs_writes_float32_and_samples_the_same_positions_over_budget(tmp_path):
+    import numpy as np
+    import torch
+    small = torch.arange(10, dtype=torch.float64)
+    big = torch.linspace(-1.0, 1.0, 3000, dtype=torch.float32)
+    bench.dump_outputs(str(tmp_path / 'a'), {'small': small, 'big': big}, limit_bytes=1 << 20)
+    a = np.load(tmp_path / 'a' / 'small.npy')
+    assert a.dtype == np.float32 and np.array_equal(a, small.float().numpy())
+    assert np.array_equal(np.load(tmp_path / 'a' / 'big.npy'), big.numpy())
+    # over the budget: every array shrinks in proportion, to a sorted sample at positions drawn by a fixed seed
+    for d in ('b', 'c'):
+        bench.dump_outputs(str(tmp_path / d), {'small': small, 'big': big}, limit_bytes=2000)
+    b, c = np.load(tmp_path / 'b' / 'big.npy'), np.load(tmp_path / 'c' / 'big.npy')
+    s = np.load(tmp_path / 'b' / 'small.npy')
+    assert b.nbytes + s.nbytes <= 2000 and b.size > 400 and np.array_equal(b, c)
+    assert np.all(np.diff(b) > 0) and np.isin(b, big.numpy()).all()

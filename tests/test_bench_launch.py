@@ -58,3 +58,10 @@ def test_a_failing_rank_fails_the_self_launched_run():
                        text=True, timeout=600)
     assert r.returncode != 0 and not _json_lines(r.stdout)
     assert 'exit status' in r.stderr
+
+
+def test_steps_below_one_is_refused():
+    # `ms_per_step` is the time of one of exactly --steps timed steps: zero steps has no such time
+    r = subprocess.run([sys.executable, 'bench.py', '--gpus', '1', '--steps', '0'], cwd=REPO, env=_env(), capture_output=True,
+                       text=True, timeout=300)
+    assert r.returncode != 0 and '--steps' in r.stderr and not _json_lines(r.stdout)
