@@ -10,5 +10,6 @@ from . import dist, graph_build, hostenv, serve, synth  # noqa: F401  (host-side
 from .batch import GraphBatch  # noqa: F401
 from .explorer import EncoderProcessDecoder  # noqa: F401
 from .smoother import ModelSmoother, SmoothBatch  # noqa: F401
+from . import episodes  # noqa: F401,E402  (training supervision: gnnmp_episode_* entry points)
 
-__all__ = ['graph_build', 'hostenv', 'synth', 'GraphBatch', 'EncoderProcessDecoder', 'ModelSmoother', 'SmoothBatch']
+__all__ = ['graph_build', 'hostenv', 'synth', 'GraphBatch', 'EncoderProcessDecoder', 'ModelSmoother', 'SmoothBatch', 'episodes']

@@ -66,6 +66,11 @@ class MazeSampleBatch(ctypes.Structure):
                 ('goal_states', ctypes.c_void_p)]
 
 
+class EpisodeGraphs(ctypes.Structure):
+    _fields_ = [('n_problems', ctypes.c_int32), ('total_nodes', ctypes.c_int32), ('total_edges', ctypes.c_int32),
+                ('node_ptr', ctypes.c_void_p), ('edge_ptr', ctypes.c_void_p), ('edge_index', ctypes.c_void_p)]
+
+
 _lib = None
 
 
@@ -132,6 +137,12 @@ def lib():
                                         vp, vp, vp, vp, vp, sz, vp]
     L.gnnmp_maze_sample.argtypes = [ctypes.POINTER(MazeSampleBatch), vp, vp, vp, vp, vp, vp]
     L.gnnmp_maze_steer.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.gnnmp_episode_label_maze.argtypes = [ctypes.POINTER(EpisodeGraphs), ctypes.c_int32, ctypes.c_int32, vp, vp, vp, vp, vp]
+    L.gnnmp_episode_workspace_bytes.argtypes = [ctypes.POINTER(EpisodeGraphs), ctypes.POINTER(sz)]
+    L.gnnmp_episode_paths.argtypes = [ctypes.POINTER(EpisodeGraphs), vp, vp, vp, vp, vp, vp, sz, vp]
+    L.gnnmp_episode_explore.argtypes = [ctypes.POINTER(EpisodeGraphs), vp, vp, vp, vp, vp, ctypes.c_int32, vp, vp, vp, sz, vp]
+    L.gnnmp_episode_frontier.argtypes = [ctypes.POINTER(EpisodeGraphs), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz,
+                                         vp]
     L.gnnmp_pack_a_tiles.restype = ctypes.c_int64
     L.gnnmp_pack_a_tiles.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp]
     L.gnnmp_pack_a_small.restype = ctypes.c_int64

@@ -1923,3 +1923,120 @@ extern "C" int gnnmp_smoother_train_backward(const gnnmp_smoother* h, const gnnm
     }
     return GNNMP_OK;
 }
+
+// =============================================================================================
+// supervision of the explorer's training step (train_explorer.py:124-176, train_episode_kernels.hip)
+// =============================================================================================
+namespace {
+struct EpCarve { size_t row_beg, rev, explored, key, key_col, key_slot, dead, colkill, done, total; };
+bool ep_graphs_ok(const gnnmp_episode_graphs* g) {
+    return g->n_problems >= 1 && g->total_nodes >= 0 && g->total_edges >= 0 && g->node_ptr && g->edge_ptr &&
+           (g->total_edges == 0 || g->edge_index);
+}
+void ep_carve(const gnnmp_episode_graphs* g, EpCarve& c) {
+    size_t o = 0;
+    auto take = [&](size_t bytes) { const size_t r = o; o += (bytes + 255) & ~(size_t)255; return r; };
+    const size_t n1 = (size_t)g->total_nodes + g->n_problems, n2 = (size_t)g->total_nodes + 2 * (size_t)g->n_problems;
+    const size_t e = (size_t)(g->total_edges > 0 ? g->total_edges : 1), n = (size_t)(g->total_nodes > 0 ? g->total_nodes : 1);
+    c.row_beg = take(sizeof(int) * n1);
+    c.rev = take(sizeof(int) * e);
+    c.explored = take(sizeof(int) * n2);
+    c.key = take(sizeof(unsigned) * n2);
+    c.key_col = take(sizeof(int) * n2);
+    c.key_slot = take(sizeof(int) * n2);
+    c.dead = take(e);
+    c.colkill = take(n);
+    c.done = take(n);
+    c.total = o;
+}
+int ep_ws_check(const gnnmp_episode_graphs* g, void* ws, size_t ws_bytes, EpCarve& c) {
+    ep_carve(g, c);
+    if (!ws) return GNNMP_ERR_NULL;
+    if (ws_bytes < c.total || (reinterpret_cast<uintptr_t>(ws) & 255)) return GNNMP_ERR_WORKSPACE;
+    return GNNMP_OK;
+}
+}  // namespace
+
+extern "C" int gnnmp_episode_label_maze(const gnnmp_episode_graphs* g, int32_t dim, int32_t width, const double* points,
+                                        const double* maps, uint8_t* edge_free, double* edge_cost, void* hip_stream) {
+    if (!g || !points || !maps || !edge_free || !edge_cost) return GNNMP_ERR_NULL;
+    if (!ep_graphs_ok(g) || width < 1) return GNNMP_ERR_ARG;
+    if (dim != 2 && dim != 3) return GNNMP_ERR_DIMS;
+    EpLabelParams p;
+    p.B = g->n_problems; p.dim = dim; p.w = width; p.total_edges = g->total_edges;
+    p.points = points; p.node_ptr = g->node_ptr; p.edge_ptr = g->edge_ptr;
+    p.edge_index = reinterpret_cast<const long long*>(g->edge_index); p.maps = maps;
+    p.edge_free = edge_free; p.edge_cost = edge_cost;
+    if (g->total_edges > 0) HIP_TRY(launch_ep_label(p, static_cast<hipStream_t>(hip_stream)));
+    return GNNMP_OK;
+}
+
+extern "C" int gnnmp_episode_workspace_bytes(const gnnmp_episode_graphs* g, size_t* bytes) {
+    if (!g || !bytes) return GNNMP_ERR_NULL;
+    if (!ep_graphs_ok(g)) return GNNMP_ERR_ARG;
+    EpCarve c;
+    ep_carve(g, c);
+    *bytes = c.total;
+    return GNNMP_OK;
+}
+
+extern "C" int gnnmp_episode_paths(const gnnmp_episode_graphs* g, const double* edge_cost, const int32_t* goal_index,
+                                   double* dist, int32_t* prev, int32_t* n_valid, void* ws, size_t ws_bytes, void* hip_stream) {
+    if (!g || !goal_index || !dist || !prev || !n_valid) return GNNMP_ERR_NULL;
+    if (!ep_graphs_ok(g)) return GNNMP_ERR_ARG;
+    if (g->total_edges > 0 && !edge_cost) return GNNMP_ERR_NULL;
+    EpCarve c;
+    if (const int s = ep_ws_check(g, ws, ws_bytes, c)) return s;
+    EpPathsParams p;
+    p.B = g->n_problems; p.total_edges = g->total_edges;
+    p.node_ptr = g->node_ptr; p.edge_ptr = g->edge_ptr; p.goal_index = goal_index;
+    p.edge_index = reinterpret_cast<const long long*>(g->edge_index); p.edge_cost = edge_cost;
+    p.dist = dist; p.prev = prev; p.n_valid = n_valid;
+    p.row_beg = at<int>(ws, c.row_beg); p.done = at<unsigned char>(ws, c.done);
+    HIP_TRY(launch_ep_paths(p, static_cast<hipStream_t>(hip_stream)));
+    return GNNMP_OK;
+}
+
+namespace {
+int ep_episode_launch(const gnnmp_episode_graphs* g, int replay, const float* scores, const uint8_t* edge_free,
+                      const int32_t* goal_index, const int32_t* start_index, const int32_t* n_valid, int32_t max_steps,
+                      const double* dist, const int32_t* prev, int32_t* step, int32_t* status, int32_t* frontier,
+                      int32_t* frontier_len, int32_t* label, void* ws, size_t ws_bytes, void* hip_stream) {
+    if (!g || !goal_index || !start_index || !n_valid || !step || !status) return GNNMP_ERR_NULL;
+    if (!ep_graphs_ok(g)) return GNNMP_ERR_ARG;
+    if (g->total_edges > 0 && (!scores || !edge_free)) return GNNMP_ERR_NULL;
+    if (replay && (!dist || !prev || !frontier || !frontier_len || !label)) return GNNMP_ERR_NULL;
+    if (!replay && max_steps < 0) return GNNMP_ERR_ARG;
+    EpCarve c;
+    if (const int s = ep_ws_check(g, ws, ws_bytes, c)) return s;
+    EpEpisodeParams p;
+    p.B = g->n_problems; p.replay = replay; p.max_steps = max_steps; p.total_edges = g->total_edges;
+    p.node_ptr = g->node_ptr; p.edge_ptr = g->edge_ptr; p.goal_index = goal_index; p.start_index = start_index;
+    p.n_valid = n_valid; p.edge_index = reinterpret_cast<const long long*>(g->edge_index);
+    p.scores = scores; p.edge_free = edge_free; p.dist = dist; p.prev = prev;
+    p.step = step; p.status = status; p.frontier = frontier; p.frontier_len = frontier_len; p.label = label;
+    p.row_beg = at<int>(ws, c.row_beg); p.rev = at<int>(ws, c.rev); p.explored = at<int>(ws, c.explored);
+    p.key = at<unsigned>(ws, c.key); p.key_col = at<int>(ws, c.key_col); p.key_slot = at<int>(ws, c.key_slot);
+    p.dead = at<unsigned char>(ws, c.dead); p.colkill = at<unsigned char>(ws, c.colkill);
+    HIP_TRY(launch_ep_episode(p, static_cast<hipStream_t>(hip_stream)));
+    return GNNMP_OK;
+}
+}  // namespace
+
+extern "C" int gnnmp_episode_explore(const gnnmp_episode_graphs* g, const float* scores, const uint8_t* edge_free,
+                                     const int32_t* goal_index, const int32_t* start_index, const int32_t* n_valid,
+                                     int32_t max_steps, int32_t* step, int32_t* status, void* ws, size_t ws_bytes,
+                                     void* hip_stream) {
+    return ep_episode_launch(g, 0, scores, edge_free, goal_index, start_index, n_valid, max_steps, nullptr, nullptr, step, status,
+                             nullptr, nullptr, nullptr, ws, ws_bytes, hip_stream);
+}
+
+extern "C" int gnnmp_episode_frontier(const gnnmp_episode_graphs* g, const float* scores, const uint8_t* edge_free,
+                                      const int32_t* goal_index, const int32_t* start_index, const int32_t* n_valid,
+                                      const double* dist, const int32_t* prev, const int32_t* step, const int32_t* status,
+                                      int32_t* frontier, int32_t* frontier_len, int32_t* label, void* ws, size_t ws_bytes,
+                                      void* hip_stream) {
+    return ep_episode_launch(g, 1, scores, edge_free, goal_index, start_index, n_valid, 0, dist, prev,
+                             const_cast<int32_t*>(step), const_cast<int32_t*>(status), frontier, frontier_len, label, ws,
+                             ws_bytes, hip_stream);
+}

@@ -202,6 +202,49 @@ struct MazeSampleParams {
 };
 hipError_t launch_maze_sample(const MazeSampleParams& p, hipStream_t st);
 
+// ---- supervision of the explorer's training step (train_episode_kernels.hip, train_explorer.py:124-176)
+struct EpLabelParams {                    // (a) edge_free / edge_cost of construct_graph for maze problems
+    int B, dim, w;
+    long long total_edges;
+    const double* points;                 // [sumN, dim] float64
+    const int *node_ptr, *edge_ptr;       // [B + 1]
+    const long long* edge_index;          // [2, sumE] graph-local, coalesced
+    const double* maps;                   // [B, w, w]
+    unsigned char* edge_free;             // out [sumE]
+    double* edge_cost;                    // out [sumE]
+};
+hipError_t launch_ep_label(const EpLabelParams& p, hipStream_t st);
+
+struct EpPathsParams {                    // (b) dijkstra to goal_index[b]
+    int B;
+    long long total_edges;
+    const int *node_ptr, *edge_ptr, *goal_index;
+    const long long* edge_index;
+    const double* edge_cost;              // [sumE]
+    double* dist;                         // out [sumN]
+    int *prev, *n_valid;                  // out [sumN], [B]
+    int* row_beg;                         // ws [sumN + B]
+    unsigned char* done;                  // ws [sumN]
+};
+hipError_t launch_ep_paths(const EpPathsParams& p, hipStream_t st);
+
+struct EpEpisodeParams {                  // (c) explore (replay = 0) / policy_data (replay = 1)
+    int B, replay, max_steps;
+    long long total_edges;
+    const int *node_ptr, *edge_ptr, *goal_index, *start_index, *n_valid;
+    const long long* edge_index;
+    const float* scores;                  // [sumE] detached edge scores
+    const unsigned char* edge_free;       // [sumE]
+    const double* dist;                   // [sumN] (replay)
+    const int* prev;                      // [sumN] (replay)
+    int *step, *status;                   // [B]: explore writes both; replay reads them
+    int *frontier, *frontier_len, *label; // replay out: frontier [2 sumE + B] (problem b at 2 edge_ptr[b] + b), [B], [B]
+    int *row_beg, *rev, *explored, *key_col, *key_slot;     // ws: [sumN + B], [sumE], 3 x [sumN + 2B]
+    unsigned* key;                        // ws [sumN + 2B]
+    unsigned char *dead, *colkill;        // ws [sumE], [sumN]
+};
+hipError_t launch_ep_episode(const EpEpisodeParams& p, hipStream_t st);
+
 // ---- training path (train_kernels.hip)
 struct TrainGeom {
     int G, C, Npad, Epad;

@@ -412,6 +412,54 @@ int gnnmp_maze_sample(const gnnmp_maze_sample_batch* batch, int64_t* cursor, flo
                       int32_t* used_out, int32_t* ok_out, void* hip_stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Supervision of the explorer's training step (train_explorer.py:124-176): edge labels, shortest paths to the goal,
+ * the greedy roll-out of the detached policy and the frontier / label of the loss, for a batch of problems.
+ *   gnnmp_episode_label_maze      construct_graph's collision checks and costs     algorithm/dijkstra.py:15-31
+ *   gnnmp_episode_paths           dijkstra(nodes, neighbors, edge_cost, goal)     algorithm/dijkstra.py:49-76
+ *   gnnmp_episode_explore         explore(edge_cost, policy, start, goal, steps)  train_explorer.py:42-63
+ *   gnnmp_episode_frontier        policy_data(...)                                train_explorer.py:66-93
+ * Problem b owns node rows [node_ptr[b], node_ptr[b+1]) and edge columns [edge_ptr[b], edge_ptr[b+1]) of edge_index
+ * (graph-local ids).  The edge set of a problem must be the coalesced, symmetric set construct_graph builds (columns sorted
+ * by (source, target); (s, t) present iff (t, s) present).  Cell (a, c) of the reference's dense P[target][source] is the
+ * edge (c -> a).  All pointers are device pointers; every call is one launch on hip_stream, no synchronisation.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct {
+    int32_t n_problems, total_nodes, total_edges;
+    const int32_t *node_ptr, *edge_ptr;
+    const int64_t* edge_index;   /* [2, total_edges]                                          */
+} gnnmp_episode_graphs;
+
+/* Maze problems: edge_free [total_edges] (1 = MazeEnv._edge_fp(points[source], points[target])) and edge_cost
+ * [total_edges] (norm(points[target] - points[source]) as numpy computes it, +inf when blocked).  points: float64
+ * [total_nodes, dim], dim 2 (point robot) or 3 (stick robot); maps: float64 [B, width, width] (1 = obstacle). */
+int gnnmp_episode_label_maze(const gnnmp_episode_graphs* graphs, int32_t dim, int32_t width, const double* points,
+                             const double* maps, uint8_t* edge_free, double* edge_cost, void* hip_stream);
+/* One workspace serves paths, explore and frontier (256-byte aligned). */
+int gnnmp_episode_workspace_bytes(const gnnmp_episode_graphs* graphs, size_t* bytes);
+/* Shortest paths to goal_index[b] over the reversed edges: dist [total_nodes] float64 (+inf when unreachable), prev
+ * [total_nodes] (next node towards the goal; prev[goal] = goal; -1 when unreachable), n_valid [B] = finite distances
+ * (-1 when the edge set is not symmetric). */
+int gnnmp_episode_paths(const gnnmp_episode_graphs* graphs, const double* edge_cost, const int32_t* goal_index,
+                        double* dist, int32_t* prev, int32_t* n_valid, void* workspace, size_t workspace_bytes,
+                        void* hip_stream);
+/* Greedy roll-out of the detached scores [total_edges] from start_index[b] for at most max_steps steps: step [B] = the
+ * step at which the goal was taken, or max_steps - 1; status [B] = 0 ok, 1 skipped (n_valid == 1: only the goal is
+ * reachable), 2 skipped (the frontier emptied), 3 bad input (ids out of range, edge set not symmetric); step = -1 when
+ * skipped. */
+int gnnmp_episode_explore(const gnnmp_episode_graphs* graphs, const float* scores, const uint8_t* edge_free,
+                          const int32_t* goal_index, const int32_t* start_index, const int32_t* n_valid, int32_t max_steps,
+                          int32_t* step, int32_t* status, void* workspace, size_t workspace_bytes, void* hip_stream);
+/* The same roll-out for exactly step[b] steps, then the frontier: frontier [2 * total_edges + B] holds problem b's cells
+ * as edge ids (batch-wide column numbers of edge_index) from int offset 2 * edge_ptr[b] + b, in the reference's order
+ * (explored position, then column), frontier_len [B]; label [B] = next_edge_idx, the label's position in that list
+ * (-1 for skipped problems: status[b] != 0, frontier_len 0). */
+int gnnmp_episode_frontier(const gnnmp_episode_graphs* graphs, const float* scores, const uint8_t* edge_free,
+                           const int32_t* goal_index, const int32_t* start_index, const int32_t* n_valid,
+                           const double* dist, const int32_t* prev, const int32_t* step, const int32_t* status,
+                           int32_t* frontier, int32_t* frontier_len, int32_t* label, void* workspace,
+                           size_t workspace_bytes, void* hip_stream);
+
+/* ------------------------------------------------------------------------------------------
  * Host-only helpers exported for the CPU test-suite (no device needed)
  * ---------------------------------------------------------------------------------------- */
 /* Pack a row-major weight matrix W[out_f, in_f] (leading dimension ld, column offset col0, n_in
