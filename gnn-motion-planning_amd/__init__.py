@@ -11,5 +11,7 @@ from .batch import GraphBatch  # noqa: F401
 from .explorer import EncoderProcessDecoder  # noqa: F401
 from .smoother import ModelSmoother, SmoothBatch  # noqa: F401
 from . import episodes  # noqa: F401,E402  (training supervision: gnnmp_episode_* entry points)
+from . import oracle_smooth  # noqa: F401,E402  (the smoother's training targets: gnnmp_oracle_smooth)
 
-__all__ = ['graph_build', 'hostenv', 'synth', 'GraphBatch', 'EncoderProcessDecoder', 'ModelSmoother', 'SmoothBatch', 'episodes']
+__all__ = ['graph_build', 'hostenv', 'synth', 'GraphBatch', 'EncoderProcessDecoder', 'ModelSmoother', 'SmoothBatch', 'episodes',
+           'oracle_smooth']

@@ -71,6 +71,14 @@ class EpisodeGraphs(ctypes.Structure):
                 ('node_ptr', ctypes.c_void_p), ('edge_ptr', ctypes.c_void_p), ('edge_index', ctypes.c_void_p)]
 
 
+class OracleSmoothBatch(ctypes.Structure):
+    _fields_ = [('n_paths', ctypes.c_int32), ('total_points', ctypes.c_int32), ('dim', ctypes.c_int32), ('width', ctypes.c_int32),
+                ('iters', ctypes.c_int32), ('random_iter', ctypes.c_int32), ('prune_iter', ctypes.c_int32),
+                ('ratio', ctypes.c_int32), ('stop', ctypes.c_int32),
+                ('path_ptr', ctypes.c_void_p), ('paths', ctypes.c_void_p), ('is32', ctypes.c_void_p), ('maps', ctypes.c_void_p),
+                ('action', ctypes.c_void_p), ('node_idx', ctypes.c_void_p), ('u', ctypes.c_void_p)]
+
+
 _lib = None
 
 
@@ -143,6 +151,8 @@ def lib():
     L.gnnmp_episode_explore.argtypes = [ctypes.POINTER(EpisodeGraphs), vp, vp, vp, vp, vp, ctypes.c_int32, vp, vp, vp, sz, vp]
     L.gnnmp_episode_frontier.argtypes = [ctypes.POINTER(EpisodeGraphs), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz,
                                          vp]
+    L.gnnmp_oracle_smooth_limits.argtypes = [c_int32_p, c_int32_p]
+    L.gnnmp_oracle_smooth.argtypes = [ctypes.POINTER(OracleSmoothBatch), vp, vp, vp, vp, vp, vp]
     L.gnnmp_pack_a_tiles.restype = ctypes.c_int64
     L.gnnmp_pack_a_tiles.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp]
     L.gnnmp_pack_a_small.restype = ctypes.c_int64

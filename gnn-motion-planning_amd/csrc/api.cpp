@@ -2040,3 +2040,33 @@ extern "C" int gnnmp_episode_frontier(const gnnmp_episode_graphs* g, const float
                              const_cast<int32_t*>(step), const_cast<int32_t*>(status), frontier, frontier_len, label, ws,
                              ws_bytes, hip_stream);
 }
+
+// =============================================================================================
+// the smoother's training targets (smoother.py:67-151, oracle_smooth_kernels.hip)
+// =============================================================================================
+extern "C" int gnnmp_oracle_smooth_limits(int32_t* max_waypoints, int32_t* max_width) {
+    if (!max_waypoints || !max_width) return GNNMP_ERR_NULL;
+    *max_waypoints = kOracleSmoothCap;
+    *max_width = kOracleSmoothMaxWidth;
+    return GNNMP_OK;
+}
+
+extern "C" int gnnmp_oracle_smooth(const gnnmp_oracle_smooth_batch* b, double* out, uint8_t* out_is32, int32_t* out_len,
+                                   int64_t* checks, int32_t* status, void* hip_stream) {
+    if (!b || !out || !out_is32 || !out_len || !checks || !status) return GNNMP_ERR_NULL;
+    if (b->dim != 2 || b->width < 1 || b->width > kOracleSmoothMaxWidth) return GNNMP_ERR_DIMS;
+    if (b->n_paths < 0 || b->total_points < 0 || b->iters < 0 || b->random_iter < 0 || b->prune_iter < 0 ||
+        b->stop < 0 || b->stop > 2 || (b->ratio != 0 && b->ratio != 1))
+        return GNNMP_ERR_ARG;
+    if (b->n_paths == 0) return GNNMP_OK;
+    if (!b->path_ptr || !b->maps || (b->total_points > 0 && !b->paths)) return GNNMP_ERR_NULL;
+    if ((long long)b->iters * b->random_iter > 0 && (!b->action || (!b->node_idx && !b->u))) return GNNMP_ERR_NULL;
+    OracleSmoothParams p;
+    p.B = b->n_paths; p.total_points = b->total_points; p.w = b->width; p.iters = b->iters; p.random_iter = b->random_iter;
+    p.prune_iter = b->prune_iter; p.ratio = b->ratio; p.stop = b->stop;
+    p.path_ptr = b->path_ptr; p.paths = b->paths; p.in_is32 = b->is32; p.maps = b->maps;
+    p.action = b->action; p.node_idx = b->node_idx; p.u = b->u;
+    p.out = out; p.out_is32 = out_is32; p.out_len = out_len; p.checks = reinterpret_cast<long long*>(checks); p.status = status;
+    HIP_TRY(launch_oracle_smooth(p, static_cast<hipStream_t>(hip_stream)));
+    return GNNMP_OK;
+}

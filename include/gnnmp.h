@@ -460,6 +460,52 @@ int gnnmp_episode_frontier(const gnnmp_episode_graphs* graphs, const float* scor
                            size_t workspace_bytes, void* hip_stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The smoother's training targets (train_smoother.py:98): joint_smoother_ratio / joint_smoother (smoother.py:67-151) for
+ * a batch of 2-D maze paths, MazeEnv(dim=2)'s collision checks and their count included, in one launch (one wave per
+ * path, the whole iters x [random_path_smoother -> prune_path -> re-spacing] loop on the device).
+ *
+ * A waypoint is a float32 row (an untouched input waypoint) or a float64 one (perturbed or re-spaced); the reference's
+ * arithmetic follows numpy's promotion per expression, so every waypoint carries a flag next to its float64 value.  The
+ * random draws are the caller's: action [B, iters, random_iter, 2] (np.random.uniform(-eps, eps, 2) per trial) and either
+ * node_idx [B, iters, random_iter] (the reference's randint(1, len - 1), replayed) or u in [0, 1) with
+ * node_idx = 1 + min(floor(u (len - 2)), len - 3) taken at the path's current length.
+ *
+ * Per-path status bits (the other paths of the batch are unaffected):
+ *   1 two waypoints with identical coordinates (the reference merges them as dictionary keys): path handed through
+ *   2 more than max_waypoints waypoints: path handed through
+ *   4 a prune round could not reach its segment's end (the reference's swallowed exception): path as before that round
+ *   8 the pruned path is not a subsequence of its input (the reference's re-spacing would raise): stopped there
+ *  16 bisection stack overflow (cannot happen for states inside [-1, 1]^2)
+ *  32 a replayed node_idx outside [1, len - 2]: that trial was skipped
+ *  64 dijkstra met two unvisited waypoints of exactly equal finite distance (the reference pops them in hash order, the
+ *     device the lowest index): the result may differ from a reference run
+ * 128 path_ptr[b] .. path_ptr[b + 1] is not a range inside [0, total_points]: nothing read or written for that path
+ * All pointers are device pointers; one launch on hip_stream, no allocation, no synchronisation.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct {
+    int32_t n_paths, total_points;
+    int32_t dim;                 /* 2 (the point robot); anything else is GNNMP_ERR_DIMS      */
+    int32_t width;               /* map cells per side, 1 .. max_width                        */
+    int32_t iters, random_iter, prune_iter;
+    int32_t ratio;               /* 1 = joint_smoother_ratio (waypoint count kept), 0 = joint_smoother (paths shrink) */
+    int32_t stop;                /* 0 = run to the end; 1 = end after the last iteration's random stage; 2 = after its
+                                    prune (before any re-spacing): the recorded stages of the reference               */
+    const int32_t* path_ptr;     /* [n_paths + 1]                                             */
+    const double* paths;         /* [total_points, 2] float64 (float32 rows upcast)           */
+    const uint8_t* is32;         /* [total_points] 1 = float32 row; NULL = all of them        */
+    const uint8_t* maps;         /* [n_paths, width, width] 0 = free                          */
+    const double* action;        /* [n_paths, iters, random_iter, 2]                          */
+    const int32_t* node_idx;     /* [n_paths, iters, random_iter] or NULL                     */
+    const double* u;             /* [n_paths, iters, random_iter], read when node_idx is NULL */
+} gnnmp_oracle_smooth_batch;
+/* The kernel's per-path limits: waypoints per path and map cells per side. */
+int gnnmp_oracle_smooth_limits(int32_t* max_waypoints, int32_t* max_width);
+/* out [total_points, 2] / out_is32 [total_points]: path b from row path_ptr[b], out_len[b] rows (the rest of its rows is
+ * not written); checks [n_paths] = collision_check_count of the call; status [n_paths] as above. */
+int gnnmp_oracle_smooth(const gnnmp_oracle_smooth_batch* batch, double* out, uint8_t* out_is32, int32_t* out_len,
+                        int64_t* checks, int32_t* status, void* hip_stream);
+
+/* ------------------------------------------------------------------------------------------
  * Host-only helpers exported for the CPU test-suite (no device needed)
  * ---------------------------------------------------------------------------------------- */
 /* Pack a row-major weight matrix W[out_f, in_f] (leading dimension ld, column offset col0, n_in
