@@ -153,6 +153,7 @@ def lib():
                                          vp]
     L.gnnmp_oracle_smooth_limits.argtypes = [c_int32_p, c_int32_p]
     L.gnnmp_oracle_smooth.argtypes = [ctypes.POINTER(OracleSmoothBatch), vp, vp, vp, vp, vp, vp]
+    L.gnnmp_stick_oracle_smooth.argtypes = [ctypes.POINTER(OracleSmoothBatch), vp, vp, vp, vp, vp, vp]
     L.gnnmp_pack_a_tiles.restype = ctypes.c_int64
     L.gnnmp_pack_a_tiles.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp]
     L.gnnmp_pack_a_small.restype = ctypes.c_int64

@@ -2051,10 +2051,11 @@ extern "C" int gnnmp_oracle_smooth_limits(int32_t* max_waypoints, int32_t* max_w
     return GNNMP_OK;
 }
 
-extern "C" int gnnmp_oracle_smooth(const gnnmp_oracle_smooth_batch* b, double* out, uint8_t* out_is32, int32_t* out_len,
-                                   int64_t* checks, int32_t* status, void* hip_stream) {
+// both entry points: the same checks in the same order, ``dim`` the one width the entry point serves
+static int oracle_smooth_run(const gnnmp_oracle_smooth_batch* b, int dim, double* out, uint8_t* out_is32, int32_t* out_len,
+                             int64_t* checks, int32_t* status, void* hip_stream) {
     if (!b || !out || !out_is32 || !out_len || !checks || !status) return GNNMP_ERR_NULL;
-    if (b->dim != 2 || b->width < 1 || b->width > kOracleSmoothMaxWidth) return GNNMP_ERR_DIMS;
+    if (b->dim != dim || b->width < 1 || b->width > kOracleSmoothMaxWidth) return GNNMP_ERR_DIMS;
     if (b->n_paths < 0 || b->total_points < 0 || b->iters < 0 || b->random_iter < 0 || b->prune_iter < 0 ||
         b->stop < 0 || b->stop > 2 || (b->ratio != 0 && b->ratio != 1))
         return GNNMP_ERR_ARG;
@@ -2063,10 +2064,21 @@ extern "C" int gnnmp_oracle_smooth(const gnnmp_oracle_smooth_batch* b, double* o
     if ((long long)b->iters * b->random_iter > 0 && (!b->action || (!b->node_idx && !b->u))) return GNNMP_ERR_NULL;
     OracleSmoothParams p;
     p.B = b->n_paths; p.total_points = b->total_points; p.w = b->width; p.iters = b->iters; p.random_iter = b->random_iter;
-    p.prune_iter = b->prune_iter; p.ratio = b->ratio; p.stop = b->stop;
+    p.prune_iter = b->prune_iter; p.ratio = b->ratio; p.stop = b->stop; p.dim = dim;
     p.path_ptr = b->path_ptr; p.paths = b->paths; p.in_is32 = b->is32; p.maps = b->maps;
     p.action = b->action; p.node_idx = b->node_idx; p.u = b->u;
     p.out = out; p.out_is32 = out_is32; p.out_len = out_len; p.checks = reinterpret_cast<long long*>(checks); p.status = status;
     HIP_TRY(launch_oracle_smooth(p, static_cast<hipStream_t>(hip_stream)));
     return GNNMP_OK;
+}
+
+extern "C" int gnnmp_oracle_smooth(const gnnmp_oracle_smooth_batch* b, double* out, uint8_t* out_is32, int32_t* out_len,
+                                   int64_t* checks, int32_t* status, void* hip_stream) {
+    return oracle_smooth_run(b, 2, out, out_is32, out_len, checks, status, hip_stream);
+}
+
+// the stick robot, MazeEnv(dim=3): batch->dim == 3, rows of three
+extern "C" int gnnmp_stick_oracle_smooth(const gnnmp_oracle_smooth_batch* b, double* out, uint8_t* out_is32,
+                                         int32_t* out_len, int64_t* checks, int32_t* status, void* hip_stream) {
+    return oracle_smooth_run(b, 3, out, out_is32, out_len, checks, status, hip_stream);
 }

@@ -245,19 +245,20 @@ struct EpEpisodeParams {                  // (c) explore (replay = 0) / policy_d
 };
 hipError_t launch_ep_episode(const EpEpisodeParams& p, hipStream_t st);
 
-// ---- the smoother's training targets (oracle_smooth_kernels.hip, smoother.py:67-151), 2-D maze paths, one wave per path
+// ---- the smoother's training targets (oracle_smooth_kernels.hip, smoother.py:67-151), 2-D / 3-D maze paths, one wave per path
 constexpr int kOracleSmoothCap = 128;         // waypoints per path
 constexpr int kOracleSmoothMaxWidth = 64;     // map cells per side
 struct OracleSmoothParams {
     int B, total_points, w, iters, random_iter, prune_iter, ratio, stop;
+    int dim;                              // 2 (point robot) or 3 (stick robot): row width of paths / out / action
     const int* path_ptr;                  // [B + 1]
-    const double* paths;                  // [sumP, 2] float64 (float32 rows upcast)
+    const double* paths;                  // [sumP, dim] float64 (float32 rows upcast)
     const unsigned char* in_is32;         // [sumP] 1 = the waypoint is a float32 row; nullptr = all of them
     const unsigned char* maps;            // [B, w, w] 0 = free
-    const double* action;                 // [B, iters, random_iter, 2]
+    const double* action;                 // [B, iters, random_iter, dim]
     const int* node_idx;                  // [B, iters, random_iter] replayed indices, or nullptr
     const double* u;                      // [B, iters, random_iter] in [0, 1) when node_idx == nullptr
-    double* out;                          // [sumP, 2], path b from row path_ptr[b], out_len[b] rows
+    double* out;                          // [sumP, dim], path b from row path_ptr[b], out_len[b] rows
     unsigned char* out_is32;              // [sumP]
     int* out_len;                         // [B]
     long long* checks;                    // [B] collision_check_count

@@ -1,6 +1,7 @@
 // oracle_smooth_kernels.hip -- the smoother's training targets on the device: joint_smoother_ratio / joint_smoother
-// (smoother.py:129-151) for a batch of 2-D maze paths, one wave per path, the whole outer loop
-// (iters x [random_path_smoother -> prune_path -> re-spacing]) in one launch.
+// (smoother.py:129-151) for a batch of maze paths -- 2-D (the point robot) or 3-D (the stick robot, MazeEnv(dim=3)) --
+// one wave per path, the whole outer loop (iters x [random_path_smoother -> prune_path -> re-spacing]) in one launch.
+// The kernel is one template over the dimension; the 2-D instantiation evaluates exactly the expressions it always did.
 //
 // Everything is the reference's arithmetic and decision order, exactly:
 //   * a waypoint is float32 (an untouched input row) or float64 (perturbed / re-spaced); numpy's promotion decides the
@@ -12,6 +13,16 @@
 //   * np.linalg.norm of a 2-vector is sqrt(dot): float64 dot = fma(d1, d1, d0 * d0) (as ep_label_kernel has it), float32
 //     dot = d0 * d0 + d1 * d1 with both operations rounded; sqrt and the float32 division go through double, whose 53 bits
 //     make the second rounding to 24 bits harmless.
+// The stick robot (maze_env.py:245-347), D = 3, waypoints (x, y, z, is32):
+//   * _valid_state compares against LIMITS = (1, 1, 0.4) in float64 (a float32 z upcasts exactly); nothing wraps or clips;
+//   * _stick_in_free_space does not depend on the waypoint's dtype: theta = z / 0.4 * pi and the stick ends are float64,
+//     each in-bounds end is one check, then the float64 bisection of the end-to-end segment;
+//   * _edge_fp of size 3: both validity tests, both stick checks, then K = int(distance / 0.015) interpolated sticks
+//     c = state + k * 1. / K * disp (disp[2] wrapped by 0.8), each the 2-D _edge_fp of its ends, up to the first blocked
+//     one.  Two float32 ends take the float32 flow of maze_kernels.hip's stick_edge_fp, anything else the float64 flow of
+//     train_episode_kernels.hip's ep_edge_fp3 on exactly upcast values;
+//   * np.linalg.norm of a 3-vector (no wrap) is sqrt(dot): float64 dot = fma(d2, d2, fma(d1, d1, d0 * d0)); float32 dot =
+//     the three float32-rounded squares summed left to right in double and rounded once to float32.
 // Parallel across lanes: the critical-index test and the all-pairs edge checks of create_graph (one ordered pair per lane),
 // dijkstra's scan and relaxation, the duplicate test, the re-spacing.  Sequential: the perturbation trials (lanes 0 / 1 check
 // the trial's two edges), dijkstra's rounds, the walk back.  Throughput comes from the batch: one 64-lane block per path.
@@ -33,7 +44,7 @@ constexpr int kOsOccWords = kOracleSmoothMaxWidth * kOracleSmoothMaxWidth / 32;
 enum : int { kStDuplicate = 1, kStCap = 2, kStUnreachable = 4, kStOrder = 8, kStStack = 16, kStNodeIdx = 32, kStTie = 64,
              kStBadPtr = 128 };
 
-struct OsPt { double x, y; bool f; };           // f: the waypoint is a float32 array
+struct OsPt { double x, y, z; bool f; };        // f: the waypoint is a float32 array; z: the stick's orientation (D = 3)
 
 struct OsMaze {
     const unsigned* occ;                        // LDS bit map, bit (cx * w + cy) set = obstacle
@@ -70,6 +81,7 @@ __device__ bool os_segment(const OsMaze& m, OsPt l, OsPt r, int& cnt) {
         else far = fabs(l.x - r.x) + fabs(l.y - r.y) > 0.05;
         if (dc > 1 && far) {
             OsPt mid;
+            mid.z = 0.0;
             mid.f = f;
             if (f) { mid.x = (double)(((float)l.x + (float)r.x) / 2.0f); mid.y = (double)(((float)l.y + (float)r.y) / 2.0f); }
             else { mid.x = (l.x + r.x) / 2.0; mid.y = (l.y + r.y) / 2.0; }
@@ -93,6 +105,91 @@ __device__ bool os_edge(const OsMaze& m, const OsPt& a, const OsPt& b, int& cnt)
     if (!os_state(m, b, cnt)) return false;
     return os_segment(m, a, b, cnt);
 }
+// ---- the stick robot.  _valid_state against LIMITS = (1, 1, 0.4)
+__device__ __forceinline__ bool os_valid3(const OsPt& p) { return os_valid(p) && p.z >= -0.4 && p.z <= 0.4; }
+// _end_points: theta = z / LIMITS[2] * pi, ends = center -+ (STICK_LENGTH / 2.) * (cos, sin), float64 whatever the state is
+__device__ __forceinline__ void os_ends(double x, double y, double z, OsPt& a, OsPt& b) {
+    const double theta = z / 0.4 * 3.141592653589793;
+    const double ox = 0.1 * cos(theta), oy = 0.1 * sin(theta);
+    a = OsPt{x - ox, y - oy, 0.0, false};
+    b = OsPt{x + ox, y + oy, 0.0, false};
+}
+__device__ bool os_stick(const OsMaze& m, const OsPt& p, int& cnt) {                           // _stick_in_free_space
+    if (!os_valid3(p)) return false;
+    OsPt a, b;
+    os_ends(p.x, p.y, p.z, a, b);
+    if (!os_state(m, a, cnt)) return false;
+    if (!os_state(m, b, cnt)) return false;
+    return os_segment(m, a, b, cnt);
+}
+__device__ bool os_edge3(const OsMaze& m, const OsPt& s, const OsPt& t, int& cnt) {            // _edge_fp, size 3
+    if (!os_valid3(s) || !os_valid3(t)) return false;
+    if (!os_stick(m, s, cnt)) return false;
+    if (!os_stick(m, t, cnt)) return false;
+    OsPt a, b;
+    if (s.f && t.f) {                                                        // float32 rows: stick_edge_fp's flow
+        const float s0 = (float)s.x, s1 = (float)s.y, s2 = (float)s.z, t0 = (float)t.x, t1 = (float)t.y, t2 = (float)t.z;
+        const float d0 = t0 - s0, d1 = t1 - s1;
+        float d2 = t2 - s2;
+        if (fabs((double)d2) > 0.4) d2 = (float)(d2 > 0.f ? (double)d2 - 0.8 : (double)d2 + 0.8);
+        // distance(): |diff| in float32, third coordinate wrapped through float64, sqrt of the float32 sum of squares
+        const float a0 = fabsf(d0), a1 = fabsf(d1), a2r = fabsf(t2 - s2);
+        const double w2 = fabs((double)a2r - 0.8);
+        const float a2 = (float)((double)a2r < w2 ? (double)a2r : w2);
+        const float q0 = a0 * a0, q1 = a1 * a1, q2 = a2 * a2;
+        const float q01 = q0 + q1;
+        const float q = q01 + q2;
+        const float dist = (float)sqrt((double)q);
+        const int K = (int)(float)((double)dist / (double)0.015f);
+        for (int k = 1; k < K; ++k) {
+            const float r = (float)((double)k * 1.0 / (double)K);
+            const float m0 = r * d0, m1 = r * d1, m2 = r * d2;
+            const float cx = s0 + m0, cy = s1 + m1, cz = s2 + m2;
+            os_ends((double)cx, (double)cy, (double)cz, a, b);
+            if (!os_edge(m, a, b, cnt)) return false;
+        }
+        return true;
+    }
+    const double d0 = t.x - s.x, d1 = t.y - s.y;                             // float64, or mixed: exactly upcast values
+    double d2 = t.z - s.z;
+    if (fabs(d2) > 0.4) d2 = d2 > 0.0 ? d2 - 0.8 : d2 + 0.8;
+    const double a0 = fabs(t.x - s.x), a1 = fabs(t.y - s.y);
+    double a2 = fabs(t.z - s.z);
+    const double w2 = fabs(a2 - 0.8);
+    a2 = w2 < a2 ? w2 : a2;
+    const double q0 = a0 * a0, q1 = a1 * a1, q2 = a2 * a2;
+    const double d = sqrt((q0 + q1) + q2);
+    const int K = (int)(d / 0.015);
+    for (int k = 1; k < K; ++k) {
+        const double r = (double)k / (double)K;                              // k * 1. / K
+        const double m0 = r * d0, m1 = r * d1, m2 = r * d2;
+        os_ends(s.x + m0, s.y + m1, s.z + m2, a, b);
+        if (!os_edge(m, a, b, cnt)) return false;
+    }
+    return true;
+}
+template <int D> __device__ __forceinline__ bool os_state_d(const OsMaze& m, const OsPt& p, int& cnt) {    // _state_fp
+    return D == 3 ? os_stick(m, p, cnt) : os_state(m, p, cnt);
+}
+template <int D> __device__ __forceinline__ bool os_edge_d(const OsMaze& m, const OsPt& a, const OsPt& b, int& cnt) {
+    return D == 3 ? os_edge3(m, a, b, cnt) : os_edge(m, a, b, cnt);
+}
+// np.linalg.norm(a - b) of 3-vectors, no wrap
+__device__ __forceinline__ double os_norm3(const OsPt& a, const OsPt& b, bool& f) {
+    f = a.f && b.f;
+    if (f) {
+        const float d0 = (float)a.x - (float)b.x, d1 = (float)a.y - (float)b.y, d2 = (float)a.z - (float)b.z;
+        const float p0 = d0 * d0, p1 = d1 * d1, p2 = d2 * d2;
+        double acc = (double)p0 + (double)p1;
+        acc = acc + (double)p2;
+        return (double)(float)sqrt((double)(float)acc);
+    }
+    const double d0 = a.x - b.x, d1 = a.y - b.y, d2 = a.z - b.z;
+    double acc = d0 * d0;
+    acc = __builtin_fma(d1, d1, acc);
+    acc = __builtin_fma(d2, d2, acc);
+    return sqrt(acc);
+}
 // np.linalg.norm(a - b): the value as a double, f = it is a np.float32
 __device__ __forceinline__ double os_norm(const OsPt& a, const OsPt& b, bool& f) {
     f = a.f && b.f;
@@ -106,6 +203,9 @@ __device__ __forceinline__ double os_norm(const OsPt& a, const OsPt& b, bool& f)
     double acc = d0 * d0;
     acc = __builtin_fma(d1, d1, acc);
     return sqrt(acc);
+}
+template <int D> __device__ __forceinline__ double os_norm_d(const OsPt& a, const OsPt& b, bool& f) {
+    return D == 3 ? os_norm3(a, b, f) : os_norm(a, b, f);
 }
 // x + y of two numpy scalars with flags
 __device__ __forceinline__ double os_add(double x, bool fx, double y, bool fy, bool& f) {
@@ -135,15 +235,18 @@ __device__ __forceinline__ unsigned long long os_wave_min_u64(unsigned long long
     return k;
 }
 
-struct OsPath {                                  // one path in LDS
-    double x[kOsCap], y[kOsCap];
+template <int D> struct OsPath {                // one path in LDS
+    double x[kOsCap], y[kOsCap], z[D == 3 ? kOsCap : 1];
     unsigned char f[kOsCap], src[kOsCap];
-    __device__ __forceinline__ OsPt at(int i) const { return OsPt{x[i], y[i], f[i] != 0}; }
-    __device__ __forceinline__ void set(int i, const OsPt& p, int s) { x[i] = p.x; y[i] = p.y; f[i] = p.f ? 1 : 0; src[i] = (unsigned char)s; }
+    __device__ __forceinline__ OsPt at(int i) const { return OsPt{x[i], y[i], D == 3 ? z[i] : 0.0, f[i] != 0}; }
+    __device__ __forceinline__ void set(int i, const OsPt& p, int s) {
+        x[i] = p.x; y[i] = p.y; f[i] = p.f ? 1 : 0; src[i] = (unsigned char)s;
+        if (D == 3) z[i] = p.z;
+    }
 };
 
-struct OsShared {
-    OsPath R, P, N;                              // after the random stage; the prune's working path; the round's new path
+template <int D> struct OsShared {
+    OsPath<D> R, P, N;                              // after the random stage; the prune's working path; the round's new path
     double dist[kOsCap];
     unsigned char dist_f[kOsCap], done[kOsCap], crit[kOsCap];
     short prev[kOsCap];
@@ -154,17 +257,17 @@ struct OsShared {
 };
 
 // two waypoints with identical coordinates among the first n of q (wave-uniform)
-__device__ bool os_duplicates(const OsPath& q, int n, int lane) {
+template <int D> __device__ bool os_duplicates(const OsPath<D>& q, int n, int lane) {
     bool dup = false;
     for (int i = lane; i < n; i += 64)
-        for (int j = i + 1; j < n; ++j) dup = dup || (q.x[i] == q.x[j] && q.y[i] == q.y[j]);
+        for (int j = i + 1; j < n; ++j) dup = dup || (q.x[i] == q.x[j] && q.y[i] == q.y[j] && (D != 3 || q.z[i] == q.z[j]));
     return __any(dup);
 }
 
 }  // namespace
 
-__global__ __launch_bounds__(64) void oracle_smooth_kernel(OracleSmoothParams p) {
-    __shared__ OsShared sh;
+template <int D> __global__ __launch_bounds__(64) void oracle_smooth_kernel(OracleSmoothParams p) {
+    __shared__ OsShared<D> sh;
     const int b = blockIdx.x, lane = threadIdx.x;
     const int lo = p.path_ptr[b], hi = p.path_ptr[b + 1];
     if (lo < 0 || hi < lo || hi > p.total_points) {                          // nothing of this path can be addressed
@@ -172,12 +275,12 @@ __global__ __launch_bounds__(64) void oracle_smooth_kernel(OracleSmoothParams p)
         return;
     }
     int n = hi - lo;
-    const double* in = p.paths + 2 * (size_t)lo;
-    double* out = p.out + 2 * (size_t)lo;
+    const double* in = p.paths + D * (size_t)lo;
+    double* out = p.out + D * (size_t)lo;
     unsigned char* out_f = p.out_is32 + lo;
     if (n > kOsCap) {                                                        // beyond the cap: handed through, flagged
         for (int i = lane; i < n; i += 64) {
-            out[2 * i] = in[2 * i]; out[2 * i + 1] = in[2 * i + 1];
+            for (int k = 0; k < D; ++k) out[D * i + k] = in[D * i + k];
             out_f[i] = p.in_is32 ? p.in_is32[lo + i] : 1;
         }
         if (lane == 0) { p.status[b] = kStCap; p.checks[b] = 0; p.out_len[b] = n; }
@@ -187,7 +290,7 @@ __global__ __launch_bounds__(64) void oracle_smooth_kernel(OracleSmoothParams p)
     if (lane == 0) sh.status = 0;
     for (int i = lane; i < n; i += 64) {
         const bool f = p.in_is32 ? p.in_is32[lo + i] != 0 : true;
-        sh.R.set(i, OsPt{in[2 * i], in[2 * i + 1], f}, i);
+        sh.R.set(i, OsPt{in[D * i], in[D * i + 1], D == 3 ? in[D * i + 2] : 0.0, f}, i);
     }
     __syncthreads();
     const unsigned char* map = p.maps + (size_t)b * p.w * p.w;
@@ -215,13 +318,14 @@ __global__ __launch_bounds__(64) void oracle_smooth_kernel(OracleSmoothParams p)
                 }
                 if (idx < 1 || idx > n - 2) { status |= kStNodeIdx; continue; }
                 const OsPt old = sh.R.at(idx), pv = sh.R.at(idx - 1), nx = sh.R.at(idx + 1);
-                const OsPt nw{old.x + p.action[2 * d], old.y + p.action[2 * d + 1], false};       // tuple + float64 array
+                const OsPt nw{old.x + p.action[D * d], old.y + p.action[D * d + 1], D == 3 ? old.z + p.action[D * d + 2] : 0.0,
+                              false};                                        // tuple + float64 array
                 int c0 = 0;
-                bool ok = os_state(m, nw, c0);                               // every lane: the same answer
+                bool ok = os_state_d<D>(m, nw, c0);                          // every lane: the same answer
                 if (ok) {
                     int ce = 0;
                     bool e = false;
-                    if (lane < 2) e = os_edge(m, nw, lane == 0 ? pv : nx, ce);
+                    if (lane < 2) e = os_edge_d<D>(m, nw, lane == 0 ? pv : nx, ce);
                     const bool e1 = __shfl((int)e, 0, 64) != 0, e2 = __shfl((int)e, 1, 64) != 0;
                     if (lane == 0) cnt += c0 + ce;
                     if (lane == 1 && e1) cnt += ce;                          // the second edge is only checked after a free first
@@ -231,9 +335,9 @@ __global__ __launch_bounds__(64) void oracle_smooth_kernel(OracleSmoothParams p)
                 }
                 if (ok) {
                     bool f1, f2, f3, f4, fs;
-                    const double a1 = os_norm(nx, nw, f1), a2 = os_norm(pv, nw, f2);
+                    const double a1 = os_norm_d<D>(nx, nw, f1), a2 = os_norm_d<D>(pv, nw, f2);
                     const double lhs = os_add(a1, f1, a2, f2, fs);
-                    const double b1 = os_norm(nx, old, f3), b2 = os_norm(pv, old, f4);
+                    const double b1 = os_norm_d<D>(nx, old, f3), b2 = os_norm_d<D>(pv, old, f4);
                     const double rhs = os_add(b1, f3, b2, f4, fs);
                     if (lhs < rhs) {
                         __syncthreads();
@@ -254,7 +358,7 @@ __global__ __launch_bounds__(64) void oracle_smooth_kernel(OracleSmoothParams p)
             const int n0 = len;
             for (int i = lane; i < n0; i += 64) {                            // critical indices
                 bool cr = i == 0 || i == n0 - 1;
-                if (!cr) { int c = 0; cr = !os_edge(m, sh.P.at(i - 1), sh.P.at(i + 1), c); cnt += c; }
+                if (!cr) { int c = 0; cr = !os_edge_d<D>(m, sh.P.at(i - 1), sh.P.at(i + 1), c); cnt += c; }
                 sh.crit[i] = cr ? 1 : 0;
             }
             if (lane == 0) sh.N.set(0, sh.P.at(0), sh.P.src[0]);
@@ -270,7 +374,7 @@ __global__ __launch_bounds__(64) void oracle_smooth_kernel(OracleSmoothParams p)
                 for (int q = lane; q < mm * mm; q += 64) {
                     const int i = q / mm, j = q - i * mm;
                     int c = 0;
-                    if (os_edge(m, sh.P.at(a + i), sh.P.at(a + j), c)) atomicOr(&sh.adj[i][j >> 5], 1u << (j & 31));
+                    if (os_edge_d<D>(m, sh.P.at(a + i), sh.P.at(a + j), c)) atomicOr(&sh.adj[i][j >> 5], 1u << (j & 31));
                     cnt += c;
                 }
                 if (lane == 0) { sh.dist[0] = 0.0; sh.prev[0] = 0; }         // dist[source] = 0: a Python int, the cost's dtype wins
@@ -305,7 +409,7 @@ __global__ __launch_bounds__(64) void oracle_smooth_kernel(OracleSmoothParams p)
                     for (int v = lane; v < mm; v += 64) {
                         if (!((sh.adj[u][v >> 5] >> (v & 31)) & 1u)) continue;
                         bool cf, af;
-                        const double c = os_norm(pu, sh.P.at(a + v), cf);
+                        const double c = os_norm_d<D>(pu, sh.P.at(a + v), cf);
                         const double alt = os_add(du, du_f, c, cf, af);
                         if (alt < sh.dist[v]) { sh.dist[v] = alt; sh.dist_f[v] = af ? 1 : 0; sh.prev[v] = (short)u; }
                     }
@@ -349,14 +453,16 @@ __global__ __launch_bounds__(64) void oracle_smooth_kernel(OracleSmoothParams p)
             const OsPt A = sh.R.at(sa), B = sh.R.at(sb);
             const bool f = A.f && B.f;
             for (int i = sa + 1 + lane; i < sb; i += 64)
-                sh.R.set(i, OsPt{os_lerp(A.x, B.x, f, i - sa, sb - sa), os_lerp(A.y, B.y, f, i - sa, sb - sa), f}, i);
+                sh.R.set(i, OsPt{os_lerp(A.x, B.x, f, i - sa, sb - sa), os_lerp(A.y, B.y, f, i - sa, sb - sa),
+                                 D == 3 ? os_lerp(A.z, B.z, f, i - sa, sb - sa) : 0.0, f}, i);
         }
         __syncthreads();
     }
 
     __syncthreads();
     for (int i = lane; i < n; i += 64) {
-        out[2 * i] = sh.R.x[i]; out[2 * i + 1] = sh.R.y[i];
+        out[D * i] = sh.R.x[i]; out[D * i + 1] = sh.R.y[i];
+        if (D == 3) out[D * i + 2] = sh.R.z[i];
         out_f[i] = sh.R.f[i];
     }
 #pragma unroll
@@ -366,7 +472,8 @@ __global__ __launch_bounds__(64) void oracle_smooth_kernel(OracleSmoothParams p)
 
 hipError_t launch_oracle_smooth(const OracleSmoothParams& p, hipStream_t st) {
     if (p.B <= 0) return hipSuccess;
-    hipLaunchKernelGGL(oracle_smooth_kernel, dim3(p.B), dim3(64), 0, st, p);
+    if (p.dim == 3) hipLaunchKernelGGL(oracle_smooth_kernel<3>, dim3(p.B), dim3(64), 0, st, p);
+    else hipLaunchKernelGGL(oracle_smooth_kernel<2>, dim3(p.B), dim3(64), 0, st, p);
     return hipGetLastError();
 }
 

@@ -461,12 +461,15 @@ int gnnmp_episode_frontier(const gnnmp_episode_graphs* graphs, const float* scor
 
 /* ------------------------------------------------------------------------------------------
  * The smoother's training targets (train_smoother.py:98): joint_smoother_ratio / joint_smoother (smoother.py:67-151) for
- * a batch of 2-D maze paths, MazeEnv(dim=2)'s collision checks and their count included, in one launch (one wave per
- * path, the whole iters x [random_path_smoother -> prune_path -> re-spacing] loop on the device).
+ * a batch of maze paths, MazeEnv's collision checks and their count included, in one launch (one wave per path, the
+ * whole iters x [random_path_smoother -> prune_path -> re-spacing] loop on the device).  Two entry points share the batch
+ * struct: gnnmp_oracle_smooth for the point robot (MazeEnv(dim=2), rows of two) and gnnmp_stick_oracle_smooth for the
+ * stick robot (MazeEnv(dim=3), rows (x, y, z) with z the orientation coordinate in [-0.4, 0.4]; a perturbed waypoint whose
+ * z leaves that range is rejected like one that leaves the map, nothing wraps).
  *
  * A waypoint is a float32 row (an untouched input waypoint) or a float64 one (perturbed or re-spaced); the reference's
  * arithmetic follows numpy's promotion per expression, so every waypoint carries a flag next to its float64 value.  The
- * random draws are the caller's: action [B, iters, random_iter, 2] (np.random.uniform(-eps, eps, 2) per trial) and either
+ * random draws are the caller's: action [B, iters, random_iter, dim] (np.random.uniform(-eps, eps, dim) per trial) and either
  * node_idx [B, iters, random_iter] (the reference's randint(1, len - 1), replayed) or u in [0, 1) with
  * node_idx = 1 + min(floor(u (len - 2)), len - 3) taken at the path's current length.
  *
@@ -484,26 +487,30 @@ int gnnmp_episode_frontier(const gnnmp_episode_graphs* graphs, const float* scor
  * ---------------------------------------------------------------------------------------- */
 typedef struct {
     int32_t n_paths, total_points;
-    int32_t dim;                 /* 2 (the point robot); anything else is GNNMP_ERR_DIMS      */
+    int32_t dim;                 /* the entry point's: 2 (point robot) or 3 (stick robot); else GNNMP_ERR_DIMS */
     int32_t width;               /* map cells per side, 1 .. max_width                        */
     int32_t iters, random_iter, prune_iter;
     int32_t ratio;               /* 1 = joint_smoother_ratio (waypoint count kept), 0 = joint_smoother (paths shrink) */
     int32_t stop;                /* 0 = run to the end; 1 = end after the last iteration's random stage; 2 = after its
                                     prune (before any re-spacing): the recorded stages of the reference               */
     const int32_t* path_ptr;     /* [n_paths + 1]                                             */
-    const double* paths;         /* [total_points, 2] float64 (float32 rows upcast)           */
+    const double* paths;         /* [total_points, dim] float64 (float32 rows upcast)         */
     const uint8_t* is32;         /* [total_points] 1 = float32 row; NULL = all of them        */
     const uint8_t* maps;         /* [n_paths, width, width] 0 = free                          */
-    const double* action;        /* [n_paths, iters, random_iter, 2]                          */
+    const double* action;        /* [n_paths, iters, random_iter, dim]                        */
     const int32_t* node_idx;     /* [n_paths, iters, random_iter] or NULL                     */
     const double* u;             /* [n_paths, iters, random_iter], read when node_idx is NULL */
 } gnnmp_oracle_smooth_batch;
-/* The kernel's per-path limits: waypoints per path and map cells per side. */
+/* The kernel's per-path limits, the same for both entry points: waypoints per path and map cells per side. */
 int gnnmp_oracle_smooth_limits(int32_t* max_waypoints, int32_t* max_width);
 /* out [total_points, 2] / out_is32 [total_points]: path b from row path_ptr[b], out_len[b] rows (the rest of its rows is
  * not written); checks [n_paths] = collision_check_count of the call; status [n_paths] as above. */
 int gnnmp_oracle_smooth(const gnnmp_oracle_smooth_batch* batch, double* out, uint8_t* out_is32, int32_t* out_len,
                         int64_t* checks, int32_t* status, void* hip_stream);
+/* The same for the stick robot: batch->dim == 3 (anything else is GNNMP_ERR_DIMS), paths / out [total_points, 3], action
+ * [n_paths, iters, random_iter, 3]; the argument checks are the point robot's, in the same order. */
+int gnnmp_stick_oracle_smooth(const gnnmp_oracle_smooth_batch* batch, double* out, uint8_t* out_is32, int32_t* out_len,
+                              int64_t* checks, int32_t* status, void* hip_stream);
 
 /* ------------------------------------------------------------------------------------------
  * Host-only helpers exported for the CPU test-suite (no device needed)

@@ -3,9 +3,10 @@
 under HIP events after a warm-up, against tests/oracle_smooth_host.py on a sample of the same paths on 16 CPU processes
 (scaled to the batch), plus collision checks per second and the split trials / prune (a run with prune_iter = 0 does the
 perturbation trials only).  The paths are the recorded fixtures' input paths (tests/golden/oracle_smooth_*.npz) repeated
-with their own maps; every repeat gets its own draws.
+with their own maps; every repeat gets its own draws.  ``--dim 3`` does the same for the stick robot: [sumP, 3] paths from
+tests/golden/oracle_smooth3_*.npz against tests/oracle_smooth3_host.py (seconds per path there: keep --host-sample small).
 
-    python tools/oracle_smooth_bench.py [--paths 2048 6000] [--host-sample 32] [--reps 5]
+    python tools/oracle_smooth_bench.py [--dim 2] [--paths 2048 6000] [--host-sample 32] [--reps 5]
 """
 import argparse
 import multiprocessing as mp
@@ -19,13 +20,14 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, 'tests'))
 
+import oracle_smooth3_host as H3  # noqa: E402
 import oracle_smooth_host as H  # noqa: E402
 
 
 def _host_one(args):
     path, maze, action, u = args
     t0 = time.perf_counter()
-    r = H.smooth(path, True, maze, action, u=u)
+    r = (H3 if path.shape[1] == 3 else H).smooth(path, True, maze, action, u=u)
     return time.perf_counter() - t0, r[2]
 
 
@@ -34,12 +36,13 @@ def main():
     ap.add_argument('--paths', type=int, nargs='+', default=[2048, 6000])
     ap.add_argument('--host-sample', type=int, default=32)
     ap.add_argument('--reps', type=int, default=5)
+    ap.add_argument('--dim', type=int, default=2, choices=(2, 3), help='2: point robot (default), 3: stick robot')
     a = ap.parse_args()
     import torch
     import gnnmp  # noqa: F401
     from gnnmp import oracle_smooth as OS
     dev = torch.device('cuda:0')
-    fix = {n: f for n, f in H.fixtures().items() if bool(f['ratio']) and bool(f['in32']) and len(f['path']) >= 5}
+    fix = {n: f for n, f in (H3 if a.dim == 3 else H).fixtures().items() if bool(f['ratio']) and bool(f['in32']) and len(f['path']) >= 5}
     names = sorted(fix)
     print('paths: the %d recorded input paths of >= 5 waypoints (%s), repeated' % (len(names), ', '.join(
         '%s:%d' % (n, len(fix[n]['path'])) for n in names)))
@@ -50,7 +53,7 @@ def main():
         maps = np.stack([fix[n]['map'] for n in pick])
         pt, mt = torch.from_numpy(paths).to(dev), torch.from_numpy(maps).to(dev)
         ptr_t = torch.from_numpy(ptr.astype(np.int32)).to(dev)
-        draws = OS.draw_device(B, generator=torch.Generator(device=dev).manual_seed(B))
+        draws = OS.draw_device(B, generator=torch.Generator(device=dev).manual_seed(B), dim=a.dim)
         res = {}
         for label, prune_iter in (('full', 100), ('trials only (prune_iter = 0)', 0)):
             r = OS.smooth(pt, ptr_t, mt, draws, prune_iter=prune_iter)            # warm-up
