@@ -79,6 +79,23 @@ class OracleSmoothBatch(ctypes.Structure):
                 ('action', ctypes.c_void_p), ('node_idx', ctypes.c_void_p), ('u', ctypes.c_void_p)]
 
 
+class TrainGeom(ctypes.Structure):
+    """gnnmp_train_geom: filled by gnnmp_train_geom_build, handed back to gnnmp_train_op (test hooks only)."""
+    _fields_ = [('n_graphs', ctypes.c_int32), ('config_size', ctypes.c_int32), ('n_pad', ctypes.c_int32), ('e_pad', ctypes.c_int32),
+                ('v', ctypes.c_void_p), ('goal', ctypes.c_void_p),
+                ('node_ptr', ctypes.c_void_p), ('node_ptr_pad', ctypes.c_void_p), ('ntile_graph', ctypes.c_void_p),
+                ('goal_node', ctypes.c_void_p), ('row_beg', ctypes.c_void_p), ('deg', ctypes.c_void_p),
+                ('csr', ctypes.c_void_p),
+                ('out_beg', ctypes.c_void_p), ('out_cnt', ctypes.c_void_p), ('out_cur', ctypes.c_void_p), ('out_slot', ctypes.c_void_p)]
+
+
+# operator numbers of gnnmp_train_op, in the order of the header's enum
+TRAIN_OPS = ('LINEAR', 'LINEAR_DX', 'LINEAR_DW', 'RELU_BWD', 'FILL', 'NODE_IN', 'EDGE_IN', 'H0', 'H0_BWD', 'CONCAT', 'SPLIT', 'MSG_IN',
+             'MSG_IN_BWD', 'POL_IN', 'POL_IN_BWD', 'SEGMENT_MAX', 'SEGMENT_MAX_BWD', 'SCORES_OUT', 'SCORES_IN', 'SM_NODES_IN', 'BN_FWD',
+             'BN_BWD', 'SM_MSG_IN', 'SM_MSG_IN_BWD', 'SM_SCATTER_ADD', 'SM_SCATTER_ADD_BWD', 'ADD_ROWS', 'SM_PATH_UPDATE',
+             'SM_PATH_UPDATE_BWD', 'SM_COORDS_BWD', 'SCALE')
+
+
 _lib = None
 
 
@@ -154,6 +171,13 @@ def lib():
     L.gnnmp_oracle_smooth_limits.argtypes = [c_int32_p, c_int32_p]
     L.gnnmp_oracle_smooth.argtypes = [ctypes.POINTER(OracleSmoothBatch), vp, vp, vp, vp, vp, vp]
     L.gnnmp_stick_oracle_smooth.argtypes = [ctypes.POINTER(OracleSmoothBatch), vp, vp, vp, vp, vp, vp]
+    L.gnnmp_train_geom_workspace_bytes.argtypes = [ctypes.POINTER(Batch), ctypes.c_int32, ctypes.POINTER(sz)]
+    L.gnnmp_train_geom_build.argtypes = [ctypes.POINTER(Batch), ctypes.c_int32, vp, sz, ctypes.POINTER(TrainGeom), vp]
+    L.gnnmp_train_op.argtypes = [ctypes.c_int, c_int64_p, ctypes.c_int, ctypes.POINTER(vp), ctypes.c_int, ctypes.POINTER(TrainGeom),
+                                 ctypes.c_float, vp]
+    L.gnnmp_train_dw_scratch_floats.restype = ctypes.c_int64
+    L.gnnmp_train_dw_scratch_floats.argtypes = [ctypes.c_int64, ctypes.c_int64, ctypes.c_int64]
+    L.gnnmp_train_op_path.argtypes = [ctypes.c_int, c_int64_p, ctypes.c_int]
     L.gnnmp_pack_a_tiles.restype = ctypes.c_int64
     L.gnnmp_pack_a_tiles.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp]
     L.gnnmp_pack_a_small.restype = ctypes.c_int64
@@ -260,6 +284,36 @@ class StatusWatch:
                 self.free.append(slot)
         if bad:
             raise RuntimeError('; '.join(bad) + ' -- the results of %s wrong' % ('that forward are' if len(bad) == 1 else 'those forwards are'))
+
+
+def train_op_raw(op, dims, bufs, geom=None, scalar=0.0, stream=None):
+    """gnnmp_train_op (a TEST HOOK: one launcher of the training path on the caller's device buffers) -> status code.
+    op: a name of TRAIN_OPS or a number; bufs: device addresses (int) or None."""
+    num = TRAIN_OPS.index(op) if isinstance(op, str) else int(op)
+    d = (ctypes.c_int64 * max(len(dims), 1))(*[int(x) for x in dims])
+    b = (ctypes.c_void_p * max(len(bufs), 1))(*[ctypes.c_void_p(x) if x else ctypes.c_void_p() for x in bufs])
+    return lib().gnnmp_train_op(num, d, len(dims), b, len(bufs), ctypes.byref(geom) if geom is not None else None,
+                                ctypes.c_float(scalar), stream)
+
+
+def train_op(op, dims, bufs, geom=None, scalar=0.0, stream=None):
+    check(train_op_raw(op, dims, bufs, geom, scalar, stream), 'gnnmp_train_op(%s)' % (op,))
+
+
+def train_op_path(op, R, K, O):
+    """'mfma' or 'plain': the kernel LINEAR / LINEAR_DX / LINEAR_DW dispatch to at these sizes."""
+    d = (ctypes.c_int64 * 3)(R, K, O)
+    rc = lib().gnnmp_train_op_path(TRAIN_OPS.index(op), d, 3)
+    if rc < 0:
+        check(rc, 'gnnmp_train_op_path')
+    return 'mfma' if rc else 'plain'
+
+
+def train_dw_scratch_floats(R, K, O):
+    n = lib().gnnmp_train_dw_scratch_floats(R, K, O)
+    if n < 0:
+        check(int(n), 'gnnmp_train_dw_scratch_floats')
+    return int(n)
 
 
 def manifest(kind, dims):

@@ -648,10 +648,11 @@ struct Carve {
 
 int round_up_i(int x, int m) { return (x + m - 1) / m * m; }
 
-bool carve(const gnnmp_explorer* h, const gnnmp_batch* b, Carve& c) {
+// by embed size and precision alone: the geometry test hook carves without a handle
+bool carve(int D, int mlp_dtype, const gnnmp_batch* b, Carve& c) {
     if (b->n_graphs < 1 || b->total_nodes < 0 || b->total_edges < 0 || b->total_obstacles < 0 || b->max_obstacles < 0)
         return false;
-    const int D = h->dims.embed_size, NT = D / 32;
+    const int NT = D / 32;
     c.D = D;
     c.G = b->n_graphs;
     const long long np = (long long)b->total_nodes + (long long)c.G * (kPad - 1);
@@ -661,7 +662,7 @@ bool carve(const gnnmp_explorer* h, const gnnmp_batch* b, Carve& c) {
     c.Epad = round_up_i((int)ep, kPad);
     c.ot_max = (b->max_obstacles + 31) / 32;
     if (c.ot_max < 1) c.ot_max = 1;
-    c.kv_stride = 2 * c.ot_max * NT * tile_unit(h->dims.mlp_dtype);
+    c.kv_stride = 2 * c.ot_max * NT * tile_unit(mlp_dtype);
     size_t o = 0;
     auto take = [&](size_t bytes) { const size_t r = o; o += (bytes + 255) & ~(size_t)255; return r; };
     c.node_ptr_pad = take(sizeof(int) * (c.G + 1));
@@ -690,13 +691,14 @@ bool carve(const gnnmp_explorer* h, const gnnmp_batch* b, Carve& c) {
     const size_t nrow = sizeof(float) * (size_t)c.Npad * D, erow = sizeof(float) * (size_t)c.Epad * D;
     c.XI = take(nrow); c.X = take(nrow); c.A = take(nrow); c.A2 = take(nrow); c.B = take(nrow); c.DN = take(nrow);
     c.H = take(nrow);
-    c.M0 = take(h->dims.mlp_dtype == GNNMP_BF16 ? 0 : nrow);      // node_f64_body -> node pre kernel (fp32-class modes)
+    c.M0 = take(mlp_dtype == GNNMP_BF16 ? 0 : nrow);      // node_f64_body -> node pre kernel (fp32-class modes)
     c.Ke = take(erow); c.PE = take(erow);
     c.kv_e = take(sizeof(float) * (size_t)c.G * 3 * c.kv_stride);
     c.kv_n = take(sizeof(float) * (size_t)c.G * 3 * c.kv_stride);
     c.total = o;
     return true;
 }
+bool carve(const gnnmp_explorer* h, const gnnmp_batch* b, Carve& c) { return carve(h->dims.embed_size, h->dims.mlp_dtype, b, c); }
 
 template <class T>
 T* at(void* ws, size_t off) { return reinterpret_cast<T*>(static_cast<char*>(ws) + off); }
@@ -811,6 +813,31 @@ extern "C" int gnnmp_explorer_status(const gnnmp_explorer* h, const gnnmp_batch*
 }
 
 namespace {
+// PrepParams of a batch over its carved workspace: the one place that fills them (the forward and the geometry test hook).
+// implicit: ONE graph given by its totals, the prefix arrays are written into the workspace by the prep stage itself.
+PrepParams prep_params(const Carve& c, const gnnmp_batch* b, int C, void* ws, bool implicit, int obs_cap, int* gstat) {
+    PrepParams q{};
+    q.G = c.G; q.E = b->total_edges; q.C = C;
+    q.edge_index = reinterpret_cast<const long long*>(b->edge_index);
+    q.single_out = implicit ? at<int>(ws, c.in_ptrs) : nullptr;
+    q.single_n = b->total_nodes; q.single_e = b->total_edges; q.single_o = b->total_obstacles;
+    q.node_ptr = implicit ? at<int>(ws, c.in_ptrs) : b->node_ptr;
+    q.edge_ptr = implicit ? at<int>(ws, c.in_ptrs) + 2 : b->edge_ptr;
+    q.v = b->v; q.goal = b->goal;
+    q.node_ptr_pad = at<int>(ws, c.node_ptr_pad); q.edge_ptr_pad = at<int>(ws, c.edge_ptr_pad);
+    q.dense_ptr = at<long long>(ws, c.dense_ptr);
+    q.deg = at<int>(ws, c.deg); q.cursor = at<int>(ws, c.cursor); q.row_beg = at<int>(ws, c.row_beg);
+    q.ntile_graph = at<int>(ws, c.ntile_graph); q.etile_graph = at<int>(ws, c.etile_graph);
+    q.csr = at<int4>(ws, c.csr);
+    q.goal_node = at<int>(ws, c.goal_node);
+    q.tile_meta = at<int>(ws, c.tile_meta); q.n_etiles = c.Epad / 32;
+    q.blk_span = at<int2>(ws, c.blk_span);
+    q.obs_ptr = implicit ? nullptr : b->obs_ptr;
+    q.obs_cap = obs_cap;
+    q.gstat = gstat;
+    return q;
+}
+
 // om_nodes / om_edges: optional [Npad, d] / [Epad, d] outputs of the attention stacks (training path); pre_only: stop
 // after the pre kernels (CSR, goal node, NF / EF are what the training path needs)
 int forward_impl(const gnnmp_explorer* h, const gnnmp_batch* b, int loop, int use_obstacles, float* edge_scores, float* dense,
@@ -838,24 +865,10 @@ int forward_impl(const gnnmp_explorer* h, const gnnmp_batch* b, int loop, int us
     const int* obs_ptr = implicit ? at<int>(ws, c.in_ptrs) + 4 : b->obs_ptr;
     {
     StageScope sc(prof, GNNMP_STAGE_PREP, st);
-    q.G = c.G; q.E = b->total_edges; q.C = C;
-    q.edge_index = reinterpret_cast<const long long*>(b->edge_index);
-    q.single_out = implicit ? at<int>(ws, c.in_ptrs) : nullptr;
-    q.single_n = b->total_nodes; q.single_e = b->total_edges; q.single_o = b->total_obstacles;
-    q.node_ptr = node_ptr; q.edge_ptr = edge_ptr; q.v = b->v; q.goal = b->goal;
-    q.node_ptr_pad = at<int>(ws, c.node_ptr_pad); q.edge_ptr_pad = at<int>(ws, c.edge_ptr_pad);
-    q.dense_ptr = at<long long>(ws, c.dense_ptr);
-    q.deg = at<int>(ws, c.deg); q.cursor = at<int>(ws, c.cursor); q.row_beg = at<int>(ws, c.row_beg);
-    q.ntile_graph = at<int>(ws, c.ntile_graph); q.etile_graph = at<int>(ws, c.etile_graph);
-    q.csr = at<int4>(ws, c.csr);
-    q.goal_node = at<int>(ws, c.goal_node);
-    q.tile_meta = at<int>(ws, c.tile_meta); q.n_etiles = c.Epad / 32;
-    q.blk_span = at<int2>(ws, c.blk_span);
-    q.obs_ptr = implicit ? nullptr : b->obs_ptr;
-    q.obs_cap = use_obstacles ? 32 * c.ot_max : 0x7fffffff;
     // the status words of this forward: the workspace region (read back by gnnmp_explorer_status), or -- gnnmp_explorer_forward_ex --
     // memory of the caller's that the device can write (pinned host memory: no copy behind the forward, the words simply arrive)
-    q.gstat = status_out ? reinterpret_cast<int*>(status_out) : at<int>(ws, c.gstat);
+    q = prep_params(c, b, C, ws, implicit, use_obstacles ? 32 * c.ot_max : 0x7fffffff,
+                    status_out ? reinterpret_cast<int*>(status_out) : at<int>(ws, c.gstat));
     HIP_TRY(launch_prep(q, c.Npad, c.Epad, at<int>(ws, c.prep_hist), st));
     // zero-fill of policy_output (model.py:148); sum_g N_g^2 is read from dense_ptr[G] on the device
     if (dense) HIP_TRY(launch_zero_dense(dense, q.dense_ptr + c.G, st));
@@ -2081,4 +2094,210 @@ extern "C" int gnnmp_oracle_smooth(const gnnmp_oracle_smooth_batch* b, double* o
 extern "C" int gnnmp_stick_oracle_smooth(const gnnmp_oracle_smooth_batch* b, double* out, uint8_t* out_is32,
                                          int32_t* out_len, int64_t* checks, int32_t* status, void* hip_stream) {
     return oracle_smooth_run(b, 3, out, out_is32, out_len, checks, status, hip_stream);
+}
+
+// =============================================================================================
+// TEST HOOKS for the training operators (gnnmp.h): one launcher of kernels.hpp per call on the caller's buffers.  Nothing
+// here restates a kernel or a dispatch rule -- the hooks only check arguments and forward them.
+// =============================================================================================
+namespace {
+
+struct TrainOpSpec {
+    int n_dims, n_bufs;
+    unsigned optional;      // bit i: bufs[i] may be NULL
+    bool geom;
+    int d_dim;              // index of D in dims for a geometry operator (-1: none)
+    unsigned flags;         // bit i: dims[i] is a 0 / 1 flag
+    unsigned zero_ok;       // bit i: dims[i] may be 0 (the launcher returns early, or the dimension is an index); every other size
+                            // must be >= 1 -- the launchers do not guard an empty grid (or N = 0 of BatchNorm)
+};
+
+const TrainOpSpec kTrainOps[GNNMP_TOP_COUNT] = {
+    /* LINEAR             */ {4, 4, 1u << 2, false, -1, 1u << 3, 1u},
+    /* LINEAR_DX          */ {4, 3, 0, false, -1, 1u << 3, 1u},
+    /* LINEAR_DW          */ {3, 5, 1u << 3, false, -1, 0, 1u},
+    /* RELU_BWD           */ {1, 2, 0, false, -1, 0, 0},
+    /* FILL               */ {1, 1, 0, false, -1, 0, 1u},
+    /* NODE_IN            */ {0, 1, 0, true, -1, 0, 0},
+    /* EDGE_IN            */ {0, 1, 0, true, -1, 0, 0},
+    /* H0                 */ {1, 2, 0, true, 0, 0, 0},
+    /* H0_BWD             */ {1, 2, 0, true, 0, 0, 0},
+    /* CONCAT             */ {3, 5, 0xe, false, -1, 0, 0},       // a1 .. a3: required up to `parts` (checked below)
+    /* SPLIT              */ {5, 2, 0, false, -1, 1u << 4, 1u << 3},
+    /* MSG_IN             */ {1, 4, 0, true, 0, 0, 0},
+    /* MSG_IN_BWD         */ {1, 3, 0, true, 0, 0, 0},
+    /* POL_IN             */ {1, 3, 0, true, 0, 0, 0},
+    /* POL_IN_BWD         */ {1, 2, 0, true, 0, 0, 0},
+    /* SEGMENT_MAX        */ {1, 3, 0, true, 0, 0, 0},
+    /* SEGMENT_MAX_BWD    */ {2, 3, 0, false, -1, 0, 0},
+    /* SCORES_OUT         */ {0, 2, 0, true, -1, 0, 0},
+    /* SCORES_IN          */ {0, 2, 0, true, -1, 0, 0},
+    /* SM_NODES_IN        */ {4, 4, 0x6, false, -1, 0, 6u},
+    /* BN_FWD             */ {3, 5, 0, false, -1, 1u << 2, 0},
+    /* BN_BWD             */ {2, 7, 0, false, -1, 0, 0},
+    /* SM_MSG_IN          */ {2, 5, 0, false, -1, 0, 0},
+    /* SM_MSG_IN_BWD      */ {2, 5, 0, false, -1, 0, 0},
+    /* SM_SCATTER_ADD     */ {2, 4, 0, false, -1, 0, 0},
+    /* SM_SCATTER_ADD_BWD */ {2, 4, 0, false, -1, 0, 0},
+    /* ADD_ROWS           */ {1, 3, 0, false, -1, 0, 0},
+    /* SM_PATH_UPDATE     */ {2, 3, 0, false, -1, 0, 0},
+    /* SM_PATH_UPDATE_BWD */ {2, 3, 0, false, -1, 0, 0},
+    /* SM_COORDS_BWD      */ {2, 2, 0, false, -1, 0, 0},
+    /* SCALE              */ {1, 2, 0, false, -1, 0, 1u},
+};
+
+int train_dims_ok(const TrainOpSpec& s, const int64_t* dims, int n_dims) {
+    if (n_dims != s.n_dims || (n_dims > 0 && !dims)) return GNNMP_ERR_ARG;
+    for (int i = 0; i < n_dims; ++i) {
+        if (dims[i] < 0 || dims[i] > 0x7fffffff) return GNNMP_ERR_ARG;
+        if (((s.flags >> i) & 1) && dims[i] > 1) return GNNMP_ERR_ARG;
+        if (dims[i] == 0 && !(((s.flags | s.zero_ok) >> i) & 1)) return GNNMP_ERR_ARG;
+    }
+    return GNNMP_OK;
+}
+
+int train_geom_ok(const gnnmp_train_geom* g) {
+    if (!g) return GNNMP_ERR_NULL;
+    if (g->n_graphs < 1 || g->config_size < 1 || g->n_pad < 1 || g->e_pad < 1) return GNNMP_ERR_ARG;
+    if (g->n_pad % 32 || g->e_pad % 32) return GNNMP_ERR_DIMS;
+    if (!g->v || !g->goal || !g->node_ptr || !g->node_ptr_pad || !g->ntile_graph || !g->goal_node || !g->row_beg || !g->deg ||
+        !g->csr || !g->out_beg || !g->out_cnt || !g->out_cur || !g->out_slot)
+        return GNNMP_ERR_NULL;
+    return GNNMP_OK;
+}
+
+TrainGeom to_train_geom(const gnnmp_train_geom* g) {
+    TrainGeom q;
+    q.G = g->n_graphs; q.C = g->config_size; q.Npad = g->n_pad; q.Epad = g->e_pad;
+    q.v = g->v; q.goal = g->goal; q.node_ptr = g->node_ptr; q.node_ptr_pad = g->node_ptr_pad; q.ntile_graph = g->ntile_graph;
+    q.goal_node = g->goal_node; q.row_beg = g->row_beg; q.deg = g->deg; q.csr = reinterpret_cast<const int4*>(g->csr);
+    q.out_beg = g->out_beg; q.out_cnt = g->out_cnt; q.out_cur = g->out_cur; q.out_slot = g->out_slot;
+    return q;
+}
+
+// the explorer's own carve (CSR, padded pointers, goal node, status words), then the out lists of the training forward
+struct GeomCarve { Carve c; size_t obeg, ocnt, ocur, oslot, total; };
+bool geom_carve(const gnnmp_batch* b, int C, GeomCarve& g) {
+    (void)C;
+    if (!carve(32, GNNMP_F32, b, g.c)) return false;        // the index arrays do not depend on the embed size
+    size_t o = g.c.total;
+    auto take = [&](size_t bytes) { const size_t r = o; o += (bytes + 255) & ~(size_t)255; return r; };
+    g.obeg = take(sizeof(int) * (size_t)g.c.Npad); g.ocnt = take(sizeof(int) * (size_t)g.c.Npad);
+    g.ocur = take(sizeof(int) * (size_t)g.c.Npad); g.oslot = take(sizeof(int) * (size_t)g.c.Epad);
+    g.total = o;
+    return true;
+}
+
+}  // namespace
+
+extern "C" int gnnmp_train_geom_workspace_bytes(const gnnmp_batch* shape, int32_t config_size, size_t* bytes) {
+    if (!shape || !bytes) return GNNMP_ERR_NULL;
+    if (config_size < 1) return GNNMP_ERR_ARG;
+    GeomCarve g;
+    if (!geom_carve(shape, config_size, g)) return GNNMP_ERR_ARG;
+    *bytes = g.total;
+    return GNNMP_OK;
+}
+
+extern "C" int gnnmp_train_geom_build(const gnnmp_batch* b, int32_t config_size, void* ws, size_t ws_bytes,
+                                      gnnmp_train_geom* out, void* hip_stream) {
+    if (!b || !ws || !out) return GNNMP_ERR_NULL;
+    if (config_size < 1) return GNNMP_ERR_ARG;
+    GeomCarve g;
+    if (!geom_carve(b, config_size, g)) return GNNMP_ERR_ARG;
+    if (!b->v || !b->goal || !b->node_ptr || !b->edge_ptr || (b->total_edges > 0 && !b->edge_index)) return GNNMP_ERR_NULL;
+    if (ws_bytes < g.total || (reinterpret_cast<uintptr_t>(ws) & 255)) return GNNMP_ERR_WORKSPACE;
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    const Carve& c = g.c;
+    // obstacles are not part of the geometry: obs_ptr may be NULL (the prep stage then takes every graph's count as 0)
+    const PrepParams q = prep_params(c, b, config_size, ws, false, 0x7fffffff, at<int>(ws, c.gstat));
+    HIP_TRY(launch_prep(q, c.Npad, c.Epad, at<int>(ws, c.prep_hist), st));
+    HIP_TRY(t_sort_csr(c.Npad, q.csr, q.row_beg, q.deg, st));
+    out->n_graphs = c.G; out->config_size = config_size; out->n_pad = c.Npad; out->e_pad = c.Epad;
+    out->v = b->v; out->goal = b->goal; out->node_ptr = b->node_ptr;
+    out->node_ptr_pad = q.node_ptr_pad; out->ntile_graph = q.ntile_graph; out->goal_node = q.goal_node;
+    out->row_beg = q.row_beg; out->deg = q.deg; out->csr = at<int32_t>(ws, c.csr);
+    out->out_beg = at<int32_t>(ws, g.obeg); out->out_cnt = at<int32_t>(ws, g.ocnt);
+    out->out_cur = at<int32_t>(ws, g.ocur); out->out_slot = at<int32_t>(ws, g.oslot);
+    HIP_TRY(t_out_csr(to_train_geom(out), st));
+    return GNNMP_OK;
+}
+
+extern "C" int64_t gnnmp_train_dw_scratch_floats(int64_t R, int64_t K, int64_t O) {
+    if (R < 0 || K < 0 || O < 0 || R > 0x7fffffff || K > 0x7fffffff || O > 0x7fffffff) return GNNMP_ERR_ARG;
+    return (int64_t)t_linear_dw_scratch_floats((int)R, (int)K, (int)O);
+}
+
+extern "C" int gnnmp_train_op_path(int op, const int64_t* dims, int n_dims) {
+    if (op != GNNMP_TOP_LINEAR && op != GNNMP_TOP_LINEAR_DX && op != GNNMP_TOP_LINEAR_DW) return GNNMP_ERR_ARG;
+    if (n_dims < 3 || !dims) return GNNMP_ERR_ARG;
+    for (int i = 0; i < 3; ++i)
+        if (dims[i] < 0 || dims[i] > 0x7fffffff) return GNNMP_ERR_ARG;
+    const int K = (int)dims[1], O = (int)dims[2];
+    return (op == GNNMP_TOP_LINEAR ? t_linear_mfma(K, O) : op == GNNMP_TOP_LINEAR_DX ? t_linear_dx_mfma(K, O) : t_linear_dw_mfma(K, O)) ? 1 : 0;
+}
+
+extern "C" int gnnmp_train_op(int op, const int64_t* dims, int n_dims, void* const* bufs, int n_bufs,
+                              const gnnmp_train_geom* geom, float scalar, void* hip_stream) {
+    if (op < 0 || op >= GNNMP_TOP_COUNT) return GNNMP_ERR_ARG;
+    const TrainOpSpec& s = kTrainOps[op];
+    int rc = train_dims_ok(s, dims, n_dims);
+    if (rc != GNNMP_OK) return rc;
+    if (n_bufs != s.n_bufs) return GNNMP_ERR_ARG;
+    if (!bufs) return GNNMP_ERR_NULL;
+    auto d = [&](int i) { return (int)dims[i]; };
+    unsigned optional = s.optional;
+    if (op == GNNMP_TOP_CONCAT) {
+        if (d(2) < 1 || d(2) > 4) return GNNMP_ERR_ARG;
+        optional = (0xfu << d(2)) & 0xfu;                       // parts beyond `parts` are not read
+    }
+    if (op == GNNMP_TOP_SPLIT && (d(2) < 1 || d(2) > 4 || d(3) >= d(2))) return GNNMP_ERR_ARG;
+    if (op == GNNMP_TOP_SM_NODES_IN) optional = (d(1) == 0 ? 2u : 0u) | (d(2) == 0 ? 4u : 0u);      // no rows: never read
+    for (int i = 0; i < n_bufs; ++i)
+        if (!bufs[i] && !((optional >> i) & 1)) return GNNMP_ERR_NULL;
+    TrainGeom q{};
+    if (s.geom) {
+        rc = train_geom_ok(geom);
+        if (rc != GNNMP_OK) return rc;
+        if (s.d_dim >= 0 && d(s.d_dim) != 32 && d(s.d_dim) != 64) return GNNMP_ERR_DIMS;
+        q = to_train_geom(geom);
+    }
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    auto F = [&](int i) { return static_cast<float*>(bufs[i]); };
+    auto I = [&](int i) { return static_cast<int*>(bufs[i]); };
+    switch (op) {
+        case GNNMP_TOP_LINEAR: HIP_TRY(t_linear(d(0), d(1), d(2), F(0), F(1), F(2), F(3), d(3) != 0, st)); break;
+        case GNNMP_TOP_LINEAR_DX: HIP_TRY(t_linear_dx(d(0), d(1), d(2), F(0), F(1), F(2), d(3) != 0, st)); break;
+        case GNNMP_TOP_LINEAR_DW: HIP_TRY(t_linear_dw(d(0), d(1), d(2), F(0), F(1), F(2), F(3), F(4), st)); break;
+        case GNNMP_TOP_RELU_BWD: HIP_TRY(t_relu_bwd((size_t)d(0), F(0), F(1), st)); break;
+        case GNNMP_TOP_FILL: HIP_TRY(t_fill((size_t)d(0), F(0), scalar, st)); break;
+        case GNNMP_TOP_NODE_IN: HIP_TRY(t_node_in(q, F(0), st)); break;
+        case GNNMP_TOP_EDGE_IN: HIP_TRY(t_edge_in(q, F(0), st)); break;
+        case GNNMP_TOP_H0: HIP_TRY(t_h0(q, d(0), F(0), F(1), st)); break;
+        case GNNMP_TOP_H0_BWD: HIP_TRY(t_h0_bwd(q, d(0), F(0), F(1), st)); break;
+        case GNNMP_TOP_CONCAT: HIP_TRY(t_concat(d(0), d(1), d(2), F(0), F(1), F(2), F(3), F(4), st)); break;
+        case GNNMP_TOP_SPLIT: HIP_TRY(t_split(d(0), d(1), d(2), d(3), F(0), F(1), d(4) != 0, st)); break;
+        case GNNMP_TOP_MSG_IN: HIP_TRY(t_msg_in(q, d(0), F(0), F(1), F(2), F(3), st)); break;
+        case GNNMP_TOP_MSG_IN_BWD: HIP_TRY(t_msg_in_bwd(q, d(0), F(0), F(1), F(2), st)); break;
+        case GNNMP_TOP_POL_IN: HIP_TRY(t_pol_in(q, d(0), F(0), F(1), F(2), st)); break;
+        case GNNMP_TOP_POL_IN_BWD: HIP_TRY(t_pol_in_bwd(q, d(0), F(0), F(1), st)); break;
+        case GNNMP_TOP_SEGMENT_MAX: HIP_TRY(t_segment_max(q, d(0), F(0), F(1), I(2), st)); break;
+        case GNNMP_TOP_SEGMENT_MAX_BWD: HIP_TRY(t_segment_max_bwd(d(0), d(1), F(0), I(1), F(2), st)); break;
+        case GNNMP_TOP_SCORES_OUT: HIP_TRY(t_scores_out(q, F(0), F(1), st)); break;
+        case GNNMP_TOP_SCORES_IN: HIP_TRY(t_scores_in(q, F(0), F(1), st)); break;
+        case GNNMP_TOP_SM_NODES_IN: HIP_TRY(t_sm_nodes_in(d(0), d(1), d(2), d(3), scalar, F(0), F(1), F(2), F(3), st)); break;
+        case GNNMP_TOP_BN_FWD: HIP_TRY(t_bn_fwd(d(0), d(1), F(0), F(1), F(2), F(3), F(4), d(2) != 0, st)); break;
+        case GNNMP_TOP_BN_BWD: HIP_TRY(t_bn_bwd(d(0), d(1), F(0), F(1), F(2), F(3), F(4), F(5), F(6), st)); break;
+        case GNNMP_TOP_SM_MSG_IN: HIP_TRY(t_sm_msg_in(I(0), d(0), I(1), I(2), F(3), F(4), d(1), st)); break;
+        case GNNMP_TOP_SM_MSG_IN_BWD: HIP_TRY(t_sm_msg_in_bwd(I(0), d(0), I(1), I(2), F(3), F(4), d(1), st)); break;
+        case GNNMP_TOP_SM_SCATTER_ADD: HIP_TRY(t_sm_scatter_add(I(0), d(0), I(1), F(2), F(3), d(1), st)); break;
+        case GNNMP_TOP_SM_SCATTER_ADD_BWD: HIP_TRY(t_sm_scatter_add_bwd(I(0), d(0), I(1), F(2), F(3), d(1), st)); break;
+        case GNNMP_TOP_ADD_ROWS: HIP_TRY(t_add_rows((size_t)d(0), F(0), F(1), F(2), st)); break;
+        case GNNMP_TOP_SM_PATH_UPDATE: HIP_TRY(t_sm_path_update(d(0), d(1), F(0), F(1), F(2), st)); break;
+        case GNNMP_TOP_SM_PATH_UPDATE_BWD: HIP_TRY(t_sm_path_update_bwd(d(0), d(1), F(0), F(1), F(2), st)); break;
+        case GNNMP_TOP_SM_COORDS_BWD: HIP_TRY(t_sm_coords_bwd(d(0), d(1), F(0), F(1), st)); break;
+        case GNNMP_TOP_SCALE: HIP_TRY(t_scale(d(0), scalar, F(0), F(1), st)); break;
+        default: return GNNMP_ERR_ARG;
+    }
+    return GNNMP_OK;
 }

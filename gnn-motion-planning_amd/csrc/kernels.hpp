@@ -277,6 +277,10 @@ struct TrainGeom {
 hipError_t t_out_csr(const TrainGeom& q, hipStream_t st);
 hipError_t t_sort_csr(int Npad, int4* csr, const int* row_beg, const int* deg, hipStream_t st);
 size_t t_linear_dw_scratch_floats(int R, int K, int O);
+// the launchers' own dispatch: true = the fp32 MFMA kernel, false = the plain one (also what the test hooks report)
+bool t_linear_mfma(int K, int O);
+bool t_linear_dx_mfma(int K, int O);
+bool t_linear_dw_mfma(int K, int O);
 hipError_t t_linear(int R, int K, int O, const float* X, const float* W, const float* b, float* Y, bool relu, hipStream_t st);
 hipError_t t_linear_dx(int R, int K, int O, const float* dY, const float* W, float* dX, bool accumulate, hipStream_t st);
 hipError_t t_linear_dw(int R, int K, int O, const float* dY, const float* X, float* dW, float* db, float* scratch, hipStream_t st);

@@ -509,9 +509,13 @@ __global__ void scores_in_kernel(TrainGeom q, const float* __restrict__ d_out, f
 // ---------------------------------------------------------------------------------------------------------------------
 static inline unsigned blocks(size_t n) { return (unsigned)((n + 255) / 256); }
 
+bool t_linear_mfma(int, int O) { return O >= 8; }       // narrow outputs (policy.4: one column) stay on the plain kernel
+bool t_linear_dx_mfma(int K, int O) { return O >= 8 && K >= 8; }
+bool t_linear_dw_mfma(int K, int O) { return O >= 8 && K >= 4; }
+
 hipError_t t_linear(int R, int K, int O, const float* X, const float* W, const float* b, float* Y, bool relu, hipStream_t st) {
     if (R <= 0) return hipSuccess;
-    if (O >= 8) {       // narrow outputs (policy.4: one column) stay on the plain kernel
+    if (t_linear_mfma(K, O)) {
         const size_t jobs = (size_t)((R + 31) / 32) * ((O + 31) / 32);
         hipLaunchKernelGGL(rows_linear_mfma_kernel, dim3((unsigned)((jobs + 3) / 4)), dim3(256), 0, st, R, K, O, X, W, b, Y, relu ? 1 : 0);
         TRAIN_LAUNCH_CHECK();
@@ -523,7 +527,7 @@ hipError_t t_linear(int R, int K, int O, const float* X, const float* W, const f
 }
 hipError_t t_linear_dx(int R, int K, int O, const float* dY, const float* W, float* dX, bool accumulate, hipStream_t st) {
     if (R <= 0) return hipSuccess;
-    if (O >= 8 && K >= 8) {
+    if (t_linear_dx_mfma(K, O)) {
         const size_t jobs = (size_t)((R + 31) / 32) * ((K + 31) / 32);
         hipLaunchKernelGGL(rows_linear_dx_mfma_kernel, dim3((unsigned)((jobs + 3) / 4)), dim3(256), 0, st, R, K, O, dY, W, dX, accumulate ? 1 : 0);
         TRAIN_LAUNCH_CHECK();
@@ -537,7 +541,7 @@ size_t t_linear_dw_scratch_floats(int R, int K, int O) { return (size_t)((R + kD
 hipError_t t_linear_dw(int R, int K, int O, const float* dY, const float* X, float* dW, float* db, float* scratch, hipStream_t st) {
     if (R <= 0) return hipSuccess;
     int nblk = (R + kDwRows - 1) / kDwRows;
-    if (O >= 8 && K >= 4) {
+    if (t_linear_dw_mfma(K, O)) {
         nblk = (R + kDwRowsM - 1) / kDwRowsM;             // fewer, larger chunks: the scratch sized for kDwRows covers them
         const int pairs = ((O + 31) / 32) * ((K + 1 + 31) / 32);
         hipLaunchKernelGGL(rows_linear_dw_mfma_kernel, dim3(nblk, (pairs + kDwPairs - 1) / kDwPairs), dim3(256), 0, st, R, K, O, dY, X, scratch);
@@ -675,30 +679,38 @@ __global__ void sm_nodes_in_kernel(int P, int F, int Co, int C, float scale, con
 }
 
 // BatchNorm1d, training mode, one block per feature: y = (x - mean) * invstd * gamma + beta with the batch's biased
-// variance; stats[f] = mean, stats[D + f] = invstd, stats[2 D + f] = unbiased variance (for the running-stat update)
+// variance; stats[f] = mean, stats[D + f] = invstd, stats[2 D + f] = unbiased variance (for the running-stat update).
+// The column mean and the deviations from it are carried in DOUBLE: a float32 mean is only good to |mean| 2^-24, and a column
+// with |mean| / std = 1e5 (coordinates far from the origin) then loses three digits of y, dgamma and dx -- torch's CPU batch
+// norm accumulates in double for the same reason (tests/test_train_ops_gpu.py, the `cancel` inputs).  The backward recomputes
+// the double mean instead of reading the rounded one from `stats`; a column is a few thousand values.
+// Cost, measured on the MI355X against the float32 kernels: forward + backward at N = 1020, D = 128 back to back 15.6 us before and
+// after (two launches, launch-bound); the smoother's optimizer step of tools/train_bench.py 22.2 - 22.4 ms before and after.
+__device__ __forceinline__ double bn_block_sum(double* red, double v) {           // fixed tree: the same bits on every run
+    const int tid = threadIdx.x;
+    __syncthreads();                                                               // the previous sum has been read
+    red[tid] = v;
+    __syncthreads();
+    for (int off = 128; off > 0; off >>= 1) { if (tid < off) red[tid] += red[tid + off]; __syncthreads(); }
+    return red[0];
+}
 __global__ __launch_bounds__(256) void bn_train_fwd_kernel(int N, int D, const float* __restrict__ x, const float* __restrict__ gamma,
                                                            const float* __restrict__ beta, float eps, float* __restrict__ y,
                                                            float* __restrict__ stats, int relu) {
-    __shared__ float red[256];
+    __shared__ double red[256];
     const int f = blockIdx.x, tid = threadIdx.x;
-    float s = 0.f;
-    for (int n = tid; n < N; n += 256) s += x[(size_t)n * D + f];
-    red[tid] = s;
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) { if (tid < off) red[tid] += red[tid + off]; __syncthreads(); }
-    const float mean = red[0] / N;
-    __syncthreads();
-    float q = 0.f;
-    for (int n = tid; n < N; n += 256) { const float dlt = x[(size_t)n * D + f] - mean; q = fmaf(dlt, dlt, q); }
-    red[tid] = q;
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) { if (tid < off) red[tid] += red[tid + off]; __syncthreads(); }
-    const float var = red[0] / N;
-    const float invstd = 1.0f / sqrtf(var + eps);
-    if (tid == 0) { stats[f] = mean; stats[D + f] = invstd; stats[2 * D + f] = N > 1 ? red[0] / (N - 1) : var; }
-    const float g = gamma[f], b = beta[f];
+    double s = 0.0;
+    for (int n = tid; n < N; n += 256) s += (double)x[(size_t)n * D + f];
+    const double mean = bn_block_sum(red, s) / N;
+    double q = 0.0;
+    for (int n = tid; n < N; n += 256) { const double dlt = (double)x[(size_t)n * D + f] - mean; q = fma(dlt, dlt, q); }
+    const double ss = bn_block_sum(red, q);
+    const double var = ss / N;
+    const double invstd = 1.0 / sqrt(var + (double)eps);
+    if (tid == 0) { stats[f] = (float)mean; stats[D + f] = (float)invstd; stats[2 * D + f] = (float)(N > 1 ? ss / (N - 1) : var); }
+    const double g = gamma[f], b = beta[f];
     for (int n = tid; n < N; n += 256) {
-        const float val = (x[(size_t)n * D + f] - mean) * invstd * g + b;
+        const float val = (float)(((double)x[(size_t)n * D + f] - mean) * invstd * g + b);
         y[(size_t)n * D + f] = (relu && val < 0.f) ? 0.f : val;
     }
 }
@@ -706,24 +718,24 @@ __global__ __launch_bounds__(256) void bn_train_fwd_kernel(int N, int D, const f
 __global__ __launch_bounds__(256) void bn_train_bwd_kernel(int N, int D, const float* __restrict__ x, const float* __restrict__ dy,
                                                            const float* __restrict__ gamma, const float* __restrict__ stats,
                                                            float* __restrict__ dx, float* __restrict__ dgamma, float* __restrict__ dbeta) {
-    __shared__ float r0[256], r1[256];
+    __shared__ double red[256];
     const int f = blockIdx.x, tid = threadIdx.x;
-    const float mean = stats[f], invstd = stats[D + f];
-    float s0 = 0.f, s1 = 0.f;
+    double s = 0.0;
+    for (int n = tid; n < N; n += 256) s += (double)x[(size_t)n * D + f];
+    const double mean = bn_block_sum(red, s) / N;
+    const double invstd = stats[D + f];
+    double s0 = 0.0, s1 = 0.0;
     for (int n = tid; n < N; n += 256) {
-        const float g = dy[(size_t)n * D + f];
+        const double g = dy[(size_t)n * D + f];
         s0 += g;
-        s1 = fmaf(g, (x[(size_t)n * D + f] - mean) * invstd, s1);
+        s1 = fma(g, ((double)x[(size_t)n * D + f] - mean) * invstd, s1);
     }
-    r0[tid] = s0; r1[tid] = s1;
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) { if (tid < off) { r0[tid] += r0[tid + off]; r1[tid] += r1[tid + off]; } __syncthreads(); }
-    const float sum_dy = r0[0], sum_dyx = r1[0];
-    if (tid == 0) { dgamma[f] += sum_dyx; dbeta[f] += sum_dy; }        // one block per feature: the only writer of slot f
-    const float k = gamma[f] * invstd / N;
+    const double sum_dy = bn_block_sum(red, s0), sum_dyx = bn_block_sum(red, s1);
+    if (tid == 0) { dgamma[f] += (float)sum_dyx; dbeta[f] += (float)sum_dy; }        // one block per feature: the only writer of slot f
+    const double k = (double)gamma[f] * invstd / N;
     for (int n = tid; n < N; n += 256) {
-        const float xhat = (x[(size_t)n * D + f] - mean) * invstd;
-        dx[(size_t)n * D + f] = k * (N * dy[(size_t)n * D + f] - sum_dy - xhat * sum_dyx);
+        const double xhat = ((double)x[(size_t)n * D + f] - mean) * invstd;
+        dx[(size_t)n * D + f] = (float)(k * (N * (double)dy[(size_t)n * D + f] - sum_dy - xhat * sum_dyx));
     }
 }
 

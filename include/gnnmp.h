@@ -210,8 +210,9 @@ int gnnmp_explorer_debug_tap(const gnnmp_explorer* h, const gnnmp_batch* batch, 
  * grad: DEVICE buffer of gnnmp_explorer_grad_floats(h) floats in MANIFEST order (the layout of the weight blob given to
  * gnnmp_explorer_create); entries of frozen tensors are zero.  The handle must be GNNMP_F32.  The same workspace
  * (>= gnnmp_explorer_train_workspace_bytes, 256-byte aligned) must be passed to forward and backward, untouched in
- * between; both enqueue on hip_stream and never synchronise.  Weight-gradient sums use float atomics: bit patterns may
- * differ from run to run in the last digits. */
+ * between; both enqueue on hip_stream and never synchronise.  No kernel of the training path uses float atomics and every
+ * sum has a fixed order (CSR segments are sorted by caller column first): the same inputs give the same gradient bits on
+ * every run. */
 int64_t gnnmp_explorer_grad_floats(const gnnmp_explorer* h);
 int gnnmp_explorer_train_workspace_bytes(const gnnmp_explorer* h, const gnnmp_batch* shape, int loop, size_t* bytes);
 int gnnmp_explorer_train_forward(const gnnmp_explorer* h, const gnnmp_batch* batch, int loop, int use_obstacles,
@@ -511,6 +512,89 @@ int gnnmp_oracle_smooth(const gnnmp_oracle_smooth_batch* batch, double* out, uin
  * [n_paths, iters, random_iter, 3]; the argument checks are the point robot's, in the same order. */
 int gnnmp_stick_oracle_smooth(const gnnmp_oracle_smooth_batch* batch, double* out, uint8_t* out_is32, int32_t* out_len,
                               int64_t* checks, int32_t* status, void* hip_stream);
+
+/* ------------------------------------------------------------------------------------------
+ * TEST HOOKS for the training operators   (train_kernels.hip; no product module calls these)
+ * ------------------------------------------------------------------------------------------
+ * gnnmp_train_op runs ONE launcher of the training path -- the very function the training entry points above call, so its
+ * dispatch between the MFMA and the plain kernels is what runs -- on caller-owned device buffers, on hip_stream, without
+ * synchronising.  dims / bufs per operator (a buffer marked ? may be NULL; `geom` is read by the operators marked G and
+ * ignored by the others; `scalar` by FILL (value), SCALE (factor) and SM_NODES_IN (scale)):
+ *
+ *   LINEAR           [R, K, O, relu]             X [R,K], W [O,K], b? [O], Y [R,O]          Y = act(X W^T + b)
+ *   LINEAR_DX        [R, K, O, accumulate]       dY [R,O], W [O,K], dX [R,K]                dX (+)= dY W
+ *   LINEAR_DW        [R, K, O]                   dY, X, dW [O,K], db? [O], scratch          dW += dY^T X, db += sum_r dY;
+ *                                                scratch: gnnmp_train_dw_scratch_floats(R, K, O) floats
+ *   RELU_BWD         [n]                         y, dy                                      dy = 0 where y <= 0
+ *   FILL             [n]                         x
+ *   NODE_IN       G  []                          out [Npad, 4C]
+ *   EDGE_IN       G  []                          out [Epad, 2C]
+ *   H0            G  [D]                         goal_encoder [D], H0 [Npad, D]
+ *   H0_BWD        G  [D]                         dH0 [Npad, D], d_goal_encoder [D] (+=)
+ *   CONCAT           [R, D, parts]               a0 .. a3 (the first `parts` are read), out [R, parts D]
+ *   SPLIT            [R, D, parts, part, accumulate]   d_in [R, parts D], dst [R, D]
+ *   MSG_IN        G  [D]                         X [Npad,D], EF [Epad,D], EC [Epad,D], out [Epad, 5D]
+ *   MSG_IN_BWD    G  [D]                         dZ [Epad,5D], dX [Npad,D] (+=), dEC [Epad,D] (+=)
+ *   POL_IN        G  [D]                         Dn [Npad,D], EF [Epad,D], out [Epad,3D]
+ *   POL_IN_BWD    G  [D]                         dP [Epad,3D], dDn [Npad,D] (+=)
+ *   SEGMENT_MAX   G  [D]                         M [Epad,D], A [Npad,D], arg [Npad,D] int32
+ *   SEGMENT_MAX_BWD  [Npad, D]                   dA [Npad,D], arg, dM [Epad,D] (written at arg only)
+ *   SCORES_OUT    G  []                          slot_scores [Epad], out [total_edges]
+ *   SCORES_IN     G  []                          d_out [total_edges], d_slot [Epad]
+ *   SM_NODES_IN      [P, F, Co, C]               cur [P,C], free_pts? [F,C], collided? [Co,C], out [P+F+Co, C+3]
+ *   BN_FWD           [N, D, relu]                x [N,D], gamma [D], beta [D], y [N,D], stats [3,D]
+ *   BN_BWD           [N, D]                      x, dy, gamma, stats, dx [N,D], dgamma [D] (+=), dbeta [D] (+=)
+ *   SM_MSG_IN        [D, cap]                    n_edges (one int32), e_src, e_dst (int32), X, out [cap, 3D]
+ *   SM_MSG_IN_BWD    [D, n_rows]                 n_edges, e_src, e_dst, dZ [cap,3D], dX [n_rows,D] (+=)
+ *   SM_SCATTER_ADD   [D, n_rows]                 n_edges, e_dst, M [cap,D], S [n_rows,D] (+=)
+ *   SM_SCATTER_ADD_BWD [D, cap]                  n_edges, e_dst, dS [n_rows,D], dM [cap,D]
+ *   ADD_ROWS         [n]                         a, b, out
+ *   SM_PATH_UPDATE   [P, C]                      prev, proposal, next [P,C]
+ *   SM_PATH_UPDATE_BWD [P, C]                    d_next, d_proposal, d_prev
+ *   SM_COORDS_BWD    [P, C]                      dXin [., C+3], d_prev [P,C] (+=)
+ *   SCALE            [n]                         x, y
+ *
+ * Everything is validated before any launch: unknown op, n_dims / n_bufs not the operator's, a negative size (or one
+ * beyond int32), a size of 0 (the launchers do not guard an empty grid; only R of the three LINEAR operators, n of FILL and
+ * SCALE, and F / Co of SM_NODES_IN may be 0), a flag that is not 0 / 1, parts outside 1 .. 4 or part outside [0, parts),
+ * a geometry with n_graphs, config_size, n_pad or e_pad below 1 -> GNNMP_ERR_ARG; a required buffer, or a geometry or one
+ * of its arrays, NULL -> GNNMP_ERR_NULL; D of a geometry operator not an embed size of the explorer (32, 64), or a
+ * geometry whose n_pad / e_pad is not a multiple of 32 -> GNNMP_ERR_DIMS. */
+enum {
+    GNNMP_TOP_LINEAR = 0, GNNMP_TOP_LINEAR_DX, GNNMP_TOP_LINEAR_DW, GNNMP_TOP_RELU_BWD, GNNMP_TOP_FILL,
+    GNNMP_TOP_NODE_IN, GNNMP_TOP_EDGE_IN, GNNMP_TOP_H0, GNNMP_TOP_H0_BWD, GNNMP_TOP_CONCAT, GNNMP_TOP_SPLIT,
+    GNNMP_TOP_MSG_IN, GNNMP_TOP_MSG_IN_BWD, GNNMP_TOP_POL_IN, GNNMP_TOP_POL_IN_BWD, GNNMP_TOP_SEGMENT_MAX,
+    GNNMP_TOP_SEGMENT_MAX_BWD, GNNMP_TOP_SCORES_OUT, GNNMP_TOP_SCORES_IN, GNNMP_TOP_SM_NODES_IN, GNNMP_TOP_BN_FWD,
+    GNNMP_TOP_BN_BWD, GNNMP_TOP_SM_MSG_IN, GNNMP_TOP_SM_MSG_IN_BWD, GNNMP_TOP_SM_SCATTER_ADD,
+    GNNMP_TOP_SM_SCATTER_ADD_BWD, GNNMP_TOP_ADD_ROWS, GNNMP_TOP_SM_PATH_UPDATE, GNNMP_TOP_SM_PATH_UPDATE_BWD,
+    GNNMP_TOP_SM_COORDS_BWD, GNNMP_TOP_SCALE, GNNMP_TOP_COUNT
+};
+
+/* The padded index space of a batch as the training path sees it (TrainGeom of kernels.hpp): device pointers into the
+ * workspace given to gnnmp_train_geom_build, plus the caller's own v / goal / node_ptr.  csr: e_pad records of four ints
+ * {source, target, caller column, 0} in padded node ids, -1 = pad slot; node n's incoming edges are the slots
+ * [row_beg[n], row_beg[n] + deg[n]); its outgoing edges are the CSR slots out_slot[out_beg[n] .. + out_cnt[n]). */
+typedef struct {
+    int32_t n_graphs, config_size, n_pad, e_pad;
+    const float *v, *goal;
+    const int32_t *node_ptr, *node_ptr_pad, *ntile_graph, *goal_node, *row_beg, *deg;
+    const int32_t* csr;
+    int32_t *out_beg, *out_cnt, *out_cur, *out_slot;
+} gnnmp_train_geom;
+
+/* The prep stage of the forward, the segment sort and the out-list build of the training forward for `batch` (explicit
+ * node_ptr / edge_ptr; obs_ptr may be NULL, obstacles play no part), enqueued on hip_stream; *geom_out is filled on the host at once.  workspace:
+ * 256-byte aligned, >= gnnmp_train_geom_workspace_bytes. */
+int gnnmp_train_geom_workspace_bytes(const gnnmp_batch* shape, int32_t config_size, size_t* bytes);
+int gnnmp_train_geom_build(const gnnmp_batch* batch, int32_t config_size, void* workspace, size_t workspace_bytes,
+                           gnnmp_train_geom* geom_out, void* hip_stream);
+int gnnmp_train_op(int op, const int64_t* dims, int n_dims, void* const* bufs, int n_bufs,
+                   const gnnmp_train_geom* geom_or_null, float scalar, void* hip_stream);
+/* Floats of LINEAR_DW's scratch (negative status on negative sizes). */
+int64_t gnnmp_train_dw_scratch_floats(int64_t R, int64_t K, int64_t O);
+/* Which kernel LINEAR / LINEAR_DX / LINEAR_DW dispatch to at dims [R, K, O, ...]: 1 = fp32 MFMA, 0 = plain; asked of the
+ * launchers' own predicate.  GNNMP_ERR_ARG for another op or bad dims. */
+int gnnmp_train_op_path(int op, const int64_t* dims, int n_dims);
 
 /* ------------------------------------------------------------------------------------------
  * Host-only helpers exported for the CPU test-suite (no device needed)
