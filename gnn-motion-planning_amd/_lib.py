@@ -138,6 +138,10 @@ def lib():
     L.gnnmp_smoother_train_workspace_bytes.argtypes = [vp, ctypes.POINTER(SmoothBatch), ctypes.c_int, ctypes.POINTER(sz)]
     L.gnnmp_smoother_train_forward.argtypes = [vp, ctypes.POINTER(SmoothBatch), ctypes.c_int, vp, vp, vp, sz, vp]
     L.gnnmp_smoother_train_backward.argtypes = [vp, ctypes.POINTER(SmoothBatch), ctypes.c_int, vp, vp, vp, sz, vp]
+    i32p = ctypes.POINTER(ctypes.c_int32)
+    L.gnnmp_smoother_train_batch_workspace_bytes.argtypes = [vp, ctypes.POINTER(SmoothBatch), i32p, ctypes.POINTER(sz)]
+    L.gnnmp_smoother_train_batch_forward.argtypes = [vp, ctypes.POINTER(SmoothBatch), i32p, vp, vp, vp, sz, vp]
+    L.gnnmp_smoother_train_batch_backward.argtypes = [vp, ctypes.POINTER(SmoothBatch), i32p, vp, vp, vp, sz, vp]
     L.gnnmp_explorer_grad_floats.restype = ctypes.c_int64
     L.gnnmp_explorer_grad_floats.argtypes = [vp]
     L.gnnmp_explorer_train_workspace_bytes.argtypes = [vp, ctypes.POINTER(Batch), ctypes.c_int, ctypes.POINTER(sz)]

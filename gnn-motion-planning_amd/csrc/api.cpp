@@ -1937,6 +1937,213 @@ extern "C" int gnnmp_smoother_train_backward(const gnnmp_smoother* h, const gnnm
     return GNNMP_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// the same for B problems per call, each with its own loop count (eight module calls per optimizer step at
+// train_smoother.py:33-61 become one).  Problems come ordered by loop count, longest first: iteration `it` runs the
+// prefix of problems with loops[b] > it, the others keep their state and contribute nothing (SmSeg, train_kernels.hip).
+// ---------------------------------------------------------------------------------------------
+namespace {
+
+struct SmBatchCarve {
+    SmTrainCarve t;
+    size_t bnpart;           // [max_loop][B][2][d] per-problem sums for dgamma / dbeta
+    size_t total_floats;
+};
+
+// per-iteration slots of SmTrainCarve widened for B problems: stats [B][3][d], edge counts [B]
+void sm_batch_carve(const gnnmp_smoother* h, const gnnmp_smooth_batch* b, int max_loop, const SmCarve& c, SmBatchCarve& q) {
+    SmTrainCarve& t = q.t;
+    const size_t d = h->dims.embed_size, C = h->dims.config_size, P = b->total_path, B = b->n_problems;
+    t.Nn = b->total_path + b->total_free + b->total_collided;
+    t.K0 = (int)C + 3;
+    t.ecap = c.ecap;
+    const size_t Nn = t.Nn, Ec = t.ecap, K0 = t.K0;
+    size_t o = 0;
+    auto take = [&](size_t n) { const size_t r = o; o += (n + 63) & ~(size_t)63; return r; };
+    t.inf_bytes = (c.total + 255) & ~(size_t)255;
+    t.states = take((size_t)(max_loop + 1) * P * C);
+    t.it0 = o;
+    t.Xin = take(Nn * K0) - t.it0; t.X0 = take(Nn * d) - t.it0; t.stats = take(B * 3 * d) - t.it0; t.X1 = take(Nn * d) - t.it0;
+    t.X = take(Nn * d) - t.it0; t.esrc = take(Ec) - t.it0; t.edst = take(Ec) - t.it0; t.ne = take(B) - t.it0;
+    t.Zh = take(Ec * d) - t.it0; t.S = take(P * d) - t.it0; t.L1h = take(P * d) - t.it0; t.Hh = take(P * d) - t.it0;
+    t.it_stride = o - t.it0;
+    o = t.it0 + t.it_stride * (size_t)max_loop;
+    t.Zin = take(Ec * 3 * d); t.M = take(Ec * d); t.dZh = take(Ec * d); t.dZin = take(Ec * 3 * d);
+    t.dX = take(Nn * d); t.dX1 = take(Nn * d); t.dX0 = take(Nn * d); t.dXin = take(Nn * K0);
+    t.dS = take(P * d); t.dL1h = take(P * d); t.dHh = take(P * d); t.prop = take(P * C); t.dprop = take(P * C);
+    t.dpa = take(P * C); t.dpb = take(P * C); t.tmpP = take(P * d);
+    {
+        size_t m = t_linear_dw_scratch_floats((int)Ec, (int)(3 * d), (int)d);
+        const size_t n1 = t_linear_dw_scratch_floats((int)Nn, (int)d, (int)d), n0 = t_linear_dw_scratch_floats((int)Nn, (int)K0, (int)d);
+        m = m > n1 ? m : n1;
+        t.dwp = take(m > n0 ? m : n0);
+    }
+    q.bnpart = take((size_t)max_loop * B * 2 * d);
+    t.total_floats = q.total_floats = o;
+}
+
+// GNNMP_OK and the largest loop count, or the error of the argument checks shared by the three entry points
+int sm_batch_args(const gnnmp_smoother* h, const gnnmp_smooth_batch* b, const int32_t* loops, int* max_loop) {
+    if (b->n_problems < 1) return GNNMP_ERR_ARG;
+    for (int i = 0; i < b->n_problems; ++i) {
+        if (loops[i] < 1) return GNNMP_ERR_ARG;
+        if (i > 0 && loops[i] > loops[i - 1]) return GNNMP_ERR_ARG;          // longest first
+    }
+    if (h->dims.mlp_dtype != GNNMP_F32 || b->total_path < 1 || b->max_samples > 2048) return GNNMP_ERR_DIMS;
+    if ((size_t)2 * (size_t)(b->max_edges + kSmK * b->max_path) * sizeof(int) > 60000) return GNNMP_ERR_DIMS;
+    *max_loop = loops[0];
+    return GNNMP_OK;
+}
+
+int sm_active(const gnnmp_smooth_batch* b, const int32_t* loops, int it) {
+    int a = 0;
+    while (a < b->n_problems && loops[a] > it) ++a;
+    return a;
+}
+
+SmSeg sm_seg(const gnnmp_smooth_batch* b, const SmTrainCarve& t) {
+    SmSeg g;
+    g.path_ptr = b->path_ptr; g.free_ptr = b->free_ptr; g.coll_ptr = b->coll_ptr; g.edge_ptr = b->edge_ptr;
+    g.B = b->n_problems; g.A = 0; g.P = b->total_path; g.Nn = t.Nn; g.Ec = t.ecap;
+    return g;
+}
+
+}  // namespace
+
+extern "C" int gnnmp_smoother_train_batch_workspace_bytes(const gnnmp_smoother* h, const gnnmp_smooth_batch* shape, const int32_t* loops_host,
+                                                          size_t* bytes) {
+    if (!h || !shape || !loops_host || !bytes) return GNNMP_ERR_NULL;
+    int L = 0;
+    const int rc = sm_batch_args(h, shape, loops_host, &L);
+    if (rc != GNNMP_OK) return rc;
+    SmCarve c;
+    if (!sm_carve(h, shape, c)) return GNNMP_ERR_ARG;
+    SmBatchCarve q;
+    sm_batch_carve(h, shape, L, c, q);
+    *bytes = q.t.inf_bytes + q.total_floats * sizeof(float);
+    return GNNMP_OK;
+}
+
+extern "C" int gnnmp_smoother_train_batch_forward(const gnnmp_smoother* h, const gnnmp_smooth_batch* b, const int32_t* loops_host,
+                                                  float* out_path, float* bn_stats, void* ws, size_t ws_bytes, void* hip_stream) {
+    if (!h || !b || !loops_host || !ws || !out_path) return GNNMP_ERR_NULL;
+    if (!b->path_ptr || !b->free_ptr || !b->coll_ptr || !b->edge_ptr) return GNNMP_ERR_NULL;
+    int L = 0;
+    const int rc = sm_batch_args(h, b, loops_host, &L);
+    if (rc != GNNMP_OK) return rc;
+    SmCarve c;
+    if (!sm_carve(h, b, c)) return GNNMP_ERR_ARG;
+    SmBatchCarve q;
+    sm_batch_carve(h, b, L, c, q);
+    const SmTrainCarve& t = q.t;
+    if (ws_bytes < t.inf_bytes + q.total_floats * sizeof(float) || (reinterpret_cast<uintptr_t>(ws) & 255)) return GNNMP_ERR_WORKSPACE;
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    float* T = reinterpret_cast<float*>(static_cast<char*>(ws) + t.inf_bytes);
+    const int d = h->dims.embed_size, C = h->dims.config_size, P = b->total_path, B = b->n_problems;
+    const int Nn = t.Nn, K0 = t.K0, Ec = t.ecap;
+    SmParams p;
+    sm_fill_params(h, b, c, ws, p);
+    SmSeg g = sm_seg(b, t);
+    const SmW nc0 = sm_wref(h, nullptr, "node_code.0"), bn = sm_wref(h, nullptr, "node_code.1"), nc3 = sm_wref(h, nullptr, "node_code.3"),
+              l00 = sm_wref(h, nullptr, "process.lin_0.0"), l02 = sm_wref(h, nullptr, "process.lin_0.2"),
+              l10 = sm_wref(h, nullptr, "process.lin_1.0"), l12 = sm_wref(h, nullptr, "process.lin_1.2"), sn = sm_wref(h, nullptr, "smooth_node");
+    float* states = T + t.states;
+    // rows no kernel writes (problems past their loop count, padding slots of the edge space) must hold finite numbers:
+    // the weight gradients sum 0 * activation over them
+    HIP_TRY(hipMemsetAsync(T, 0, q.total_floats * sizeof(float), st));
+    if (bn_stats) HIP_TRY(hipMemsetAsync(bn_stats, 0, (size_t)B * L * 2 * d * sizeof(float), st));
+    HIP_TRY(launch_sm_init(P * C, p.scale, b->path, states, st));                              // model_smoother.py:118
+    for (int it = 0; it < L; ++it) {
+        float* I = T + t.it0 + t.it_stride * (size_t)it;
+        float* cur = states + (size_t)it * P * C;
+        g.A = sm_active(b, loops_host, it);
+        // the graph stage of the active prefix writes this iteration's edge list straight into its kept slots
+        p.B = g.A; p.cur = cur; p.cur_next = cur;
+        p.e_src = reinterpret_cast<int*>(I + t.esrc); p.e_dst = reinterpret_cast<int*>(I + t.edst); p.e_count = reinterpret_cast<int*>(I + t.ne);
+        HIP_TRY(hipMemsetAsync(at<char>(ws, c.ff_beg), 0xFF, c.ff_end - c.ff_beg, st));
+        HIP_TRY(launch_sm_knn_edges(p, st));                                                    // :125-128
+        const int *ne = p.e_count, *es = p.e_src, *ed = p.e_dst;
+        HIP_TRY(t_sm_nodes_in_seg(g, C, p.scale, cur, b->free_pts, b->collided, I + t.Xin, st));   // :130-135
+        HIP_TRY(t_linear(Nn, K0, d, I + t.Xin, nc0.w, nc0.b, I + t.X0, false, st));
+        HIP_TRY(t_bn_seg_fwd(g, d, I + t.X0, bn.w, bn.b, I + t.X1, I + t.stats, bn_stats ? bn_stats + (size_t)it * 2 * d : nullptr,
+                             (size_t)L * 2 * d, true, st));                                    // BatchNorm per problem + ReLU
+        HIP_TRY(t_linear(Nn, d, d, I + t.X1, nc3.w, nc3.b, I + t.X, false, st));
+        HIP_TRY(t_sm_msg_in_seg(g, ne, d, es, ed, I + t.X, T + t.Zin, st));                    // :36-37
+        HIP_TRY(t_linear(Ec, 3 * d, d, T + t.Zin, l00.w, l00.b, I + t.Zh, true, st));
+        HIP_TRY(t_linear(Ec, d, d, I + t.Zh, l02.w, l02.b, T + t.M, false, st));
+        HIP_TRY(t_sm_scatter_add_seg(g, ne, d, ed, T + t.M, I + t.S, st));                     // aggr = 'add' (:32)
+        HIP_TRY(t_linear(P, d, d, I + t.S, l10.w, l10.b, I + t.L1h, true, st));
+        HIP_TRY(t_linear(P, d, d, I + t.L1h, l12.w, l12.b, T + t.tmpP, false, st));
+        HIP_TRY(t_sm_add_path_seg(g, d, I + t.X, T + t.tmpP, I + t.Hh, st));                   // x + lin_1(out) (:34), path rows
+        HIP_TRY(t_linear(P, d, C, I + t.Hh, sn.w, sn.b, T + t.prop, false, st));
+        HIP_TRY(t_sm_path_update_seg(g, C, cur, T + t.prop, cur + (size_t)P * C, st));         // :139
+    }
+    HIP_TRY(t_scale(P * C, p.scale, states + (size_t)L * P * C, out_path, st));                // :142
+    return GNNMP_OK;
+}
+
+extern "C" int gnnmp_smoother_train_batch_backward(const gnnmp_smoother* h, const gnnmp_smooth_batch* b, const int32_t* loops_host,
+                                                   const float* d_out_path, float* grad, void* ws, size_t ws_bytes, void* hip_stream) {
+    if (!h || !b || !loops_host || !ws || !grad || !d_out_path) return GNNMP_ERR_NULL;
+    if (!b->path_ptr || !b->free_ptr || !b->coll_ptr || !b->edge_ptr) return GNNMP_ERR_NULL;
+    int L = 0;
+    const int rc = sm_batch_args(h, b, loops_host, &L);
+    if (rc != GNNMP_OK) return rc;
+    SmCarve c;
+    if (!sm_carve(h, b, c)) return GNNMP_ERR_ARG;
+    SmBatchCarve q;
+    sm_batch_carve(h, b, L, c, q);
+    const SmTrainCarve& t = q.t;
+    if (ws_bytes < t.inf_bytes + q.total_floats * sizeof(float) || (reinterpret_cast<uintptr_t>(ws) & 255)) return GNNMP_ERR_WORKSPACE;
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    float* T = reinterpret_cast<float*>(static_cast<char*>(ws) + t.inf_bytes);
+    const int d = h->dims.embed_size, C = h->dims.config_size, P = b->total_path, B = b->n_problems;
+    const int Nn = t.Nn, K0 = t.K0, Ec = t.ecap;
+    SmSeg g = sm_seg(b, t);
+    HIP_TRY(hipMemsetAsync(grad, 0, (size_t)h->n_raw * sizeof(float), st));
+    const SmW nc0 = sm_wref(h, grad, "node_code.0"), bn = sm_wref(h, grad, "node_code.1"), nc3 = sm_wref(h, grad, "node_code.3"),
+              l00 = sm_wref(h, grad, "process.lin_0.0"), l02 = sm_wref(h, grad, "process.lin_0.2"),
+              l10 = sm_wref(h, grad, "process.lin_1.0"), l12 = sm_wref(h, grad, "process.lin_1.2"), sn = sm_wref(h, grad, "smooth_node");
+    float* dcur = T + t.dpa;
+    float* dprev = T + t.dpb;
+    HIP_TRY(t_scale(P * C, h->dims.scale, d_out_path, dcur, st));
+    for (int it = L - 1; it >= 0; --it) {
+        float* I = T + t.it0 + t.it_stride * (size_t)it;
+        const int* ne = reinterpret_cast<const int*>(I + t.ne);
+        const int* es = reinterpret_cast<const int*>(I + t.esrc);
+        const int* ed = reinterpret_cast<const int*>(I + t.edst);
+        g.A = sm_active(b, loops_host, it);
+        // every adjoint below is zero on the rows of problems that did not run this iteration: their d_out passes through
+        HIP_TRY(t_sm_path_update_bwd_seg(g, C, dcur, T + t.dprop, dprev, st));
+        HIP_TRY(t_linear_dw(P, d, C, T + t.dprop, I + t.Hh, sn.gw, sn.gb, T + t.dwp, st));
+        HIP_TRY(t_linear_dx(P, d, C, T + t.dprop, sn.w, T + t.dHh, false, st));
+        HIP_TRY(t_sm_add_path_bwd_seg(g, d, T + t.dHh, T + t.dX, st));                          // x + ...: identity branch
+        HIP_TRY(t_linear_dw(P, d, d, T + t.dHh, I + t.L1h, l12.gw, l12.gb, T + t.dwp, st));
+        HIP_TRY(t_linear_dx(P, d, d, T + t.dHh, l12.w, T + t.dL1h, false, st));
+        HIP_TRY(t_relu_bwd((size_t)P * d, I + t.L1h, T + t.dL1h, st));
+        HIP_TRY(t_linear_dw(P, d, d, T + t.dL1h, I + t.S, l10.gw, l10.gb, T + t.dwp, st));
+        HIP_TRY(t_linear_dx(P, d, d, T + t.dL1h, l10.w, T + t.dS, false, st));
+        HIP_TRY(t_sm_scatter_add_bwd_seg(g, ne, d, ed, T + t.dS, T + t.M, st));                 // dM
+        HIP_TRY(t_linear_dw(Ec, d, d, T + t.M, I + t.Zh, l02.gw, l02.gb, T + t.dwp, st));
+        HIP_TRY(t_linear_dx(Ec, d, d, T + t.M, l02.w, T + t.dZh, false, st));
+        HIP_TRY(t_relu_bwd((size_t)Ec * d, I + t.Zh, T + t.dZh, st));
+        HIP_TRY(t_sm_msg_in_seg(g, ne, d, es, ed, I + t.X, T + t.Zin, st));                     // Zin recomputed
+        HIP_TRY(t_linear_dw(Ec, 3 * d, d, T + t.dZh, T + t.Zin, l00.gw, l00.gb, T + t.dwp, st));
+        HIP_TRY(t_linear_dx(Ec, 3 * d, d, T + t.dZh, l00.w, T + t.dZin, false, st));
+        HIP_TRY(t_sm_msg_in_bwd_seg(g, ne, d, es, ed, T + t.dZin, T + t.dX, st));
+        HIP_TRY(t_linear_dw(Nn, d, d, T + t.dX, I + t.X1, nc3.gw, nc3.gb, T + t.dwp, st));
+        HIP_TRY(t_linear_dx(Nn, d, d, T + t.dX, nc3.w, T + t.dX1, false, st));
+        HIP_TRY(t_relu_bwd((size_t)Nn * d, I + t.X1, T + t.dX1, st));
+        HIP_TRY(t_bn_seg_bwd(g, d, I + t.X0, T + t.dX1, bn.w, I + t.stats, T + t.dX0, T + q.bnpart + (size_t)it * B * 2 * d, st));
+        HIP_TRY(t_linear_dw(Nn, K0, d, T + t.dX0, I + t.Xin, nc0.gw, nc0.gb, T + t.dwp, st));
+        HIP_TRY(t_linear_dx(Nn, K0, d, T + t.dX0, nc0.w, T + t.dXin, false, st));
+        HIP_TRY(t_sm_coords_bwd_seg(g, C, T + t.dXin, dprev, st));                              // nodes[:P] = path (:140)
+        float* sw = dcur; dcur = dprev; dprev = sw;
+    }
+    HIP_TRY(t_bn_seg_dgb(L, B, d, T + q.bnpart, bn.gw, bn.gb, st));
+    return GNNMP_OK;
+}
+
 // =============================================================================================
 // supervision of the explorer's training step (train_explorer.py:124-176, train_episode_kernels.hip)
 // =============================================================================================

@@ -318,6 +318,31 @@ hipError_t t_sm_coords_bwd(int P, int C, const float* dXin, float* d_prev, hipSt
 hipError_t t_scale(int n, float s, const float* x, float* y, hipStream_t st);
 hipError_t launch_sm_knn_edges(const SmParams& p, hipStream_t st);      // kNN + coalesced edge list only (training path)
 
+// the batched training path of the smoother: the batch's prefix arrays (device) and, per iteration, how many problems still run
+struct SmSeg {
+    const int *path_ptr, *free_ptr, *coll_ptr, *edge_ptr;   // [B + 1] each
+    int B, A;                                                // problems; [0, A) are active in this iteration (loop counts descend)
+    int P, Nn, Ec;                                           // total path rows, node rows (path + free + collided), padded edge slots
+};
+hipError_t t_sm_nodes_in_seg(const SmSeg& g, int C, float scale, const float* cur, const float* free_pts, const float* coll, float* out,
+                             hipStream_t st);
+hipError_t t_bn_seg_fwd(const SmSeg& g, int D, const float* x, const float* gamma, const float* beta, float* y, float* stats,
+                        float* out_stats, size_t out_stride, bool relu, hipStream_t st);
+hipError_t t_bn_seg_bwd(const SmSeg& g, int D, const float* x, const float* dy, const float* gamma, const float* stats, float* dx,
+                        float* part, hipStream_t st);
+hipError_t t_bn_seg_dgb(int L, int B, int D, const float* part, float* dgamma, float* dbeta, hipStream_t st);
+hipError_t t_sm_msg_in_seg(const SmSeg& g, const int* n_edges, int D, const int* e_src, const int* e_dst, const float* X, float* out,
+                           hipStream_t st);
+hipError_t t_sm_msg_in_bwd_seg(const SmSeg& g, const int* n_edges, int D, const int* e_src, const int* e_dst, const float* dZ, float* dX,
+                               hipStream_t st);
+hipError_t t_sm_scatter_add_seg(const SmSeg& g, const int* n_edges, int D, const int* e_dst, const float* M, float* S, hipStream_t st);
+hipError_t t_sm_scatter_add_bwd_seg(const SmSeg& g, const int* n_edges, int D, const int* e_dst, const float* dS, float* dM, hipStream_t st);
+hipError_t t_sm_add_path_seg(const SmSeg& g, int D, const float* X, const float* Y, float* out, hipStream_t st);
+hipError_t t_sm_add_path_bwd_seg(const SmSeg& g, int D, const float* dH, float* dX, hipStream_t st);
+hipError_t t_sm_path_update_seg(const SmSeg& g, int C, const float* prev, const float* proposal, float* next, hipStream_t st);
+hipError_t t_sm_path_update_bwd_seg(const SmSeg& g, int C, const float* d_next, float* d_proposal, float* d_prev, hipStream_t st);
+hipError_t t_sm_coords_bwd_seg(const SmSeg& g, int C, const float* dXin, float* d_prev, hipStream_t st);
+
 int prep_parts(int G, int E);
 hipError_t launch_prep(const PrepParams& q, int Npad, int Epad, int* hist, hipStream_t st);
 hipError_t launch_obs(int D, int P, const ObsParams& p, const NodeF64Params& q, int G, hipStream_t st);

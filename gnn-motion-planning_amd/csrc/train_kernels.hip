@@ -883,3 +883,290 @@ hipError_t t_scale(int n, float s, const float* x, float* y, hipStream_t st) {
 }
 
 }  // namespace gnnmp
+
+// =====================================================================================================================
+// smoother training path, B problems per call (gnnmp_smoother_train_batch_*).  Node rows are stacked problem by problem,
+// [path_b; free_b; collided_b] from row path_ptr[b] + free_ptr[b] + coll_ptr[b]; path rows and edge slots use the
+// batch's own spaces (path_ptr; the padded edge space of the kNN stage, smoother_kernels.hip sm_eoff).  The caller orders
+// the problems by loop count, longest first, so the problems still running in an iteration are the prefix [0, A): every
+// kernel here treats problem b >= A as absent -- no statistics, no edges, zero adjoints -- and a thread looks only at its
+// own problem's rows and edge segment.  Summation orders inside a problem are those of the one-problem kernels above.
+// =====================================================================================================================
+namespace gnnmp {
+
+__device__ __forceinline__ int seg_n0(const SmSeg& g, int b) { return g.path_ptr[b] + g.free_ptr[b] + g.coll_ptr[b]; }
+__device__ __forceinline__ int seg_e0(const SmSeg& g, int b) { return ((g.edge_ptr[b] + kSmK * g.path_ptr[b] + 31) & ~31) + 32 * b; }
+// problem of a path row / node row / edge slot: the last b whose range starts at or before it
+__device__ __forceinline__ int seg_of_path(const SmSeg& g, int r) {
+    int lo = 0, hi = g.B;
+    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (g.path_ptr[mid] <= r) lo = mid; else hi = mid; }
+    return lo;
+}
+__device__ __forceinline__ int seg_of_node(const SmSeg& g, int r) {
+    int lo = 0, hi = g.B;
+    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (seg_n0(g, mid) <= r) lo = mid; else hi = mid; }
+    return lo;
+}
+__device__ __forceinline__ int seg_of_edge(const SmSeg& g, int e) {
+    int lo = 0, hi = g.B;
+    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (seg_e0(g, mid) <= e) lo = mid; else hi = mid; }
+    return lo;
+}
+
+// Xin rows of the active problems (sm_nodes_in_kernel per problem); rows of the others are left as they are (zero)
+__global__ void sm_nodes_in_seg_kernel(SmSeg g, int C, float scale, const float* __restrict__ cur, const float* __restrict__ free_pts,
+                                       const float* __restrict__ coll, float* __restrict__ out) {
+    const int K = C + 3;
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)g.Nn * K) return;
+    const int r = (int)(i / K), k = (int)(i % K);
+    const int b = seg_of_node(g, r);
+    if (b >= g.A) return;
+    const int p0 = g.path_ptr[b], f0 = g.free_ptr[b], c0 = g.coll_ptr[b];
+    const int P = g.path_ptr[b + 1] - p0, F = g.free_ptr[b + 1] - f0;
+    const int n = r - (p0 + f0 + c0);
+    const int kind = n < P ? 0 : (n < P + F ? 1 : 2);
+    float val;
+    if (k < C) val = kind == 0 ? cur[(size_t)(p0 + n) * C + k]
+                               : (kind == 1 ? free_pts[(size_t)(f0 + n - P) * C + k] / scale : coll[(size_t)(c0 + n - P - F) * C + k] / scale);
+    else val = (k - C == kind) ? 1.f : 0.f;
+    out[i] = val;
+}
+
+// bn_train_fwd_kernel per problem: block (feature f, problem b < A) over the problem's own node rows.  stats [B][3][D] as there;
+// out_stats (may be null) + b * out_stride receives [mean; unbiased variance] of this iteration.
+__global__ __launch_bounds__(256) void bn_seg_fwd_kernel(SmSeg g, int D, const float* __restrict__ x, const float* __restrict__ gamma,
+                                                         const float* __restrict__ beta, float eps, float* __restrict__ y,
+                                                         float* __restrict__ stats, float* __restrict__ out_stats, size_t out_stride, int relu) {
+    __shared__ double red[256];
+    const int f = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+    const int r0 = seg_n0(g, b), N = seg_n0(g, b + 1) - r0;
+    if (N <= 0) return;
+    x += (size_t)r0 * D; y += (size_t)r0 * D; stats += (size_t)b * 3 * D;
+    double s = 0.0;
+    for (int n = tid; n < N; n += 256) s += (double)x[(size_t)n * D + f];
+    const double mean = bn_block_sum(red, s) / N;
+    double q = 0.0;
+    for (int n = tid; n < N; n += 256) { const double dlt = (double)x[(size_t)n * D + f] - mean; q = fma(dlt, dlt, q); }
+    const double ss = bn_block_sum(red, q);
+    const double var = ss / N;
+    const double invstd = 1.0 / sqrt(var + (double)eps);
+    if (tid == 0) {
+        const float unb = (float)(N > 1 ? ss / (N - 1) : var);
+        stats[f] = (float)mean; stats[D + f] = (float)invstd; stats[2 * D + f] = unb;
+        if (out_stats) { float* o = out_stats + (size_t)b * out_stride; o[f] = (float)mean; o[D + f] = unb; }
+    }
+    const double ga = gamma[f], be = beta[f];
+    for (int n = tid; n < N; n += 256) {
+        const float val = (float)(((double)x[(size_t)n * D + f] - mean) * invstd * ga + be);
+        y[(size_t)n * D + f] = (relu && val < 0.f) ? 0.f : val;
+    }
+}
+// bn_train_bwd_kernel per problem: block (f, b) over all B problems.  Active: dx of its rows, and its sums for dgamma / dbeta go to
+// part[b][2][D] (added up in a fixed order by bn_seg_dgb_kernel, no float atomics).  Not active: dx rows and the sums are zero.
+__global__ __launch_bounds__(256) void bn_seg_bwd_kernel(SmSeg g, int D, const float* __restrict__ x, const float* __restrict__ dy,
+                                                         const float* __restrict__ gamma, const float* __restrict__ stats,
+                                                         float* __restrict__ dx, float* __restrict__ part) {
+    __shared__ double red[256];
+    const int f = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+    const int r0 = seg_n0(g, b), N = seg_n0(g, b + 1) - r0;
+    part += (size_t)b * 2 * D;
+    if (b >= g.A || N <= 0) {
+        for (int n = tid; n < N; n += 256) dx[(size_t)(r0 + n) * D + f] = 0.f;
+        if (tid == 0) { part[f] = 0.f; part[D + f] = 0.f; }
+        return;
+    }
+    x += (size_t)r0 * D; dy += (size_t)r0 * D; dx += (size_t)r0 * D; stats += (size_t)b * 3 * D;
+    double s = 0.0;
+    for (int n = tid; n < N; n += 256) s += (double)x[(size_t)n * D + f];
+    const double mean = bn_block_sum(red, s) / N;
+    const double invstd = stats[D + f];
+    double s0 = 0.0, s1 = 0.0;
+    for (int n = tid; n < N; n += 256) {
+        const double gr = dy[(size_t)n * D + f];
+        s0 += gr;
+        s1 = fma(gr, ((double)x[(size_t)n * D + f] - mean) * invstd, s1);
+    }
+    const double sum_dy = bn_block_sum(red, s0), sum_dyx = bn_block_sum(red, s1);
+    if (tid == 0) { part[f] = (float)sum_dyx; part[D + f] = (float)sum_dy; }
+    const double k = (double)gamma[f] * invstd / N;
+    for (int n = tid; n < N; n += 256) {
+        const double xhat = ((double)x[(size_t)n * D + f] - mean) * invstd;
+        dx[(size_t)n * D + f] = (float)(k * (N * (double)dy[(size_t)n * D + f] - sum_dy - xhat * sum_dyx));
+    }
+}
+// dgamma[f] += sum of part[it][b][0][f], dbeta[f] += ... [1][f]: iterations last to first (the order the backward visits them),
+// problems ascending inside an iteration
+__global__ void bn_seg_dgb_kernel(int L, int B, int D, const float* __restrict__ part, float* __restrict__ dgamma, float* __restrict__ dbeta) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= 2 * D) return;
+    float acc = i < D ? dgamma[i] : dbeta[i - D];
+    for (int it = L - 1; it >= 0; --it)
+        for (int b = 0; b < B; ++b) acc += part[((size_t)it * B + b) * 2 * D + i];
+    if (i < D) dgamma[i] = acc; else dbeta[i - D] = acc;
+}
+
+// Zin over the whole padded edge space: [X_s - X_t, X_s, X_t] for the slots in use of active problems, 0 elsewhere
+__global__ void sm_msg_in_seg_kernel(SmSeg g, const int* __restrict__ n_edges, int D, const int* __restrict__ e_src, const int* __restrict__ e_dst,
+                                     const float* __restrict__ X, float* __restrict__ out) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)g.Ec * 3 * D) return;
+    const int e = (int)(i / (3 * D)), k = (int)(i % (3 * D));
+    const int b = seg_of_edge(g, e);
+    float val = 0.f;
+    if (b < g.A && e - seg_e0(g, b) < n_edges[b]) {
+        const int part = k / D, f = k % D, n0 = seg_n0(g, b);
+        const float xs = X[(size_t)(n0 + e_src[e]) * D + f], xt = X[(size_t)(n0 + e_dst[e]) * D + f];
+        val = part == 0 ? xs - xt : (part == 1 ? xs : xt);
+    }
+    out[i] = val;
+}
+// node-centric adjoint: a (node row, feature) thread walks its own problem's edge segment in order
+__global__ void sm_msg_in_bwd_seg_kernel(SmSeg g, const int* __restrict__ n_edges, int D, const int* __restrict__ e_src,
+                                         const int* __restrict__ e_dst, const float* __restrict__ dZ, float* __restrict__ dX) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)g.Nn * D) return;
+    const int r = (int)(i / D), f = (int)(i % D);
+    const int b = seg_of_node(g, r);
+    if (b >= g.A) return;
+    const int n = r - seg_n0(g, b), e0 = seg_e0(g, b), e1 = e0 + n_edges[b];
+    float acc = 0.f;
+    for (int e = e0; e < e1; ++e) {
+        const float* z = dZ + (size_t)e * 3 * D;
+        if (e_src[e] == n) acc += z[f] + z[D + f];
+        if (e_dst[e] == n) acc += z[2 * D + f] - z[f];
+    }
+    dX[i] += acc;
+}
+// S[path row] = ordered sum of the messages into it (0 for problems that are not active)
+__global__ void sm_scatter_add_seg_kernel(SmSeg g, const int* __restrict__ n_edges, int D, const int* __restrict__ e_dst,
+                                          const float* __restrict__ M, float* __restrict__ S) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)g.P * D) return;
+    const int r = (int)(i / D), f = (int)(i % D);
+    const int b = seg_of_path(g, r);
+    float acc = 0.f;
+    if (b < g.A) {
+        const int n = r - g.path_ptr[b], e0 = seg_e0(g, b), e1 = e0 + n_edges[b];
+        for (int e = e0; e < e1; ++e)
+            if (e_dst[e] == n) acc += M[(size_t)e * D + f];
+    }
+    S[i] = acc;
+}
+__global__ void sm_scatter_add_bwd_seg_kernel(SmSeg g, const int* __restrict__ n_edges, int D, const int* __restrict__ e_dst,
+                                              const float* __restrict__ dS, float* __restrict__ dM) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)g.Ec * D) return;
+    const int e = (int)(i / D);
+    const int b = seg_of_edge(g, e);
+    const bool valid = b < g.A && e - seg_e0(g, b) < n_edges[b];
+    dM[i] = valid ? dS[(size_t)(g.path_ptr[b] + e_dst[e]) * D + i % D] : 0.f;
+}
+// Hh[path row] = X[its node row] + Y[path row]  (x + lin_1(out), model_smoother.py:34, rows < P of each active problem)
+__global__ void sm_add_path_seg_kernel(SmSeg g, int D, const float* __restrict__ X, const float* __restrict__ Y, float* __restrict__ out) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)g.P * D) return;
+    const int r = (int)(i / D);
+    const int b = seg_of_path(g, r);
+    if (b >= g.A) return;
+    out[i] = X[(size_t)(r + g.free_ptr[b] + g.coll_ptr[b]) * D + i % D] + Y[i];
+}
+// its adjoint on the identity branch: dX[node row] = dHh[path row] for path rows of active problems, 0 for every other node row
+__global__ void sm_add_path_bwd_seg_kernel(SmSeg g, int D, const float* __restrict__ dH, float* __restrict__ dX) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)g.Nn * D) return;
+    const int r = (int)(i / D);
+    const int b = seg_of_node(g, r);
+    const int n = r - seg_n0(g, b);
+    const bool on = b < g.A && n < g.path_ptr[b + 1] - g.path_ptr[b];
+    dX[i] = on ? dH[(size_t)(g.path_ptr[b] + n) * D + i % D] : 0.f;
+}
+// interior rows of active problems take the proposal; end rows and problems past their loop count keep their state
+__global__ void sm_path_update_seg_kernel(SmSeg g, int C, const float* __restrict__ prev, const float* __restrict__ proposal, float* __restrict__ next) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)g.P * C) return;
+    const int r = (int)(i / C);
+    const int b = seg_of_path(g, r);
+    const int n = r - g.path_ptr[b], P = g.path_ptr[b + 1] - g.path_ptr[b];
+    next[i] = (b < g.A && n >= 1 && n <= P - 2) ? proposal[i] : prev[i];
+}
+__global__ void sm_path_update_bwd_seg_kernel(SmSeg g, int C, const float* __restrict__ d_next, float* __restrict__ d_proposal, float* __restrict__ d_prev) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)g.P * C) return;
+    const int r = (int)(i / C);
+    const int b = seg_of_path(g, r);
+    const int n = r - g.path_ptr[b], P = g.path_ptr[b + 1] - g.path_ptr[b];
+    const bool inner = b < g.A && n >= 1 && n <= P - 2;
+    d_proposal[i] = inner ? d_next[i] : 0.f;
+    d_prev[i] = inner ? 0.f : d_next[i];
+}
+__global__ void sm_coords_bwd_seg_kernel(SmSeg g, int C, const float* __restrict__ dXin, float* __restrict__ d_prev) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)g.P * C) return;
+    const int r = (int)(i / C);
+    const int b = seg_of_path(g, r);
+    if (b >= g.A) return;
+    d_prev[i] += dXin[(size_t)(r + g.free_ptr[b] + g.coll_ptr[b]) * (C + 3) + i % C];
+}
+
+#define SEG_LAUNCH(kernel, n, ...)                                                              \
+    do {                                                                                        \
+        if ((n) > 0) {                                                                          \
+            hipLaunchKernelGGL(kernel, dim3(blocks((size_t)(n))), dim3(256), 0, st, __VA_ARGS__); \
+            TRAIN_LAUNCH_CHECK();                                                               \
+        }                                                                                       \
+        return hipSuccess;                                                                      \
+    } while (0)
+
+hipError_t t_sm_nodes_in_seg(const SmSeg& g, int C, float scale, const float* cur, const float* free_pts, const float* coll, float* out,
+                             hipStream_t st) {
+    SEG_LAUNCH(sm_nodes_in_seg_kernel, (size_t)g.Nn * (C + 3), g, C, scale, cur, free_pts, coll, out);
+}
+hipError_t t_bn_seg_fwd(const SmSeg& g, int D, const float* x, const float* gamma, const float* beta, float* y, float* stats,
+                        float* out_stats, size_t out_stride, bool relu, hipStream_t st) {
+    if (g.A <= 0) return hipSuccess;
+    hipLaunchKernelGGL(bn_seg_fwd_kernel, dim3(D, g.A), dim3(256), 0, st, g, D, x, gamma, beta, 1e-5f, y, stats, out_stats, out_stride, relu ? 1 : 0);
+    TRAIN_LAUNCH_CHECK();
+    return hipSuccess;
+}
+hipError_t t_bn_seg_bwd(const SmSeg& g, int D, const float* x, const float* dy, const float* gamma, const float* stats, float* dx,
+                        float* part, hipStream_t st) {
+    hipLaunchKernelGGL(bn_seg_bwd_kernel, dim3(D, g.B), dim3(256), 0, st, g, D, x, dy, gamma, stats, dx, part);
+    TRAIN_LAUNCH_CHECK();
+    return hipSuccess;
+}
+hipError_t t_bn_seg_dgb(int L, int B, int D, const float* part, float* dgamma, float* dbeta, hipStream_t st) {
+    SEG_LAUNCH(bn_seg_dgb_kernel, (size_t)2 * D, L, B, D, part, dgamma, dbeta);
+}
+hipError_t t_sm_msg_in_seg(const SmSeg& g, const int* n_edges, int D, const int* e_src, const int* e_dst, const float* X, float* out,
+                           hipStream_t st) {
+    SEG_LAUNCH(sm_msg_in_seg_kernel, (size_t)g.Ec * 3 * D, g, n_edges, D, e_src, e_dst, X, out);
+}
+hipError_t t_sm_msg_in_bwd_seg(const SmSeg& g, const int* n_edges, int D, const int* e_src, const int* e_dst, const float* dZ, float* dX,
+                               hipStream_t st) {
+    SEG_LAUNCH(sm_msg_in_bwd_seg_kernel, (size_t)g.Nn * D, g, n_edges, D, e_src, e_dst, dZ, dX);
+}
+hipError_t t_sm_scatter_add_seg(const SmSeg& g, const int* n_edges, int D, const int* e_dst, const float* M, float* S, hipStream_t st) {
+    SEG_LAUNCH(sm_scatter_add_seg_kernel, (size_t)g.P * D, g, n_edges, D, e_dst, M, S);
+}
+hipError_t t_sm_scatter_add_bwd_seg(const SmSeg& g, const int* n_edges, int D, const int* e_dst, const float* dS, float* dM, hipStream_t st) {
+    SEG_LAUNCH(sm_scatter_add_bwd_seg_kernel, (size_t)g.Ec * D, g, n_edges, D, e_dst, dS, dM);
+}
+hipError_t t_sm_add_path_seg(const SmSeg& g, int D, const float* X, const float* Y, float* out, hipStream_t st) {
+    SEG_LAUNCH(sm_add_path_seg_kernel, (size_t)g.P * D, g, D, X, Y, out);
+}
+hipError_t t_sm_add_path_bwd_seg(const SmSeg& g, int D, const float* dH, float* dX, hipStream_t st) {
+    SEG_LAUNCH(sm_add_path_bwd_seg_kernel, (size_t)g.Nn * D, g, D, dH, dX);
+}
+hipError_t t_sm_path_update_seg(const SmSeg& g, int C, const float* prev, const float* proposal, float* next, hipStream_t st) {
+    SEG_LAUNCH(sm_path_update_seg_kernel, (size_t)g.P * C, g, C, prev, proposal, next);
+}
+hipError_t t_sm_path_update_bwd_seg(const SmSeg& g, int C, const float* d_next, float* d_proposal, float* d_prev, hipStream_t st) {
+    SEG_LAUNCH(sm_path_update_bwd_seg_kernel, (size_t)g.P * C, g, C, d_next, d_proposal, d_prev);
+}
+hipError_t t_sm_coords_bwd_seg(const SmSeg& g, int C, const float* dXin, float* d_prev, hipStream_t st) {
+    SEG_LAUNCH(sm_coords_bwd_seg_kernel, (size_t)g.P * C, g, C, dXin, d_prev);
+}
+#undef SEG_LAUNCH
+
+}  // namespace gnnmp

@@ -57,6 +57,8 @@ class SmoothBatch:
         self.max_samples = max(f.shape[0] + c.shape[0] for f, c in zip(frees, collideds))
         self.max_edges = max(e.shape[1] for e in edge_indexes)
         self.path_counts = [t.shape[0] for t in paths]
+        self.free_counts, self.coll_counts = [t.shape[0] for t in frees], [t.shape[0] for t in collideds]
+        self.edge_counts = [e.shape[1] for e in edge_indexes]
         self.caps_from_host = True        # max_* computed from the same host-side counts as the prefix arrays: cannot be exceeded
 
     @classmethod
@@ -79,6 +81,7 @@ class SmoothBatch:
         sb.max_samples = max(f + c for f, c in zip(free_counts, coll_counts))
         sb.max_edges = max(edge_counts)
         sb.path_counts = list(path_counts)
+        sb.free_counts, sb.coll_counts, sb.edge_counts = list(free_counts), list(coll_counts), list(edge_counts)
         sb.caps_from_host = True
         return sb
 
@@ -156,6 +159,70 @@ class _TrainSmooth(torch.autograd.Function):
             _lib.check(_lib.lib().gnnmp_smoother_train_backward(ctx.handle, ctypes.byref(cb), ctx.loop, d_out.data_ptr(),
                                                                 grad.data_ptr(), ctx.ws.data_ptr(), ctx.ws.numel(), st),
                        'gnnmp_smoother_train_backward')
+        sd = model.state_dict(keep_vars=True)
+        out, off = [], 0
+        for name, numel in model._manifest:
+            t = sd[name]
+            out.append(grad[off:off + numel].view_as(t).to(t.device) if name in SMOOTHER_TRAINABLE else None)
+            off += numel
+        return (None, None, None) + tuple(out)
+
+
+def _reordered(sb, order):
+    """``sb`` with its problems in ``order`` (device-side gathers of the concatenated tensors; host-side counts)."""
+    dev = sb.path.device
+    pick = lambda counts: [counts[b] for b in order]  # noqa: E731
+
+    def rows(counts):
+        starts = [0]
+        for c in counts:
+            starts.append(starts[-1] + c)
+        idx = [torch.arange(starts[b], starts[b + 1]) for b in order]
+        return torch.cat(idx).to(dev) if idx else torch.zeros(0, dtype=torch.int64, device=dev)
+    return SmoothBatch.from_device(sb.path.index_select(0, rows(sb.path_counts)), sb.free.index_select(0, rows(sb.free_counts)),
+                                   sb.collided.index_select(0, rows(sb.coll_counts)),
+                                   sb.edge_index.index_select(1, rows(sb.edge_counts)), pick(sb.path_counts),
+                                   pick(sb.free_counts), pick(sb.coll_counts), pick(sb.edge_counts))
+
+
+class _TrainSmoothBatch(torch.autograd.Function):
+    """New waypoints [sum P, C] of B smoothing problems, each with its own loop count, with gradients for the smoother's
+    parameters: B calls of :class:`_TrainSmooth` as one (gnnmp_smoother_train_batch_forward / _backward).  ``sb`` holds the
+    problems ordered by loop count, longest first; ``loops`` is that order's ctypes int32 array."""
+
+    @staticmethod
+    def forward(ctx, model, sb, loops, *params):
+        dev = sb.path.device
+        _check_limits(sb)
+        h = model._native(dev, for_training=True)
+        cb = _cbatch(sb)
+        need = ctypes.c_size_t()
+        _lib.check(_lib.lib().gnnmp_smoother_train_batch_workspace_bytes(h, ctypes.byref(cb), loops, ctypes.byref(need)),
+                   'gnnmp_smoother_train_batch_workspace_bytes')
+        ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
+        out = torch.empty_like(sb.path)
+        stats = torch.empty(sb.n, max(loops), 2, model.embed_size, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            st = torch.cuda.current_stream().cuda_stream
+            _lib.check(_lib.lib().gnnmp_smoother_train_batch_forward(h, ctypes.byref(cb), loops, out.data_ptr(), stats.data_ptr(),
+                                                                     ws.data_ptr(), ws.numel(), st),
+                       'gnnmp_smoother_train_batch_forward')
+        ctx.model, ctx.sb, ctx.loops, ctx.ws, ctx.handle = model, sb, loops, ws, h
+        ctx.mark_non_differentiable(stats)
+        return out, stats
+
+    @staticmethod
+    def backward(ctx, d_out, _d_stats):
+        model, sb, dev = ctx.model, ctx.sb, ctx.sb.path.device
+        cb = _cbatch(sb)
+        n = int(_lib.lib().gnnmp_smoother_grad_floats(ctx.handle))
+        grad = torch.empty(n, dtype=torch.float32, device=dev)
+        d_out = d_out.contiguous().float()
+        with torch.cuda.device(dev):
+            st = torch.cuda.current_stream().cuda_stream
+            _lib.check(_lib.lib().gnnmp_smoother_train_batch_backward(ctx.handle, ctypes.byref(cb), ctx.loops, d_out.data_ptr(),
+                                                                      grad.data_ptr(), ctx.ws.data_ptr(), ctx.ws.numel(), st),
+                       'gnnmp_smoother_train_batch_backward')
         sd = model.state_dict(keep_vars=True)
         out, off = [], 0
         for name, numel in model._manifest:
@@ -361,6 +428,75 @@ class ModelSmoother(nn.Module):
                 bn.running_mean.mul_(1 - m).add_(stats[it, 0].to(bn.running_mean.device), alpha=m)
                 bn.running_var.mul_(1 - m).add_(stats[it, 1].to(bn.running_var.device), alpha=m)
         return out
+
+    def forward_train_batch(self, sb, loops):
+        """:meth:`forward_train` for a whole :class:`SmoothBatch` in one call: new waypoints [sum P, C] with a ``grad_fn``,
+        equal to one ``forward_train`` per problem (BatchNorm statistics per problem, nothing pooled).  ``loops``: one loop
+        count per problem, or one int for all of them; problem b's rows are its path after ``loops[b]`` iterations.  The
+        running statistics end up as after the B chained calls, problem 0's iterations first.  fp32 only."""
+        if self.mlp_dtype != 'fp32':
+            raise RuntimeError('training runs in fp32 (mlp_dtype = %r)' % self.mlp_dtype)
+        if sb.path.device.type != 'cuda':
+            raise RuntimeError('gnnmp runs on the GPU only (got %s tensors); there is no CPU fallback' % sb.path.device)
+        loops = [int(v) for v in loops] if hasattr(loops, '__len__') else [int(loops)] * sb.n
+        if len(loops) != sb.n:
+            raise ValueError('%d loop counts for %d smoothing problems' % (len(loops), sb.n))
+        if min(loops) < 1:
+            raise ValueError('loop counts must be at least 1 (got %d)' % min(loops))
+        # the library takes the problems longest loop first (gnnmp.h): the ones still running are then a prefix of every range
+        order = sorted(range(sb.n), key=lambda b: -loops[b])
+        ordered = order == list(range(sb.n))
+        run = sb
+        if not ordered or sb.path_ptr is None:
+            if not hasattr(sb, 'free_counts'):
+                raise ValueError('forward_train_batch needs the host-side counts SmoothBatch(...) / SmoothBatch.from_device(...) keep')
+            run = _reordered(sb, order)
+        self._native(sb.path.device, for_training=True)
+        sd = self.state_dict(keep_vars=True)
+        c_loops = (ctypes.c_int32 * sb.n)(*[loops[b] for b in order])
+        out, stats = _TrainSmoothBatch.apply(self, run, c_loops, *[sd[n] for n, _ in self._manifest])
+        if not ordered:                       # rows back in the caller's order (differentiable)
+            starts = [0]
+            for b in order:
+                starts.append(starts[-1] + sb.path_counts[b])
+            at = {b: i for i, b in enumerate(order)}
+            back = torch.cat([torch.arange(starts[at[b]], starts[at[b] + 1]) for b in range(sb.n)]).to(out.device)
+            out = out.index_select(0, back)
+        else:
+            at = {b: b for b in range(sb.n)}
+        bn = self.node_code[1]
+        with torch.no_grad():
+            # the updates of B chained forward_train calls, same arithmetic: mean and variance side by side, one counter bump
+            seq = torch.tensor([at[b] * stats.shape[1] + it for b in range(sb.n) for it in range(loops[b])], device=stats.device)
+            steps = stats.reshape(-1, 2, stats.shape[-1]).index_select(0, seq).to(bn.running_mean.device)
+            both = torch.stack((bn.running_mean, bn.running_var)).float()
+            n0 = int(bn.num_batches_tracked) if bn.momentum is None else 0
+            for j in range(steps.shape[0]):
+                m = 1.0 / float(n0 + j + 1) if bn.momentum is None else bn.momentum
+                both.mul_(1 - m).add_(steps[j], alpha=m)
+            bn.running_mean.copy_(both[0])
+            bn.running_var.copy_(both[1])
+            bn.num_batches_tracked += steps.shape[0]
+        return out
+
+    def training_loss(self, sb, targets, loops):
+        """The reference's loss of one optimizer step (train_smoother.py:55-58) over a :class:`SmoothBatch`: per problem
+        ``mse_loss(target[1:-1], pred[1:-1])`` with ``pred`` from :meth:`forward_train_batch`, averaged over the problems that
+        have an interior waypoint (``P_b <= 2`` makes no sample in the reference, train_smoother.py:97: neither summed nor
+        counted).  ``targets`` [sum P, C] is aligned with ``sb.path`` (what ``oracle_smooth.smoothing_targets`` returns)."""
+        pred = self.forward_train_batch(sb, loops)
+        if tuple(targets.shape) != tuple(pred.shape):
+            raise ValueError('targets %s do not match the batch\'s path rows %s' % (tuple(targets.shape), tuple(pred.shape)))
+        C = pred.shape[1]
+        counted = sum(1 for P in sb.path_counts if P > 2)
+        w = torch.zeros(pred.shape[0], dtype=torch.float32)
+        r = 0
+        for P in sb.path_counts:              # row weights: 1 / (interior elements of the problem * problems that count)
+            if P > 2:
+                w[r + 1:r + P - 1] = 1.0 / ((P - 2) * C * counted)
+            r += P
+        diff = targets.to(pred.device, pred.dtype) - pred
+        return (diff * diff * w.to(pred.device)[:, None]).sum()
 
     def forward(self, path, free, collided, obstacles=None, edge_index=None, loop=10, **kwargs):
         """Reference call (smoother.py:243): returns the new path [P, C]; ``obstacles`` and extra

@@ -292,7 +292,8 @@ int gnnmp_smoother_status_decode(const int32_t* words_host, int n_problems, int3
 /* ------------------------------------------------------------------------------------------
  * Training path of the smoother   (train_smoother.py:33-61 through model_smoother.py:104-142 under model.train())
  * ------------------------------------------------------------------------------------------
- * One problem per call (batch->n_problems == 1), fp32 handle.  The training forward differs from the inference one where
+ * One problem per call (batch->n_problems == 1, anything else is GNNMP_ERR_DIMS; gnnmp_smoother_train_batch_* below take B),
+ * fp32 handle.  The training forward differs from the inference one where
  * the reference's does: BatchNorm (node_code.1) normalises with the statistics of THIS call's node rows (path + free +
  * collided) in every loop iteration, and activations are kept.  bn_stats_or_null [loop][2][d] receives, per iteration, the
  * batch mean and the UNBIASED batch variance (what a caller needs to update running_mean / running_var the way
@@ -304,6 +305,27 @@ int gnnmp_smoother_train_forward(const gnnmp_smoother* h, const gnnmp_smooth_bat
                                  float* bn_stats_or_null, void* workspace, size_t workspace_bytes, void* hip_stream);
 int gnnmp_smoother_train_backward(const gnnmp_smoother* h, const gnnmp_smooth_batch* batch, int loop, const float* d_out_path,
                                   float* grad, void* workspace, size_t workspace_bytes, void* hip_stream);
+
+/* The same for B problems per call (the eight module calls of one optimizer step, train_smoother.py:33-61, as one): the result
+ * equals B independent calls above.  loops_host [B] (HOST memory: it decides how many launches are made) gives every problem
+ * its own loop count >= 1, and the problems must come ordered by it, longest first (loops_host non-increasing; the Python
+ * wrapper sorts and restores the caller's order), so that the problems still running in an iteration are a prefix of every
+ * row range.  BatchNorm normalises every problem with the statistics of its own P_b + F_b + Co_b rows; problem b stops after
+ * loops_host[b] iterations, out_path holds its state at that point (times scale), and in later iterations its rows contribute
+ * nothing: no statistics, no edges, no weight gradient.  bn_stats_or_null [B][max loop][2][d]: per (problem, iteration) the
+ * batch mean and the UNBIASED variance, rows past loops_host[b] zero.  train_batch_backward: d loss / d out_path
+ * [total_path, C] -> the SUM over problems of d loss / d parameters, manifest order; bit-identical for identical inputs.
+ * All four prefix arrays are required.  GNNMP_ERR_NULL for NULL arguments, GNNMP_ERR_ARG for a loop count below 1 or an
+ * ascending pair, GNNMP_ERR_DIMS for a bf16 handle or a problem beyond the per-problem limits above, GNNMP_ERR_WORKSPACE as
+ * elsewhere.  Same workspace (and the same loops_host) for forward and backward. */
+int gnnmp_smoother_train_batch_workspace_bytes(const gnnmp_smoother* h, const gnnmp_smooth_batch* shape, const int32_t* loops_host,
+                                               size_t* bytes);
+int gnnmp_smoother_train_batch_forward(const gnnmp_smoother* h, const gnnmp_smooth_batch* batch, const int32_t* loops_host,
+                                       float* out_path, float* bn_stats_or_null, void* workspace, size_t workspace_bytes,
+                                       void* hip_stream);
+int gnnmp_smoother_train_batch_backward(const gnnmp_smoother* h, const gnnmp_smooth_batch* batch, const int32_t* loops_host,
+                                        const float* d_out_path, float* grad, void* workspace, size_t workspace_bytes,
+                                        void* hip_stream);
 
 /* ------------------------------------------------------------------------------------------
  * Graph construction on the device   (create_data, eval_gnn.py:150-165; knn_graph :160,162; coalesce :164)

@@ -139,3 +139,27 @@ def smoother_step():
 ms_sm = timeit(smoother_step, 5)
 print('smoother training step (train_smoother.py:33-61 shape: 8 replay entries of 20 waypoints + 500 + 500 samples, loop 5, smooth_2d_attv3,\n'
       '  model.train(), one backward of the summed MSE, SGD + momentum)       %8.2f ms / optimizer step' % ms_sm)
+
+# ---- the same optimizer step as ONE batched forward / backward (ModelSmoother.training_loss: forward_train_batch + the loss of
+# train_smoother.py:55-58), at the reference's 8 replay entries and at 64
+from gnnmp.smoother import SmoothBatch  # noqa: E402
+
+
+def batched_leg(entries):
+    sb = SmoothBatch.from_device(torch.cat([e[0] for e in entries]), torch.cat([e[1] for e in entries]), torch.cat([e[2] for e in entries]),
+                                 torch.cat([e[3] for e in entries], dim=1), [e[0].shape[0] for e in entries],
+                                 [e[1].shape[0] for e in entries], [e[2].shape[0] for e in entries], [e[3].shape[1] for e in entries])
+    targets = torch.cat([e[4] for e in entries])
+
+    def step():
+        sopt.zero_grad()
+        sm.training_loss(sb, targets, 5).backward()
+        sopt.step()
+    return timeit(step, 5)
+
+
+ms_b8 = batched_leg(replay)
+ms_b64 = batched_leg(replay * 8)
+print('  the same 8 entries as one forward_train_batch + one backward          %8.2f ms / optimizer step' % ms_b8)
+print('  64 entries (the 8 above, eight times) as one batched call             %8.2f ms / optimizer step (%.3f ms / entry)'
+      % (ms_b64, ms_b64 / 64))
