@@ -147,6 +147,10 @@ def lib():
     L.gnnmp_explorer_train_workspace_bytes.argtypes = [vp, ctypes.POINTER(Batch), ctypes.c_int, ctypes.POINTER(sz)]
     L.gnnmp_explorer_train_forward.argtypes = [vp, ctypes.POINTER(Batch), ctypes.c_int, ctypes.c_int, vp, vp, sz, vp]
     L.gnnmp_explorer_train_backward.argtypes = [vp, ctypes.POINTER(Batch), ctypes.c_int, vp, vp, vp, sz, vp]
+    L.gnnmp_explorer_train_batch_workspace_bytes.argtypes = [vp, ctypes.POINTER(Batch), i32p, i32p, i32p, ctypes.POINTER(sz)]
+    L.gnnmp_explorer_train_batch_forward.argtypes = [vp, ctypes.POINTER(Batch), i32p, i32p, i32p, ctypes.c_int, vp, vp, sz, vp]
+    L.gnnmp_explorer_train_batch_backward.argtypes = [vp, ctypes.POINTER(Batch), i32p, i32p, i32p, vp, vp, vp, sz, vp]
+    L.gnnmp_explorer_train_batch_plan.argtypes = [ctypes.c_int32, i32p, i32p, i32p, ctypes.c_int32, i32p, i32p, i32p, i32p]
     L.gnnmp_explorer_forward_ex.argtypes = [vp, ctypes.POINTER(Batch), ctypes.c_int, ctypes.c_int, vp, vp, vp, sz, vp, vp]
     L.gnnmp_explorer_status_words.argtypes = [ctypes.POINTER(Batch), ctypes.POINTER(sz)]
     L.gnnmp_explorer_status.argtypes = [vp, ctypes.POINTER(Batch), vp, sz, vp, c_int32_p]
@@ -318,6 +322,37 @@ def train_dw_scratch_floats(R, K, O):
     if n < 0:
         check(int(n), 'gnnmp_train_dw_scratch_floats')
     return int(n)
+
+
+TRAIN_BATCH_MAX_LOOP = 64              # GNNMP_TRAIN_BATCH_MAX_LOOP of the header
+
+
+def i32_array(values):
+    return (ctypes.c_int32 * max(len(values), 1))(*[int(x) for x in values])
+
+
+def explorer_train_batch_plan_raw(loops, node_counts, edge_counts):
+    """gnnmp_explorer_train_batch_plan (host only) -> (status, active, node_rows, edge_rows): per iteration the graphs still
+    running and their padded node / edge rows; the lists are empty when the status is not 0."""
+    L = lib()
+    G = len(loops)
+    lp, nc, ec = i32_array(loops), i32_array(node_counts), i32_array(edge_counts)
+    n_it = ctypes.c_int32(0)
+    rc = L.gnnmp_explorer_train_batch_plan(G, lp, nc, ec, 0, None, None, None, ctypes.byref(n_it))
+    if rc != 0:
+        return rc, [], [], []
+    cap = n_it.value
+    a, nr, er = ((ctypes.c_int32 * cap)() for _ in range(3))
+    rc = L.gnnmp_explorer_train_batch_plan(G, lp, nc, ec, cap, a, nr, er, ctypes.byref(n_it))
+    if rc != 0:
+        return rc, [], [], []
+    return 0, list(a), list(nr), list(er)
+
+
+def explorer_train_batch_plan(loops, node_counts, edge_counts):
+    rc, a, nr, er = explorer_train_batch_plan_raw(loops, node_counts, edge_counts)
+    check(rc, 'gnnmp_explorer_train_batch_plan')
+    return a, nr, er
 
 
 def manifest(kind, dims):

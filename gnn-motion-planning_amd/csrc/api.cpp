@@ -1726,6 +1726,229 @@ extern "C" int gnnmp_explorer_train_backward(const gnnmp_explorer* h, const gnnm
     return GNNMP_OK;
 }
 
+// ---- a loop count per graph (train_explorer.py:148), graphs longest loop first: the graphs of iteration `it` are a prefix of the
+// batch, of the padded node space and of the padded CSR edge space, and every launch of that iteration covers the prefix only
+extern "C" int gnnmp_explorer_train_batch_plan(int32_t n_graphs, const int32_t* loops_host, const int32_t* node_counts_host,
+                                               const int32_t* edge_counts_host, int32_t cap, int32_t* active, int32_t* node_rows,
+                                               int32_t* edge_rows, int32_t* n_iters) {
+    if (!loops_host || !node_counts_host || !edge_counts_host || !n_iters) return GNNMP_ERR_NULL;
+    if (cap > 0 && (!active || !node_rows || !edge_rows)) return GNNMP_ERR_NULL;
+    if (n_graphs < 1 || cap < 0) return GNNMP_ERR_ARG;
+    for (int g = 0; g < n_graphs; ++g) {
+        if (loops_host[g] < 1 || loops_host[g] > GNNMP_TRAIN_BATCH_MAX_LOOP) return GNNMP_ERR_ARG;
+        if (g > 0 && loops_host[g] > loops_host[g - 1]) return GNNMP_ERR_ARG;          // longest first
+        if (node_counts_host[g] < 0 || edge_counts_host[g] < 0) return GNNMP_ERR_ARG;
+    }
+    *n_iters = loops_host[0];
+    if (cap == 0) return GNNMP_OK;
+    if (cap < loops_host[0]) return GNNMP_ERR_ARG;
+    // iterations from the last to the first: the prefix only grows, so one walk over the graphs serves all of them
+    int a = 0;
+    long long nr = 0, er = 0;
+    for (int it = loops_host[0] - 1; it >= 0; --it) {
+        while (a < n_graphs && loops_host[a] > it) {
+            nr += round_up_i(node_counts_host[a], kPad);           // the prep stage's rule (prep_prefix): node_ptr_pad / edge_ptr_pad
+            er += round_up_i(edge_counts_host[a], kPad);
+            ++a;
+        }
+        if (nr > 0x7fffffffLL || er > 0x7fffffffLL) return GNNMP_ERR_ARG;
+        active[it] = a; node_rows[it] = (int)nr; edge_rows[it] = (int)er;
+    }
+    return GNNMP_OK;
+}
+
+namespace {
+
+struct TrainBatchPlan {
+    int L;                                               // loops_host[0]
+    int A[kTrainBatchMaxLoop], Np[kTrainBatchMaxLoop], Ep[kTrainBatchMaxLoop];
+};
+
+// the argument checks the three entry points share; GNNMP_OK and the plan
+int train_batch_args(const gnnmp_explorer* h, const gnnmp_batch* b, const int32_t* loops, const int32_t* ncnt, const int32_t* ecnt,
+                     TrainBatchPlan& p) {
+    const int rc = gnnmp_explorer_train_batch_plan(b->n_graphs, loops, ncnt, ecnt, kTrainBatchMaxLoop, p.A, p.Np, p.Ep, &p.L);
+    if (rc != GNNMP_OK) return rc;
+    long long n = 0, e = 0;
+    for (int g = 0; g < b->n_graphs; ++g) { n += ncnt[g]; e += ecnt[g]; }
+    if (n != b->total_nodes || e != b->total_edges) return GNNMP_ERR_ARG;
+    if (h->dims.mlp_dtype != GNNMP_F32) return GNNMP_ERR_DIMS;          // training runs in fp32
+    return GNNMP_OK;
+}
+
+TrainGeom geom_prefix(TrainGeom q, int Np, int Ep) {      // the geometry launchers bound their rows / slots by these two
+    q.Npad = Np; q.Epad = Ep;
+    return q;
+}
+
+}  // namespace
+
+extern "C" int gnnmp_explorer_train_batch_workspace_bytes(const gnnmp_explorer* h, const gnnmp_batch* shape, const int32_t* loops_host,
+                                                          const int32_t* node_counts_host, const int32_t* edge_counts_host,
+                                                          size_t* bytes) {
+    if (!h || !shape || !loops_host || !node_counts_host || !edge_counts_host || !bytes) return GNNMP_ERR_NULL;
+    TrainBatchPlan p;
+    const int rc = train_batch_args(h, shape, loops_host, node_counts_host, edge_counts_host, p);
+    if (rc != GNNMP_OK) return rc;
+    return gnnmp_explorer_train_workspace_bytes(h, shape, p.L, bytes);
+}
+
+extern "C" int gnnmp_explorer_train_batch_forward(const gnnmp_explorer* h, const gnnmp_batch* b, const int32_t* loops_host,
+                                                  const int32_t* node_counts_host, const int32_t* edge_counts_host, int use_obstacles,
+                                                  float* edge_scores, void* ws, size_t ws_bytes, void* hip_stream) {
+    if (!h || !b || !loops_host || !node_counts_host || !edge_counts_host || !ws || (b->total_edges > 0 && !edge_scores))
+        return GNNMP_ERR_NULL;
+    if (!b->node_ptr || !b->edge_ptr || !b->obs_ptr) return GNNMP_ERR_NULL;
+    TrainBatchPlan pl;
+    const int prc = train_batch_args(h, b, loops_host, node_counts_host, edge_counts_host, pl);
+    if (prc != GNNMP_OK) return prc;
+    Carve c;
+    if (!carve(h, b, c)) return GNNMP_ERR_ARG;
+    TrainCarve t;
+    train_carve(h, b, pl.L, c, t);
+    if (ws_bytes < t.inf_bytes + t.total_floats * sizeof(float) || (reinterpret_cast<uintptr_t>(ws) & 255)) return GNNMP_ERR_WORKSPACE;
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    float* T = reinterpret_cast<float*>(static_cast<char*>(ws) + t.inf_bytes);
+    const int d = h->dims.embed_size, C = h->dims.config_size;
+    const int Np = pl.Np[0], Ep = pl.Ep[0];             // every graph runs iteration 0: the rows in use (<= c.Npad / c.Epad, upper bounds)
+    // rows no kernel writes (padding tiles, graphs past their loop count) must hold finite numbers
+    HIP_TRY(hipMemsetAsync(T, 0, t.total_floats * sizeof(float), st));
+    const int rc = forward_impl(h, b, pl.L, use_obstacles, nullptr, nullptr, ws, t.inf_bytes, hip_stream, T + t.NF, T + t.EF, true);
+    if (rc != GNNMP_OK) return rc;
+    const TrainGeom q = train_geom(h, b, c, t, ws);
+    const TrainGeom qa = geom_prefix(q, Np, Ep);
+    const WRef nc0 = wref(h, nullptr, "node_code.0"), nc2 = wref(h, nullptr, "node_code.2"), ec0 = wref(h, nullptr, "edge_code.0"),
+               ec2 = wref(h, nullptr, "edge_code.2"), enc = wref(h, nullptr, "encoder"), l00 = wref(h, nullptr, "process.lin_0.0"),
+               l02 = wref(h, nullptr, "process.lin_0.2"), l1 = wref(h, nullptr, "process.lin_1"), dec = wref(h, nullptr, "decoder"),
+               p0 = wref(h, nullptr, "policy.0"), p2 = wref(h, nullptr, "policy.2"), p4 = wref(h, nullptr, "policy.4", false);
+    const float* ge = nullptr;
+    for (size_t i = 0; i < h->man.size(); ++i) if (h->man[i].name == "goal_encoder") ge = h->w_raw_dev + h->man_off[i];
+    HIP_TRY(t_out_csr(q, st));
+    HIP_TRY(t_node_in(qa, T + t.NCin, st));
+    HIP_TRY(t_linear(Np, 4 * C, d, T + t.NCin, nc0.w, nc0.b, T + t.NCh, true, st));
+    HIP_TRY(t_linear(Np, d, d, T + t.NCh, nc2.w, nc2.b, T + t.NC, false, st));
+    HIP_TRY(t_edge_in(qa, T + t.ECin, st));
+    HIP_TRY(t_linear(Ep, 2 * C, d, T + t.ECin, ec0.w, ec0.b, T + t.ECh, true, st));
+    HIP_TRY(t_linear(Ep, d, d, T + t.ECh, ec2.w, ec2.b, T + t.EC, false, st));
+    HIP_TRY(t_h0(qa, d, ge, T + t.H0, st));
+    const float* Hprev = T + t.H0;
+    TrainLoopRows lr;
+    lr.n_it = pl.L;
+    for (int it = 0; it < kTrainBatchMaxLoop; ++it) lr.rows[it] = it < pl.L ? pl.Np[it] : 0;
+    for (int it = 0; it < pl.L; ++it) {
+        float* I = T + t.it0 + t.it_stride * (size_t)it;
+        const int Na = pl.Np[it], Ea = pl.Ep[it];        // graphs with loops_host[g] > it
+        const TrainGeom qi = geom_prefix(q, Na, Ea);
+        HIP_TRY(t_concat(Na, d, 4, T + t.NC, T + t.NF, T + t.H0, Hprev, I + t.Xin, st));                 // model.py:141
+        HIP_TRY(t_linear(Na, 4 * d, d, I + t.Xin, enc.w, enc.b, I + t.X, false, st));
+        HIP_TRY(t_msg_in(qi, d, I + t.X, T + t.EF, T + t.EC, T + t.T5a, st));                            // model.py:38-39
+        HIP_TRY(t_linear(Ea, 5 * d, d, T + t.T5a, l00.w, l00.b, I + t.Zh, true, st));
+        HIP_TRY(t_linear(Ea, d, d, I + t.Zh, l02.w, l02.b, T + t.Te1, false, st));
+        HIP_TRY(t_segment_max(qi, d, T + t.Te1, I + t.A, reinterpret_cast<int*>(I + t.arg), st));        // model.py:33
+        HIP_TRY(t_concat(Na, d, 2, I + t.X, I + t.A, nullptr, nullptr, T + t.cat2, st));
+        HIP_TRY(t_linear(Na, 2 * d, d, T + t.cat2, l1.w, l1.b, I + t.H, false, st));                     // model.py:36
+        Hprev = I + t.H;
+    }
+    // every graph's own last hidden state (model.py:143 at loop = loops_host[g])
+    HIP_TRY(t_final_cat(lr, d, T + t.NC, T + t.it0 + t.H, t.it_stride, T + t.DinCat, st));
+    HIP_TRY(t_linear(Np, 2 * d, d, T + t.DinCat, dec.w, dec.b, T + t.Dn, false, st));
+    HIP_TRY(t_pol_in(qa, d, T + t.Dn, T + t.EF, T + t.Pin, st));                                         // model.py:145
+    HIP_TRY(t_linear(Ep, 3 * d, d, T + t.Pin, p0.w, p0.b, T + t.P1, true, st));
+    HIP_TRY(t_linear(Ep, d, d, T + t.P1, p2.w, p2.b, T + t.P2, true, st));
+    HIP_TRY(t_linear(Ep, d, 1, T + t.P2, p4.w, nullptr, T + t.sc, false, st));
+    if (b->total_edges > 0) HIP_TRY(t_scores_out(qa, T + t.sc, edge_scores, st));
+    return GNNMP_OK;
+}
+
+extern "C" int gnnmp_explorer_train_batch_backward(const gnnmp_explorer* h, const gnnmp_batch* b, const int32_t* loops_host,
+                                                   const int32_t* node_counts_host, const int32_t* edge_counts_host,
+                                                   const float* d_edge_scores, float* grad, void* ws, size_t ws_bytes, void* hip_stream) {
+    if (!h || !b || !loops_host || !node_counts_host || !edge_counts_host || !ws || !grad || (b->total_edges > 0 && !d_edge_scores))
+        return GNNMP_ERR_NULL;
+    if (!b->node_ptr || !b->edge_ptr || !b->obs_ptr) return GNNMP_ERR_NULL;
+    TrainBatchPlan pl;
+    const int prc = train_batch_args(h, b, loops_host, node_counts_host, edge_counts_host, pl);
+    if (prc != GNNMP_OK) return prc;
+    Carve c;
+    if (!carve(h, b, c)) return GNNMP_ERR_ARG;
+    TrainCarve t;
+    train_carve(h, b, pl.L, c, t);
+    if (ws_bytes < t.inf_bytes + t.total_floats * sizeof(float) || (reinterpret_cast<uintptr_t>(ws) & 255)) return GNNMP_ERR_WORKSPACE;
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    float* T = reinterpret_cast<float*>(static_cast<char*>(ws) + t.inf_bytes);
+    const int d = h->dims.embed_size, C = h->dims.config_size;
+    const int Np = pl.Np[0], Ep = pl.Ep[0];
+    // the weight gradients' second stage sums in the order of the uniform call (c.Npad / c.Epad rows, the missing ones all zero)
+    const int No = c.Npad, Eo = c.Epad;
+    const TrainGeom q = train_geom(h, b, c, t, ws);
+    const TrainGeom qa = geom_prefix(q, Np, Ep);
+    HIP_TRY(hipMemsetAsync(grad, 0, (size_t)h->n_raw * sizeof(float), st));
+    const WRef nc0 = wref(h, grad, "node_code.0"), nc2 = wref(h, grad, "node_code.2"), ec0 = wref(h, grad, "edge_code.0"),
+               ec2 = wref(h, grad, "edge_code.2"), enc = wref(h, grad, "encoder"), l00 = wref(h, grad, "process.lin_0.0"),
+               l02 = wref(h, grad, "process.lin_0.2"), l1 = wref(h, grad, "process.lin_1"), dec = wref(h, grad, "decoder"),
+               p0 = wref(h, grad, "policy.0"), p2 = wref(h, grad, "policy.2"), p4 = wref(h, grad, "policy.4", false);
+    float* g_ge = nullptr;
+    for (size_t i = 0; i < h->man.size(); ++i) if (h->man[i].name == "goal_encoder") g_ge = grad + h->man_off[i];
+    // ---- policy head (model.py:145-146), all graphs
+    HIP_TRY(t_scores_in(qa, d_edge_scores, T + t.Te1, st));
+    HIP_TRY(t_linear_dw(Ep, d, 1, T + t.Te1, T + t.P2, p4.gw, nullptr, T + t.dwp, st, Eo));
+    HIP_TRY(t_linear_dx(Ep, d, 1, T + t.Te1, p4.w, T + t.Te2, false, st));          // dP2
+    HIP_TRY(t_relu_bwd((size_t)Ep * d, T + t.P2, T + t.Te2, st));
+    HIP_TRY(t_linear_dw(Ep, d, d, T + t.Te2, T + t.P1, p2.gw, p2.gb, T + t.dwp, st, Eo));
+    HIP_TRY(t_linear_dx(Ep, d, d, T + t.Te2, p2.w, T + t.Te1, false, st));          // dP1
+    HIP_TRY(t_relu_bwd((size_t)Ep * d, T + t.P1, T + t.Te1, st));
+    HIP_TRY(t_linear_dw(Ep, 3 * d, d, T + t.Te1, T + t.Pin, p0.gw, p0.gb, T + t.dwp, st, Eo));
+    HIP_TRY(t_linear_dx(Ep, 3 * d, d, T + t.Te1, p0.w, T + t.T3, false, st));       // dPin
+    HIP_TRY(t_fill((size_t)Np * d, T + t.dDn, 0.f, st));
+    HIP_TRY(t_pol_in_bwd(qa, d, T + t.T3, T + t.dDn, st));
+    // ---- decoder (model.py:143): its input gradient's second half is d h_final of EVERY graph; it waits in dDn (free from here on)
+    // until the backward loop reaches the graph's last iteration
+    HIP_TRY(t_linear_dw(Np, 2 * d, d, T + t.dDn, T + t.DinCat, dec.gw, dec.gb, T + t.dwp, st, No));
+    HIP_TRY(t_linear_dx(Np, 2 * d, d, T + t.dDn, dec.w, T + t.dcat2, false, st));
+    HIP_TRY(t_split(Np, d, 2, 0, T + t.dcat2, T + t.dNC, false, st));
+    HIP_TRY(t_split(Np, d, 2, 1, T + t.dcat2, T + t.dDn, false, st));
+    HIP_TRY(t_fill((size_t)Np * d, T + t.dH0, 0.f, st));
+    HIP_TRY(t_fill((size_t)Ep * d, T + t.dEC, 0.f, st));
+    // ---- the loop, backwards (model.py:139-142), iteration `it` over the graphs that ran it
+    for (int it = pl.L - 1; it >= 0; --it) {
+        float* I = T + t.it0 + t.it_stride * (size_t)it;
+        const int Na = pl.Np[it], Ea = pl.Ep[it];
+        const TrainGeom qi = geom_prefix(q, Na, Ea);
+        HIP_TRY(t_seed_dh(Na, it + 1 < pl.L ? pl.Np[it + 1] : 0, d, T + t.dDn, T + t.dXin, T + t.dH, st));
+        HIP_TRY(t_concat(Na, d, 2, I + t.X, I + t.A, nullptr, nullptr, T + t.cat2, st));
+        HIP_TRY(t_linear_dw(Na, 2 * d, d, T + t.dH, T + t.cat2, l1.gw, l1.gb, T + t.dwp, st, No));
+        HIP_TRY(t_linear_dx(Na, 2 * d, d, T + t.dH, l1.w, T + t.dcat2, false, st));
+        HIP_TRY(t_split(Na, d, 2, 0, T + t.dcat2, T + t.dX, false, st));
+        HIP_TRY(t_split(Na, d, 2, 1, T + t.dcat2, T + t.dA, false, st));
+        HIP_TRY(t_fill((size_t)Ea * d, T + t.Te1, 0.f, st));                        // dM
+        HIP_TRY(t_segment_max_bwd(Na, d, T + t.dA, reinterpret_cast<const int*>(I + t.arg), T + t.Te1, st));
+        HIP_TRY(t_linear_dw(Ea, d, d, T + t.Te1, I + t.Zh, l02.gw, l02.gb, T + t.dwp, st, Eo));
+        HIP_TRY(t_linear_dx(Ea, d, d, T + t.Te1, l02.w, T + t.Te2, false, st));      // dZh
+        HIP_TRY(t_relu_bwd((size_t)Ea * d, I + t.Zh, T + t.Te2, st));
+        HIP_TRY(t_msg_in(qi, d, I + t.X, T + t.EF, T + t.EC, T + t.T5a, st));        // Zin recomputed
+        HIP_TRY(t_linear_dw(Ea, 5 * d, d, T + t.Te2, T + t.T5a, l00.gw, l00.gb, T + t.dwp, st, Eo));
+        HIP_TRY(t_linear_dx(Ea, 5 * d, d, T + t.Te2, l00.w, T + t.T5b, false, st));   // dZin
+        HIP_TRY(t_msg_in_bwd(qi, d, T + t.T5b, T + t.dX, T + t.dEC, st));
+        HIP_TRY(t_linear_dw(Na, 4 * d, d, T + t.dX, I + t.Xin, enc.gw, enc.gb, T + t.dwp, st, No));
+        HIP_TRY(t_linear_dx(Na, 4 * d, d, T + t.dX, enc.w, T + t.dXin, false, st));
+        HIP_TRY(t_split(Na, d, 4, 0, T + t.dXin, T + t.dNC, true, st));              // node_code
+        HIP_TRY(t_split(Na, d, 4, 2, T + t.dXin, T + t.dH0, true, st));              // h_0   (part 1 = node_free_code: detached)
+        // part 3, d h_{i-1}: the next round's t_seed_dh takes it; h_i of the first iteration IS h_0
+        if (it == 0) HIP_TRY(t_split(Na, d, 4, 3, T + t.dXin, T + t.dH0, true, st));
+    }
+    HIP_TRY(t_h0_bwd(qa, d, T + t.dH0, g_ge, st));
+    // ---- edge_code, node_code encoders (model.py:119-120), all graphs
+    HIP_TRY(t_linear_dw(Ep, d, d, T + t.dEC, T + t.ECh, ec2.gw, ec2.gb, T + t.dwp, st, Eo));
+    HIP_TRY(t_linear_dx(Ep, d, d, T + t.dEC, ec2.w, T + t.Te1, false, st));
+    HIP_TRY(t_relu_bwd((size_t)Ep * d, T + t.ECh, T + t.Te1, st));
+    HIP_TRY(t_linear_dw(Ep, 2 * C, d, T + t.Te1, T + t.ECin, ec0.gw, ec0.gb, T + t.dwp, st, Eo));
+    HIP_TRY(t_linear_dw(Np, d, d, T + t.dNC, T + t.NCh, nc2.gw, nc2.gb, T + t.dwp, st, No));
+    HIP_TRY(t_linear_dx(Np, d, d, T + t.dNC, nc2.w, T + t.dX, false, st));
+    HIP_TRY(t_relu_bwd((size_t)Np * d, T + t.NCh, T + t.dX, st));
+    HIP_TRY(t_linear_dw(Np, 4 * C, d, T + t.dX, T + t.NCin, nc0.gw, nc0.gb, T + t.dwp, st, No));
+    return GNNMP_OK;
+}
+
 // =============================================================================================
 // training path of the smoother (train_smoother.py:33-61; model_smoother.py:104-142 under model.train())
 // =============================================================================================

@@ -283,7 +283,10 @@ bool t_linear_dx_mfma(int K, int O);
 bool t_linear_dw_mfma(int K, int O);
 hipError_t t_linear(int R, int K, int O, const float* X, const float* W, const float* b, float* Y, bool relu, hipStream_t st);
 hipError_t t_linear_dx(int R, int K, int O, const float* dY, const float* W, float* dX, bool accumulate, hipStream_t st);
-hipError_t t_linear_dw(int R, int K, int O, const float* dY, const float* X, float* dW, float* db, float* scratch, hipStream_t st);
+// R_order > R: the second stage cuts its eight slices as it would for R_order rows, so a call over a prefix of R rows sums in the
+// order of the call over all R_order rows whose other rows have dY = 0 (the ragged-loop training path); 0 = R itself
+hipError_t t_linear_dw(int R, int K, int O, const float* dY, const float* X, float* dW, float* db, float* scratch, hipStream_t st,
+                       int R_order = 0);
 hipError_t t_relu_bwd(size_t n, const float* y, float* dy, hipStream_t st);
 hipError_t t_fill(size_t n, float* x, float val, hipStream_t st);
 hipError_t t_node_in(const TrainGeom& q, float* out, hipStream_t st);
@@ -301,6 +304,20 @@ hipError_t t_segment_max(const TrainGeom& q, int D, const float* M, float* A, in
 hipError_t t_segment_max_bwd(int Npad, int D, const float* dA, const int* arg, float* dM, hipStream_t st);
 hipError_t t_scores_out(const TrainGeom& q, const float* slot_scores, float* out, hipStream_t st);
 hipError_t t_scores_in(const TrainGeom& q, const float* d_out, float* d_slot, hipStream_t st);
+
+// the explorer's training path with a loop count per graph, longest first (gnnmp_explorer_train_batch_*): rows[it] = padded node
+// rows of the graphs still running in iteration it -- non-increasing multiples of kPad, rows[0] = all graphs
+constexpr int kTrainBatchMaxLoop = 64;      // GNNMP_TRAIN_BATCH_MAX_LOOP: the table travels as a kernel argument
+struct TrainLoopRows {
+    int n_it;
+    int rows[kTrainBatchMaxLoop];
+};
+// out[n] = [NC[n], H of iteration (loop count of n's graph) - 1 [n]]  (model.py:143), n < lr.rows[0]; H_it0 = iteration 0's H, the
+// others it_stride floats apart.  D in {32, 64}
+hipError_t t_final_cat(const TrainLoopRows& lr, int D, const float* NC, const float* H_it0, size_t it_stride, float* out, hipStream_t st);
+// its adjoint, per backward iteration: dH[n] = d_dec[n] for rows in [rows_next, rows_it) (graphs whose LAST iteration this is: the
+// decoder's input gradient), dH[n] = dXin[n, 3D:4D] below rows_next (graphs that ran the next iteration: h_{i-1} of its encoder input)
+hipError_t t_seed_dh(int rows_it, int rows_next, int D, const float* d_dec, const float* dXin, float* dH, hipStream_t st);
 
 hipError_t t_sm_nodes_in(int P, int F, int Co, int C, float scale, const float* cur, const float* free_pts, const float* coll, float* out,
                          hipStream_t st);

@@ -79,11 +79,12 @@ __global__ __launch_bounds__(256) void rows_linear_dw_partial_kernel(int R, int 
 // second stage: element i of dW / db += the nblk partials in a FIXED order -- eight contiguous slices of the block range summed side by
 // side (ascending inside a slice), the eight slice sums added in ascending order.  (One serial loop over all blocks per element was
 // 26 us per layer at 88 blocks and 170 us at 700: the second largest item of a training step.)
-__global__ __launch_bounds__(256) void dw_reduce_kernel(int nblk, int OK, int O, const float* __restrict__ part, float* __restrict__ dW, float* __restrict__ db) {
+// per = blocks per slice: ceil(nblk / 8), or that of a LARGER block count whose trailing blocks are not there (t_linear_dw's R_order).
+__global__ __launch_bounds__(256) void dw_reduce_kernel(int nblk, int per, int OK, int O, const float* __restrict__ part, float* __restrict__ dW, float* __restrict__ db) {
     __shared__ float sm[8][32];
     const int l = threadIdx.x & 31, sl = threadIdx.x >> 5;
     const int i = blockIdx.x * 32 + l;
-    const int per = (nblk + 7) >> 3, b0 = sl * per, b1 = min(nblk, b0 + per);
+    const int b0 = sl * per, b1 = min(nblk, b0 + per);
     float acc = 0.f;
     if (i < OK + O)
         for (int b = b0; b < b1; ++b) acc += part[(size_t)b * (OK + O) + i];
@@ -506,6 +507,29 @@ __global__ void scores_in_kernel(TrainGeom q, const float* __restrict__ d_out, f
     d_slot[e] = rec.x >= 0 ? d_out[rec.z] : 0.f;
 }
 
+// ---- a loop count per graph, longest first (gnnmp_explorer_train_batch_*).  Row streams: one 16-byte access per lane, D / 4 lanes
+// per row (a full 128-byte row per 8 lanes at D = 32), a wave covers 64 / (D / 4) consecutive rows starting at a multiple of that
+// count -- inside one kPad block, whose rows share a graph and so a loop count: the look-ups below run on the wave's first row.
+// out[n] = [NC[n], H_{L(n) - 1}[n]] with L(n) = the number of iterations whose active prefix lr.rows[it] holds row n
+__global__ __launch_bounds__(256) void final_cat_kernel(TrainLoopRows lr, int D4, const float4* __restrict__ NC,
+                                                        const float4* __restrict__ H_it0, size_t it_stride4, float4* __restrict__ out) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (size_t)lr.rows[0] * 2 * D4) return;
+    const int n = (int)(i / (2 * D4)), c = (int)(i % (2 * D4));
+    const int n0 = __builtin_amdgcn_readfirstlane(n);
+    int L = 0;
+    for (int it = 0; it < lr.n_it; ++it) L += lr.rows[it] > n0 ? 1 : 0;          // rows[] descends: the graph ran iterations 0 .. L - 1
+    out[i] = c < D4 ? NC[(size_t)n * D4 + c] : H_it0[(size_t)(L - 1) * it_stride4 + (size_t)n * D4 + (c - D4)];
+}
+__global__ __launch_bounds__(256) void seed_dh_kernel(int rows_it, int rows_next, int D4, const float4* __restrict__ d_dec,
+                                                      const float4* __restrict__ dXin, float4* __restrict__ dH) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (size_t)rows_it * D4) return;
+    const int n = (int)(i / D4), c = (int)(i % D4);
+    const int n0 = __builtin_amdgcn_readfirstlane(n);
+    dH[i] = n0 >= rows_next ? d_dec[i] : dXin[(size_t)n * 4 * D4 + 3 * D4 + c];
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 static inline unsigned blocks(size_t n) { return (unsigned)((n + 255) / 256); }
 
@@ -538,9 +562,12 @@ hipError_t t_linear_dx(int R, int K, int O, const float* dY, const float* W, flo
     return hipSuccess;
 }
 size_t t_linear_dw_scratch_floats(int R, int K, int O) { return (size_t)((R + kDwRows - 1) / kDwRows) * ((size_t)O * K + O); }
-hipError_t t_linear_dw(int R, int K, int O, const float* dY, const float* X, float* dW, float* db, float* scratch, hipStream_t st) {
+hipError_t t_linear_dw(int R, int K, int O, const float* dY, const float* X, float* dW, float* db, float* scratch, hipStream_t st,
+                       int R_order) {
     if (R <= 0) return hipSuccess;
     int nblk = (R + kDwRows - 1) / kDwRows;
+    static_assert(kDwRows == kDwRowsM, "both first stages cut the rows into the same blocks: one slice width serves them");
+    const int per = ((R_order > R ? (R_order + kDwRows - 1) / kDwRows : nblk) + 7) >> 3;
     if (t_linear_dw_mfma(K, O)) {
         nblk = (R + kDwRowsM - 1) / kDwRowsM;             // fewer, larger chunks: the scratch sized for kDwRows covers them
         const int pairs = ((O + 31) / 32) * ((K + 1 + 31) / 32);
@@ -549,7 +576,7 @@ hipError_t t_linear_dw(int R, int K, int O, const float* dY, const float* X, flo
         hipLaunchKernelGGL(rows_linear_dw_partial_kernel, dim3(nblk), dim3(256), 0, st, R, K, O, dY, X, scratch);
     }
     TRAIN_LAUNCH_CHECK();
-    hipLaunchKernelGGL(dw_reduce_kernel, dim3((unsigned)(((size_t)O * K + O + 31) / 32)), dim3(256), 0, st, nblk, O * K, O, scratch, dW, db);
+    hipLaunchKernelGGL(dw_reduce_kernel, dim3((unsigned)(((size_t)O * K + O + 31) / 32)), dim3(256), 0, st, nblk, per, O * K, O, scratch, dW, db);
     TRAIN_LAUNCH_CHECK();
     return hipSuccess;
 }
@@ -652,6 +679,22 @@ hipError_t t_scores_out(const TrainGeom& q, const float* slot_scores, float* out
 }
 hipError_t t_scores_in(const TrainGeom& q, const float* d_out, float* d_slot, hipStream_t st) {
     hipLaunchKernelGGL(scores_in_kernel, dim3(blocks((size_t)q.Epad)), dim3(256), 0, st, q, d_out, d_slot);
+    TRAIN_LAUNCH_CHECK();
+    return hipSuccess;
+}
+hipError_t t_final_cat(const TrainLoopRows& lr, int D, const float* NC, const float* H_it0, size_t it_stride, float* out, hipStream_t st) {
+    if (lr.n_it < 1 || lr.rows[0] <= 0) return hipSuccess;
+    if ((D != 32 && D != 64) || (it_stride & 3)) return hipErrorInvalidValue;     // rows of whole 16-byte pieces, a wave inside one kPad block
+    hipLaunchKernelGGL(final_cat_kernel, dim3(blocks((size_t)lr.rows[0] * 2 * (D / 4))), dim3(256), 0, st, lr, D / 4,
+                       reinterpret_cast<const float4*>(NC), reinterpret_cast<const float4*>(H_it0), it_stride / 4, reinterpret_cast<float4*>(out));
+    TRAIN_LAUNCH_CHECK();
+    return hipSuccess;
+}
+hipError_t t_seed_dh(int rows_it, int rows_next, int D, const float* d_dec, const float* dXin, float* dH, hipStream_t st) {
+    if (rows_it <= 0) return hipSuccess;
+    if (D != 32 && D != 64) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(seed_dh_kernel, dim3(blocks((size_t)rows_it * (D / 4))), dim3(256), 0, st, rows_it, rows_next, D / 4,
+                       reinterpret_cast<const float4*>(d_dec), reinterpret_cast<const float4*>(dXin), reinterpret_cast<float4*>(dH));
     TRAIN_LAUNCH_CHECK();
     return hipSuccess;
 }

@@ -12,6 +12,7 @@ host after the graph build (whose edge count / per-problem edge offsets are the 
   policy_frontier          policy_data(...)                              (train_explorer.py:66-93)
   frontier_loss            -policy[frontier].log_softmax(0)[next_edge_idx] (train_explorer.py:172), per problem
   draw_device / draw_host  the random choices of :129, :148, :165, :170
+  forward_scores           the training forward, one pass per distinct loop value (forward_scores_batched: one pass in all)
   training_step            all of it for one batch: losses of the problems that were not skipped, ready for backward
 
 Per-problem status: 0 ok, 1 skipped (only the goal is reachable, :133), 2 skipped (the frontier emptied inside explore,
@@ -328,6 +329,19 @@ def forward_scores(model, graphs, goal, loops):
     return torch.cat(parts)[inv]
 
 
+def forward_scores_batched(model, graphs, goal, loops):
+    """:func:`forward_scores` as ONE ``model.train_scores_batch`` over all problems, each at its own loop count: one forward
+    and one backward per optimizer step, their launch count set by ``max(loops)`` alone (:func:`forward_scores` makes one
+    pass per distinct loop value).  Scores [sumE] in the batch's edge order; the sizes come from the host copies of the prefix
+    arrays, nothing is read back.
+
+    Both are fp32 evaluations of the same function and differ in the last bits: the launchers size their work by the row count
+    of the call -- the weight gradients stage their partial sums by it -- so the two sum in different orders.  A near-tie
+    between two edge scores inside an episode may therefore resolve differently."""
+    size = lambda ptr: [ptr[i + 1] - ptr[i] for i in range(graphs.n_problems)]          # noqa: E731
+    return model.train_scores_batch(graphs.batch(goal), loops, size(graphs.node_ptr_host), size(graphs.edge_ptr_host))
+
+
 def draw_start(graphs, paths, generator=None):
     """start = the floor(u * n_valid)-th valid node in id order (the goal itself when n_valid <= 1)."""
     dev = graphs.device
@@ -374,14 +388,16 @@ def draw_host(sizes, valid_of, step_of, loop, rng=np.random):
 
 
 # ---------------------------------------------------------------------------------------------------------------- driver
-def training_step(model, graphs, loop=10, max_steps=1000, generator=None, cpu_generator=None):
+def training_step(model, graphs, loop=10, max_steps=1000, generator=None, cpu_generator=None, batched=False):
     """Supervision + loss of one batch in device mode: draws, shortest paths, the training forward (one ``train_scores`` per
-    loop value), explore, replay, frontier loss.  Returns (loss = sum of the per-problem losses, info dict).  ``loss`` is
-    ready for ``backward()``; nothing is read back to the host."""
+    loop value; ``batched=True``: one ``train_scores_batch`` for all of them, :func:`forward_scores_batched`), explore,
+    replay, frontier loss.  Returns (loss = sum of the per-problem losses, info dict).  ``loss`` is ready for ``backward()``;
+    nothing is read back to the host.  The two forwards agree to fp32 rounding, not bit for bit (different summation orders
+    in the dense layers), so a near-tie inside an episode may resolve differently between them."""
     goal, loops = draw_device(graphs, loop, generator, cpu_generator)
     paths = shortest_paths(graphs, goal)
     start = draw_start(graphs, paths, generator)
-    scores = forward_scores(model, graphs, paths['goal'], loops)
+    scores = (forward_scores_batched if batched else forward_scores)(model, graphs, paths['goal'], loops)
     step, status = explore_steps(graphs, scores, start, paths['goal'], paths['n_valid'], max_steps)
     s = draw_step(step, generator)
     fr = policy_frontier(graphs, scores, paths, start, paths['goal'], s, status)

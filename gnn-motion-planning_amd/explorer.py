@@ -9,6 +9,7 @@ import ctypes
 import operator
 import os
 
+import numpy as np
 import torch
 from torch import nn
 from torch.nn import Linear as Lin, ReLU, Sequential as Seq
@@ -113,6 +114,49 @@ class _TrainScores(torch.autograd.Function):
             out.append(g)
             off += numel
         return (None, None, None) + tuple(out)
+
+
+class _TrainScoresBatch(torch.autograd.Function):
+    """:class:`_TrainScores` with a loop count per graph, graphs longest loop first (gnnmp_explorer_train_batch_forward /
+    _backward): one forward and one backward whatever the loop values are."""
+
+    @staticmethod
+    def forward(ctx, model, batch, loops, node_counts, edge_counts, *params):
+        dev = batch.v.device
+        h = model._native(dev)
+        cb = model._cbatch(batch)
+        host = tuple(_lib.i32_array(x) for x in (loops, node_counts, edge_counts))
+        need = ctypes.c_size_t()
+        _lib.check(_lib.lib().gnnmp_explorer_train_batch_workspace_bytes(h, ctypes.byref(cb), *host, ctypes.byref(need)),
+                   'gnnmp_explorer_train_batch_workspace_bytes')
+        ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
+        scores = torch.empty(batch.total_edges, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            st = torch.cuda.current_stream().cuda_stream
+            _lib.check(_lib.lib().gnnmp_explorer_train_batch_forward(h, ctypes.byref(cb), *host, 1 if model.use_obstacles else 0,
+                                                                     scores.data_ptr(), ws.data_ptr(), ws.numel(), st),
+                       'gnnmp_explorer_train_batch_forward')
+        ctx.model, ctx.batch, ctx.host, ctx.ws, ctx.handle = model, batch, host, ws, h
+        return scores
+
+    @staticmethod
+    def backward(ctx, d_scores):
+        model, batch, dev = ctx.model, ctx.batch, ctx.batch.v.device
+        cb = model._cbatch(batch)
+        n = int(_lib.lib().gnnmp_explorer_grad_floats(ctx.handle))
+        grad = torch.empty(n, dtype=torch.float32, device=dev)
+        d_scores = d_scores.contiguous().float()
+        with torch.cuda.device(dev):
+            st = torch.cuda.current_stream().cuda_stream
+            _lib.check(_lib.lib().gnnmp_explorer_train_batch_backward(ctx.handle, ctypes.byref(cb), *ctx.host, d_scores.data_ptr(),
+                                                                      grad.data_ptr(), ctx.ws.data_ptr(), ctx.ws.numel(), st),
+                       'gnnmp_explorer_train_batch_backward')
+        out, off = [], 0
+        for (name, numel), t in zip(model._manifest, model._live_weights()):
+            g = grad[off:off + numel].view_as(t).to(t.device) if name.split('.')[0] in TRAINABLE else None
+            out.append(g)
+            off += numel
+        return (None, None, None, None, None) + tuple(out)
 
 
 # top-level modules that receive a gradient from the policy loss (everything else forward() reads is behind a detach)
@@ -453,6 +497,77 @@ class EncoderProcessDecoder(nn.Module):
             raise RuntimeError('gnnmp runs on the GPU only (got %s tensors); there is no CPU fallback' % batch.v.device)
         self._native(batch.v.device)                      # builds the manifest / packed + raw weights on the device
         return _TrainScores.apply(self, batch, loop, *self._live_weights())
+
+    def train_scores_batch(self, batch, loops, node_counts=None, edge_counts=None):
+        """:meth:`train_scores` with a loop count per graph (train_explorer.py:148 draws one per sample): graph g's scores are
+        ``model(..., loop=loops[g])``'s, in ONE forward and ONE backward whose launch count depends on ``max(loops)`` only.
+        ``loops``: host sequence [G] in the batch's graph order.  The graphs are sorted longest loop first (stable) and
+        gathered with host-known offsets, so that the graphs of an iteration are a prefix of every row range (gnnmp.h:
+        gnnmp_explorer_train_batch_*); the scores come back in the batch's own edge order with autograd flowing through.
+        ``node_counts`` / ``edge_counts``: host sequences [G] of the per-graph sizes; without them the prefix arrays are read
+        back once.  A batch needs its prefix arrays (node_ptr / edge_ptr / obs_ptr).  fp32 only."""
+        if self.mlp_dtype != 'fp32':
+            raise RuntimeError('training runs in fp32 (mlp_dtype = %r)' % self.mlp_dtype)
+        if batch.v.device.type != 'cuda':
+            raise RuntimeError('gnnmp runs on the GPU only (got %s tensors); there is no CPU fallback' % batch.v.device)
+        loops = [int(x) for x in loops]
+        G = batch.n_graphs
+        if len(loops) != G:
+            raise ValueError('loops has %d entries for a batch of %d graphs' % (len(loops), G))
+        if min(loops) < 1:
+            raise ValueError('every loop count must be >= 1: the reference binds `decode` only inside the loop (model.py:139-145)')
+        if max(loops) > _lib.TRAIN_BATCH_MAX_LOOP:
+            raise ValueError('loop counts above %d are not supported by the batched training path' % _lib.TRAIN_BATCH_MAX_LOOP)
+        if batch.node_ptr is None or batch.edge_ptr is None or batch.obs_ptr is None:
+            raise ValueError('train_scores_batch needs a batch with node_ptr / edge_ptr / obs_ptr')
+        if node_counts is None or edge_counts is None:
+            nptr, eptr = torch.stack((batch.node_ptr, batch.edge_ptr)).tolist()         # the one read-back
+            node_counts = [nptr[i + 1] - nptr[i] for i in range(G)]
+            edge_counts = [eptr[i + 1] - eptr[i] for i in range(G)]
+        node_counts, edge_counts = [int(x) for x in node_counts], [int(x) for x in edge_counts]
+        if len(node_counts) != G or len(edge_counts) != G:
+            raise ValueError('node_counts / edge_counts must have one entry per graph')
+        self._native(batch.v.device)
+        order = sorted(range(G), key=lambda g: -loops[g])                               # stable: ties keep the caller's order
+        if order == list(range(G)):
+            return _TrainScoresBatch.apply(self, batch, loops, node_counts, edge_counts, *self._live_weights())
+        sb, inv = self._sorted_batch(batch, order, node_counts, edge_counts)
+        scores = _TrainScoresBatch.apply(self, sb, [loops[g] for g in order], [node_counts[g] for g in order],
+                                         [edge_counts[g] for g in order], *self._live_weights())
+        return scores[inv]
+
+    @staticmethod
+    def _sorted_batch(batch, order, node_counts, edge_counts):
+        """``batch`` with its graphs in ``order`` (host ints), and for every edge of ``batch`` its position in the new edge
+        list.  Nodes and edges are gathered with offsets the host knows; the obstacle rows, whose per-graph counts live on the
+        device only, with an index built there (their total does not change, so nothing is read back)."""
+        dev = batch.v.device
+        G = len(order)
+
+        def starts(counts):
+            p = np.zeros(G + 1, np.int64)
+            p[1:] = np.cumsum(counts)
+            return p
+
+        def gather(counts):
+            p = starts(counts)
+            return np.concatenate([np.arange(p[g], p[g + 1]) for g in order] + [np.zeros(0, np.int64)])
+
+        nodes, edges = gather(node_counts), gather(edge_counts)
+        inv = np.empty(edges.shape[0], np.int64)
+        inv[edges] = np.arange(edges.shape[0])
+        nodes_d, edges_d, inv_d = (torch.from_numpy(x).to(dev) for x in (nodes, edges, inv))
+        perm = torch.tensor(order, dtype=torch.int64).to(dev)
+        i32 = lambda counts: torch.from_numpy(starts([counts[g] for g in order]).astype(np.int32)).to(dev)     # noqa: E731
+        optr = batch.obs_ptr.long()
+        ocnt = (optr[1:] - optr[:-1])[perm]
+        new_optr = torch.cat((torch.zeros(1, dtype=torch.int64, device=dev), torch.cumsum(ocnt, 0)))
+        n_obs = batch.total_obstacles
+        og = torch.repeat_interleave(torch.arange(G, device=dev), ocnt, output_size=n_obs)
+        obs_rows = optr[:-1][perm][og] + (torch.arange(n_obs, device=dev) - new_optr[og])
+        sb = GraphBatch(batch.v[nodes_d], batch.goal[perm], batch.obstacles[obs_rows], batch.edge_index[:, edges_d],
+                        i32(node_counts), i32(edge_counts), new_optr.to(torch.int32), batch.max_obstacles, dense_floats=batch.dense_floats)
+        return sb, inv_d
 
     def forward_train(self, goal, loop, v, obstacles, free=None, collided=None, edge_index=None, k=10, **kwargs):
         """The reference call with gradients (train_explorer.py:156-160): dense ``policy_output[N, N]``; the scatter

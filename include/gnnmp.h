@@ -220,6 +220,43 @@ int gnnmp_explorer_train_forward(const gnnmp_explorer* h, const gnnmp_batch* bat
 int gnnmp_explorer_train_backward(const gnnmp_explorer* h, const gnnmp_batch* batch, int loop, const float* d_edge_scores,
                                   float* grad, void* workspace, size_t workspace_bytes, void* hip_stream);
 
+/* The same with a loop count PER GRAPH (train_explorer.py:148 draws one per sample): graph g's scores are the reference's
+ * model(..., loop = loops_host[g]) -- its hidden state after loops_host[g] iterations goes through decoder and policy
+ * (model.py:139-146) -- and after that the graph takes part in nothing: no message, no aggregation, no weight gradient.
+ * loops_host [G] is HOST memory (it decides how many launches are made): every entry >= 1 and at most
+ * GNNMP_TRAIN_BATCH_MAX_LOOP, and the graphs must come longest loop first (loops_host non-increasing; the Python wrapper
+ * sorts and restores the caller's order).  The graphs still running in iteration `it` are then a prefix of the batch and,
+ * because every graph's rows start at a multiple of 256 in the padded node space and in the padded CSR edge space, a
+ * prefix of both: iteration `it`'s launches cover only those rows, and the number of launches depends on loops_host[0]
+ * alone, never on G or on how many distinct loop values occur.  node_counts_host / edge_counts_host [G]: host copies of
+ * the per-graph node and edge counts (batch->node_ptr / edge_ptr are device memory and nothing is read back); they must
+ * sum to batch->total_nodes / total_edges.  train_batch_backward returns the SUM over graphs of d loss / d parameters in
+ * manifest order, frozen tensors zero, bit-identical for identical inputs (no float atomics, fixed summation orders).
+ * With all loops equal the result is the uniform call's, bit for bit.  The workspace is the uniform call's at
+ * loop = loops_host[0]; the same workspace, loops and counts go to forward and backward.
+ * GNNMP_ERR_NULL for NULL arguments (the prefix arrays included), GNNMP_ERR_ARG for a loop below 1 or above the limit, an
+ * ascending pair, a negative count or counts that do not sum to the batch totals, GNNMP_ERR_DIMS for a non-fp32 handle,
+ * GNNMP_ERR_WORKSPACE as elsewhere. */
+#define GNNMP_TRAIN_BATCH_MAX_LOOP 64
+int gnnmp_explorer_train_batch_workspace_bytes(const gnnmp_explorer* h, const gnnmp_batch* shape, const int32_t* loops_host,
+                                               const int32_t* node_counts_host, const int32_t* edge_counts_host, size_t* bytes);
+int gnnmp_explorer_train_batch_forward(const gnnmp_explorer* h, const gnnmp_batch* batch, const int32_t* loops_host,
+                                       const int32_t* node_counts_host, const int32_t* edge_counts_host, int use_obstacles,
+                                       float* edge_scores, void* workspace, size_t workspace_bytes, void* hip_stream);
+int gnnmp_explorer_train_batch_backward(const gnnmp_explorer* h, const gnnmp_batch* batch, const int32_t* loops_host,
+                                        const int32_t* node_counts_host, const int32_t* edge_counts_host,
+                                        const float* d_edge_scores, float* grad, void* workspace, size_t workspace_bytes,
+                                        void* hip_stream);
+/* Host only (no device needed): the launch sizes of the two calls above.  For it in [0, loops_host[0]): active[it] = the
+ * number of graphs with loops_host[g] > it (a prefix of the batch), node_rows[it] / edge_rows[it] = the sum over those
+ * graphs of the node / edge count rounded up to 256 -- the prep stage's rule for node_ptr_pad and the CSR ranges.
+ * *n_iters = loops_host[0]; the three arrays hold `cap` entries each and may be NULL together with cap = 0 to ask for
+ * n_iters alone.  Same argument errors as above, and GNNMP_ERR_ARG when 0 < cap < loops_host[0].  The forward and the
+ * backward size their launches with this very function. */
+int gnnmp_explorer_train_batch_plan(int32_t n_graphs, const int32_t* loops_host, const int32_t* node_counts_host,
+                                    const int32_t* edge_counts_host, int32_t cap, int32_t* active, int32_t* node_rows,
+                                    int32_t* edge_rows, int32_t* n_iters);
+
 /* ------------------------------------------------------------------------------------------
  * Smoother   (ModelSmoother, model_smoother.py:46-142)
  * ---------------------------------------------------------------------------------------- */

@@ -5,7 +5,12 @@
 replay) and the loss -- next to the plain-Python restatement of the same supervision (tests/episodes_host.py: labels,
 dijkstra, explore, policy_data) on the host, with hostenv.limit_host_threads(): timed on the first 8 problems of each batch and
 scaled to B (an extrapolation, labelled as such).  The stages are disjoint: fwd+bwd starts its backward from dloss/dscores,
-the loss column is the loss's own forward and backward."""
+the loss column is the loss's own forward and backward.
+
+Second table: the same forward + backward as ONE train_scores_batch over all problems (episodes.forward_scores_batched) next to
+the grouped form, in the same process and on the same draws: three timed repetitions of each leg (each the mean of 10 steps
+after a warm-up step that is not timed), the kernel launches of the training path per step and the workspace bytes.
+`--write FILE` also writes that table to FILE (profiles/explorer_train_batch.txt)."""
 import os
 import sys
 import time
@@ -45,7 +50,36 @@ def timed(fn, reps=REPS):
     return a.elapsed_time(b) / reps
 
 
+def train_launches(loop, batched):
+    """Kernel launches of one training forward + backward at `loop` iterations, counted from csrc/api.cpp
+    (gnnmp_explorer_train_forward / _backward and their _batch_ forms): forward 18 + 8 per iteration, backward 34 + 25 per
+    iteration (a weight gradient is two launches); the batched backward has one more (the decoder gradient waits in a buffer
+    of its own).  Not counted: the frozen attention front stage (once per call in both forms), memsets, torch's own kernels."""
+    return 18 + 8 * loop + 34 + 25 * loop + (1 if batched else 0)
+
+
+def workspace_bytes(m, g, goal, loops, batched):
+    """Bytes of training workspace alive during one step: the batched call's one buffer, or the sum over the grouped calls
+    (they run one after the other, but autograd keeps every group's buffer until its backward)."""
+    import ctypes
+    from gnnmp import _lib
+    L = _lib.lib()
+    need = ctypes.c_size_t()
+    if batched:
+        b = g.batch(goal)
+        _lib.check(L.gnnmp_explorer_train_workspace_bytes(m._native(DEV), ctypes.byref(m._cbatch(b)), max(loops), ctypes.byref(need)), 'ws')
+        return need.value
+    total = 0
+    for lp in sorted(set(loops)):
+        b, _ = g.subset([i for i, x in enumerate(loops) if x == lp], goal)
+        _lib.check(L.gnnmp_explorer_train_workspace_bytes(m._native(DEV), ctypes.byref(m._cbatch(b)), lp, ctypes.byref(need)), 'ws')
+        total += need.value
+    return total
+
+
 def main():
+    out_path = sys.argv[sys.argv.index('--write') + 1] if '--write' in sys.argv else None
+    legs = []
     hostenv.limit_host_threads()
     m = gnnmp.EncoderProcessDecoder(2, 2, 32, 2)
     m.load_state_dict(load_weights('weights_maze'))
@@ -82,6 +116,18 @@ def main():
             fwd().backward(d_scores)
         t_fb = timed(fb)
 
+        def fb_batched():
+            ep.forward_scores_batched(m, g, paths['goal'], loops).backward(d_scores)
+        # the two legs in turn, three repetitions each (timed() runs one untimed warm-up step first)
+        reps_g, reps_b = [t_fb], []
+        for r in range(3):
+            reps_b.append(timed(fb_batched))
+            if r < 2:
+                reps_g.append(timed(fb))
+        legs.append(dict(B=B, edges=g.total_edges, loops=sorted(set(loops)), grouped=reps_g, batched=reps_b,
+                         launches_g=sum(train_launches(lp, False) for lp in set(loops)), launches_b=train_launches(max(loops), True),
+                         ws_g=workspace_bytes(m, g, paths['goal'], loops, False), ws_b=workspace_bytes(m, g, paths['goal'], loops, True)))
+
         def episodes():
             st, ss = ep.explore_steps(g, scores, start, paths['goal'], paths['n_valid'])
             ep.policy_frontier(g, scores, paths, start, paths['goal'], s, ss)
@@ -108,6 +154,27 @@ def main():
         print('%5d %8d | %8.3f %8.3f %10.3f %9.3f %9.3f | %9.3f | %10.0f  (status ok/single/empty: %d/%d/%d, max step %d)'
               % (B, g.total_edges, t_lab, t_path, t_fb, t_ep, t_loss, total, host, st_h[0], st_h[1], st_h[2],
                  int(step.max())))
+    lines = ['explorer training forward + backward per optimizer step, grouped (one train_scores per distinct loop value) vs batched '
+             '(one train_scores_batch), same process, same draws (loop = 10, seed 1), synthetic maze2 problems of 100-400 nodes, fp32, one MI355X',
+             'ms per step: three repetitions per leg, each the mean of %d steps after an untimed warm-up step' % REPS,
+             '%5s %8s %-22s | %-26s | %-26s | %7s | %9s %9s | %12s %12s' % ('B', 'edges', 'loop values', 'grouped ms', 'batched ms', 'ratio',
+                                                                          'launch g', 'launch b', 'ws bytes g', 'ws bytes b')]
+    for x in legs:
+        lines.append('%5d %8d %-22s | %-26s | %-26s | %7.2f | %9d %9d | %12d %12d'
+                     % (x['B'], x['edges'], ','.join(map(str, x['loops'])), ' '.join('%8.3f' % t for t in x['grouped']),
+                        ' '.join('%8.3f' % t for t in x['batched']), min(x['grouped']) / max(x['batched']), x['launches_g'],
+                        x['launches_b'], x['ws_g'], x['ws_b']))
+    last = legs[-1]
+    lines.append('ratio = fastest grouped / slowest batched repetition.  At %d problems the slowest batched repetition (%.3f ms) is %s the '
+                 'fastest grouped one (%.3f ms).' % (last['B'], max(last['batched']), 'below' if max(last['batched']) < min(last['grouped'])
+                                                     else 'NOT below', min(last['grouped'])))
+    lines.append('launches: kernel launches of the training path per step (train_launches() of tools/train_episodes_bench.py); '
+                 'ws bytes g: sum over the groups, all held until their backward')
+    print()
+    print('\n'.join(lines))
+    if out_path:
+        with open(out_path, 'w') as f:
+            f.write('\n'.join(lines) + '\n')
 
 
 if __name__ == '__main__':
