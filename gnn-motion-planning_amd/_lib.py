@@ -93,7 +93,10 @@ class TrainGeom(ctypes.Structure):
 TRAIN_OPS = ('LINEAR', 'LINEAR_DX', 'LINEAR_DW', 'RELU_BWD', 'FILL', 'NODE_IN', 'EDGE_IN', 'H0', 'H0_BWD', 'CONCAT', 'SPLIT', 'MSG_IN',
              'MSG_IN_BWD', 'POL_IN', 'POL_IN_BWD', 'SEGMENT_MAX', 'SEGMENT_MAX_BWD', 'SCORES_OUT', 'SCORES_IN', 'SM_NODES_IN', 'BN_FWD',
              'BN_BWD', 'SM_MSG_IN', 'SM_MSG_IN_BWD', 'SM_SCATTER_ADD', 'SM_SCATTER_ADD_BWD', 'ADD_ROWS', 'SM_PATH_UPDATE',
-             'SM_PATH_UPDATE_BWD', 'SM_COORDS_BWD', 'SCALE')
+             'SM_PATH_UPDATE_BWD', 'SM_COORDS_BWD', 'SCALE',
+             'SM_NODES_IN_SEG', 'BN_SEG_FWD', 'BN_SEG_BWD', 'BN_SEG_DGB', 'SM_MSG_IN_SEG', 'SM_MSG_IN_BWD_SEG', 'SM_SCATTER_ADD_SEG',
+             'SM_SCATTER_ADD_BWD_SEG', 'SM_ADD_PATH_SEG', 'SM_ADD_PATH_BWD_SEG', 'SM_PATH_UPDATE_SEG', 'SM_PATH_UPDATE_BWD_SEG',
+             'SM_COORDS_BWD_SEG', 'FINAL_CAT', 'SEED_DH', 'LINEAR_DW_ORDER')
 
 
 _lib = None
@@ -309,7 +312,7 @@ def train_op(op, dims, bufs, geom=None, scalar=0.0, stream=None):
 
 
 def train_op_path(op, R, K, O):
-    """'mfma' or 'plain': the kernel LINEAR / LINEAR_DX / LINEAR_DW dispatch to at these sizes."""
+    """'mfma' or 'plain': the kernel LINEAR / LINEAR_DX / LINEAR_DW / LINEAR_DW_ORDER dispatch to at these sizes."""
     d = (ctypes.c_int64 * 3)(R, K, O)
     rc = lib().gnnmp_train_op_path(TRAIN_OPS.index(op), d, 3)
     if rc < 0:

@@ -2542,6 +2542,8 @@ struct TrainOpSpec {
                             // must be >= 1 -- the launchers do not guard an empty grid (or N = 0 of BatchNorm)
 };
 
+constexpr unsigned kSegZero = 0x1eu;       // A, P, Nn, Ec of a segmented operator
+
 const TrainOpSpec kTrainOps[GNNMP_TOP_COUNT] = {
     /* LINEAR             */ {4, 4, 1u << 2, false, -1, 1u << 3, 1u},
     /* LINEAR_DX          */ {4, 3, 0, false, -1, 1u << 3, 1u},
@@ -2574,17 +2576,38 @@ const TrainOpSpec kTrainOps[GNNMP_TOP_COUNT] = {
     /* SM_PATH_UPDATE_BWD */ {2, 3, 0, false, -1, 0, 0},
     /* SM_COORDS_BWD      */ {2, 2, 0, false, -1, 0, 0},
     /* SCALE              */ {1, 2, 0, false, -1, 0, 1u},
+    // segmented operators: dims [B, A, P, Nn, Ec, D or C, ...], A / P / Nn / Ec may be 0 (every launcher guards an empty range)
+    /* SM_NODES_IN_SEG    */ {6, 8, 0, false, -1, 0, kSegZero},
+    /* BN_SEG_FWD         */ {8, 10, 1u << 9, false, -1, 1u << 6, kSegZero | 1u << 7},
+    /* BN_SEG_BWD         */ {6, 10, 0, false, -1, 0, kSegZero},
+    /* BN_SEG_DGB         */ {3, 3, 0, false, -1, 0, 0},
+    /* SM_MSG_IN_SEG      */ {6, 9, 0, false, -1, 0, kSegZero},
+    /* SM_MSG_IN_BWD_SEG  */ {6, 9, 0, false, -1, 0, kSegZero},
+    /* SM_SCATTER_ADD_SEG */ {6, 8, 0, false, -1, 0, kSegZero},
+    /* SM_SCATTER_ADD_BWD_SEG */ {6, 8, 0, false, -1, 0, kSegZero},
+    /* SM_ADD_PATH_SEG    */ {6, 7, 0, false, -1, 0, kSegZero},
+    /* SM_ADD_PATH_BWD_SEG */ {6, 6, 0, false, -1, 0, kSegZero},
+    /* SM_PATH_UPDATE_SEG */ {6, 7, 0, false, -1, 0, kSegZero},
+    /* SM_PATH_UPDATE_BWD_SEG */ {6, 7, 0, false, -1, 0, kSegZero},
+    /* SM_COORDS_BWD_SEG  */ {6, 6, 0, false, -1, 0, kSegZero},
+    /* FINAL_CAT          */ {3, 3, 0, false, -1, 0, 0},         // + n_it entries of rows[] (checked below)
+    /* SEED_DH            */ {3, 3, 0, false, -1, 0, 1u << 1},
+    /* LINEAR_DW_ORDER    */ {4, 5, 1u << 3, false, -1, 0, 1u | 1u << 3},
 };
 
-int train_dims_ok(const TrainOpSpec& s, const int64_t* dims, int n_dims) {
-    if (n_dims != s.n_dims || (n_dims > 0 && !dims)) return GNNMP_ERR_ARG;
+// want: the number of dims of this call (the operator's own, except for FINAL_CAT's row table)
+int train_dims_ok(const TrainOpSpec& s, const int64_t* dims, int n_dims, int want) {
+    if (n_dims != want || (n_dims > 0 && !dims)) return GNNMP_ERR_ARG;
     for (int i = 0; i < n_dims; ++i) {
+        const unsigned flag = i < 32 ? (s.flags >> i) & 1u : 0u, zero_ok = i < 32 ? (s.zero_ok >> i) & 1u : 0u;
         if (dims[i] < 0 || dims[i] > 0x7fffffff) return GNNMP_ERR_ARG;
-        if (((s.flags >> i) & 1) && dims[i] > 1) return GNNMP_ERR_ARG;
-        if (dims[i] == 0 && !(((s.flags | s.zero_ok) >> i) & 1)) return GNNMP_ERR_ARG;
+        if (flag && dims[i] > 1) return GNNMP_ERR_ARG;
+        if (dims[i] == 0 && !(flag | zero_ok)) return GNNMP_ERR_ARG;
     }
     return GNNMP_OK;
 }
+
+bool train_op_is_seg(int op) { return op >= GNNMP_TOP_SM_NODES_IN_SEG && op <= GNNMP_TOP_SM_COORDS_BWD_SEG && op != GNNMP_TOP_BN_SEG_DGB; }
 
 int train_geom_ok(const gnnmp_train_geom* g) {
     if (!g) return GNNMP_ERR_NULL;
@@ -2659,6 +2682,7 @@ extern "C" int64_t gnnmp_train_dw_scratch_floats(int64_t R, int64_t K, int64_t O
 }
 
 extern "C" int gnnmp_train_op_path(int op, const int64_t* dims, int n_dims) {
+    if (op == GNNMP_TOP_LINEAR_DW_ORDER) op = GNNMP_TOP_LINEAR_DW;           // the same launcher
     if (op != GNNMP_TOP_LINEAR && op != GNNMP_TOP_LINEAR_DX && op != GNNMP_TOP_LINEAR_DW) return GNNMP_ERR_ARG;
     if (n_dims < 3 || !dims) return GNNMP_ERR_ARG;
     for (int i = 0; i < 3; ++i)
@@ -2671,11 +2695,33 @@ extern "C" int gnnmp_train_op(int op, const int64_t* dims, int n_dims, void* con
                               const gnnmp_train_geom* geom, float scalar, void* hip_stream) {
     if (op < 0 || op >= GNNMP_TOP_COUNT) return GNNMP_ERR_ARG;
     const TrainOpSpec& s = kTrainOps[op];
-    int rc = train_dims_ok(s, dims, n_dims);
+    int want = s.n_dims;
+    if (op == GNNMP_TOP_FINAL_CAT) {                                // [D, it_stride, n_it, rows[0] .. rows[n_it - 1]]
+        if (n_dims < 3 || !dims || dims[2] < 1 || dims[2] > kTrainBatchMaxLoop) return GNNMP_ERR_ARG;
+        want = 3 + (int)dims[2];
+    }
+    int rc = train_dims_ok(s, dims, n_dims, want);
     if (rc != GNNMP_OK) return rc;
     if (n_bufs != s.n_bufs) return GNNMP_ERR_ARG;
     if (!bufs) return GNNMP_ERR_NULL;
     auto d = [&](int i) { return (int)dims[i]; };
+    if (train_op_is_seg(op) && d(1) > d(0)) return GNNMP_ERR_ARG;                              // A inside [0, B]
+    if (op == GNNMP_TOP_LINEAR_DW_ORDER && d(3) > 0 && d(3) < d(0)) return GNNMP_ERR_ARG;      // R_order: 0, or >= R
+    TrainLoopRows lr{};
+    if (op == GNNMP_TOP_FINAL_CAT) {
+        lr.n_it = d(2);
+        for (int i = 0; i < lr.n_it; ++i) {
+            lr.rows[i] = d(3 + i);
+            if (i > 0 && lr.rows[i] > lr.rows[i - 1]) return GNNMP_ERR_ARG;                    // longest loop first
+        }
+        for (int i = 0; i < lr.n_it; ++i)
+            if (lr.rows[i] % 256) return GNNMP_ERR_DIMS;
+        if ((d(0) != 32 && d(0) != 64) || d(1) % 4) return GNNMP_ERR_DIMS;
+    }
+    if (op == GNNMP_TOP_SEED_DH) {
+        if (d(1) > d(0)) return GNNMP_ERR_ARG;
+        if (d(0) % 256 || d(1) % 256 || (d(2) != 32 && d(2) != 64)) return GNNMP_ERR_DIMS;
+    }
     unsigned optional = s.optional;
     if (op == GNNMP_TOP_CONCAT) {
         if (d(2) < 1 || d(2) > 4) return GNNMP_ERR_ARG;
@@ -2685,6 +2731,9 @@ extern "C" int gnnmp_train_op(int op, const int64_t* dims, int n_dims, void* con
     if (op == GNNMP_TOP_SM_NODES_IN) optional = (d(1) == 0 ? 2u : 0u) | (d(2) == 0 ? 4u : 0u);      // no rows: never read
     for (int i = 0; i < n_bufs; ++i)
         if (!bufs[i] && !((optional >> i) & 1)) return GNNMP_ERR_NULL;
+    if (op == GNNMP_TOP_FINAL_CAT || op == GNNMP_TOP_SEED_DH)      // rows travel as float4
+        for (int i = 0; i < n_bufs; ++i)
+            if (reinterpret_cast<uintptr_t>(bufs[i]) & 15) return GNNMP_ERR_DIMS;
     TrainGeom q{};
     if (s.geom) {
         rc = train_geom_ok(geom);
@@ -2695,6 +2744,11 @@ extern "C" int gnnmp_train_op(int op, const int64_t* dims, int n_dims, void* con
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
     auto F = [&](int i) { return static_cast<float*>(bufs[i]); };
     auto I = [&](int i) { return static_cast<int*>(bufs[i]); };
+    SmSeg g{};
+    if (train_op_is_seg(op)) {
+        g.path_ptr = I(0); g.free_ptr = I(1); g.coll_ptr = I(2); g.edge_ptr = I(3);
+        g.B = d(0); g.A = d(1); g.P = d(2); g.Nn = d(3); g.Ec = d(4);
+    }
     switch (op) {
         case GNNMP_TOP_LINEAR: HIP_TRY(t_linear(d(0), d(1), d(2), F(0), F(1), F(2), F(3), d(3) != 0, st)); break;
         case GNNMP_TOP_LINEAR_DX: HIP_TRY(t_linear_dx(d(0), d(1), d(2), F(0), F(1), F(2), d(3) != 0, st)); break;
@@ -2727,6 +2781,24 @@ extern "C" int gnnmp_train_op(int op, const int64_t* dims, int n_dims, void* con
         case GNNMP_TOP_SM_PATH_UPDATE_BWD: HIP_TRY(t_sm_path_update_bwd(d(0), d(1), F(0), F(1), F(2), st)); break;
         case GNNMP_TOP_SM_COORDS_BWD: HIP_TRY(t_sm_coords_bwd(d(0), d(1), F(0), F(1), st)); break;
         case GNNMP_TOP_SCALE: HIP_TRY(t_scale(d(0), scalar, F(0), F(1), st)); break;
+        case GNNMP_TOP_SM_NODES_IN_SEG: HIP_TRY(t_sm_nodes_in_seg(g, d(5), scalar, F(4), F(5), F(6), F(7), st)); break;
+        case GNNMP_TOP_BN_SEG_FWD:
+            HIP_TRY(t_bn_seg_fwd(g, d(5), F(4), F(5), F(6), F(7), F(8), F(9), (size_t)d(7), d(6) != 0, st));
+            break;
+        case GNNMP_TOP_BN_SEG_BWD: HIP_TRY(t_bn_seg_bwd(g, d(5), F(4), F(5), F(6), F(7), F(8), F(9), st)); break;
+        case GNNMP_TOP_BN_SEG_DGB: HIP_TRY(t_bn_seg_dgb(d(0), d(1), d(2), F(0), F(1), F(2), st)); break;
+        case GNNMP_TOP_SM_MSG_IN_SEG: HIP_TRY(t_sm_msg_in_seg(g, I(4), d(5), I(5), I(6), F(7), F(8), st)); break;
+        case GNNMP_TOP_SM_MSG_IN_BWD_SEG: HIP_TRY(t_sm_msg_in_bwd_seg(g, I(4), d(5), I(5), I(6), F(7), F(8), st)); break;
+        case GNNMP_TOP_SM_SCATTER_ADD_SEG: HIP_TRY(t_sm_scatter_add_seg(g, I(4), d(5), I(5), F(6), F(7), st)); break;
+        case GNNMP_TOP_SM_SCATTER_ADD_BWD_SEG: HIP_TRY(t_sm_scatter_add_bwd_seg(g, I(4), d(5), I(5), F(6), F(7), st)); break;
+        case GNNMP_TOP_SM_ADD_PATH_SEG: HIP_TRY(t_sm_add_path_seg(g, d(5), F(4), F(5), F(6), st)); break;
+        case GNNMP_TOP_SM_ADD_PATH_BWD_SEG: HIP_TRY(t_sm_add_path_bwd_seg(g, d(5), F(4), F(5), st)); break;
+        case GNNMP_TOP_SM_PATH_UPDATE_SEG: HIP_TRY(t_sm_path_update_seg(g, d(5), F(4), F(5), F(6), st)); break;
+        case GNNMP_TOP_SM_PATH_UPDATE_BWD_SEG: HIP_TRY(t_sm_path_update_bwd_seg(g, d(5), F(4), F(5), F(6), st)); break;
+        case GNNMP_TOP_SM_COORDS_BWD_SEG: HIP_TRY(t_sm_coords_bwd_seg(g, d(5), F(4), F(5), st)); break;
+        case GNNMP_TOP_FINAL_CAT: HIP_TRY(t_final_cat(lr, d(0), F(0), F(1), (size_t)d(1), F(2), st)); break;
+        case GNNMP_TOP_SEED_DH: HIP_TRY(t_seed_dh(d(0), d(1), d(2), F(0), F(1), F(2), st)); break;
+        case GNNMP_TOP_LINEAR_DW_ORDER: HIP_TRY(t_linear_dw(d(0), d(1), d(2), F(0), F(1), F(2), F(3), F(4), st, d(3))); break;
         default: return GNNMP_ERR_ARG;
     }
     return GNNMP_OK;

@@ -613,12 +613,49 @@ int gnnmp_stick_oracle_smooth(const gnnmp_oracle_smooth_batch* batch, double* ou
  *   SM_COORDS_BWD    [P, C]                      dXin [., C+3], d_prev [P,C] (+=)
  *   SCALE            [n]                         x, y
  *
+ * The batched smoother path (the `_seg` launchers).  Every segmented operator takes the fields of the launchers' SmSeg as its
+ * first dims -- S = B, A, P, Nn, Ec: problems, active problems (the prefix [0, A)), total path rows, total node rows, padded
+ * edge slots -- and the four prefix arrays as its first buffers -- ptr = path_ptr, free_ptr, coll_ptr, edge_ptr, [B+1] int32
+ * each, on the device.  The remaining buffers follow the launcher's own argument order.  Problem b's node rows start at
+ * path_ptr[b] + free_ptr[b] + coll_ptr[b], its edge slots at round32(edge_ptr[b] + 10 path_ptr[b]) + 32 b; n_edges is [B] int32,
+ * e_src / e_dst [Ec] int32 hold problem-local node ids.  `scalar` is read by SM_NODES_IN_SEG (scale).
+ *
+ *   SM_NODES_IN_SEG  [S, C]                      ptr, cur [P,C], free_pts, collided, out [Nn, C+3]    rows of b >= A left alone
+ *   BN_SEG_FWD       [S, D, relu, out_stride]    ptr, x [Nn,D], gamma, beta, y [Nn,D], stats [B,3,D], out_stats?
+ *                                                out_stats + b out_stride receives [mean; unbiased variance]; b >= A left alone
+ *   BN_SEG_BWD       [S, D]                      ptr, x, dy, gamma, stats, dx [Nn,D], part [B,2,D]    dx rows, part of b >= A = 0
+ *   BN_SEG_DGB       [L, B, D]                   part [L,B,2,D], dgamma [D] (+=), dbeta [D] (+=)      iterations last to first
+ *   SM_MSG_IN_SEG    [S, D]                      ptr, n_edges, e_src, e_dst, X [Nn,D], out [Ec,3D]    0 in every slot not in use
+ *   SM_MSG_IN_BWD_SEG [S, D]                     ptr, n_edges, e_src, e_dst, dZ [Ec,3D], dX [Nn,D] (+=)   rows of b >= A left alone
+ *   SM_SCATTER_ADD_SEG [S, D]                    ptr, n_edges, e_dst, M [Ec,D], S [P,D] (assigned)    0 for b >= A
+ *   SM_SCATTER_ADD_BWD_SEG [S, D]                ptr, n_edges, e_dst, dS [P,D], dM [Ec,D]             0 in every slot not in use
+ *   SM_ADD_PATH_SEG  [S, D]                      ptr, X [Nn,D], Y [P,D], out [P,D]                    rows of b >= A left alone
+ *   SM_ADD_PATH_BWD_SEG [S, D]                   ptr, dH [P,D], dX [Nn,D]                             0 off the active path rows
+ *   SM_PATH_UPDATE_SEG [S, C]                    ptr, prev, proposal, next [P,C]                      b >= A: next = prev
+ *   SM_PATH_UPDATE_BWD_SEG [S, C]                ptr, d_next, d_proposal, d_prev [P,C]                b >= A: d_prev = d_next
+ *   SM_COORDS_BWD_SEG [S, C]                     ptr, dXin [Nn, C+3], d_prev [P,C] (+=)               rows of b >= A left alone
+ *
+ * The explorer's path with a loop count per graph:
+ *
+ *   FINAL_CAT        [D, it_stride, n_it, rows[0] .. rows[n_it-1]]   NC [rows[0], D], H_it0 (iteration i's H [rows[0], D] at
+ *                                                i it_stride floats), out [rows[0], 2D]      out[n] = [NC[n], H of n's last iteration [n]]
+ *   SEED_DH          [rows_it, rows_next, D]     d_dec [rows_it, D], dXin [rows_it, 4D], dH [rows_it, D]
+ *   LINEAR_DW_ORDER  [R, K, O, R_order]          as LINEAR_DW                               the sums of LINEAR_DW over R_order rows whose
+ *                                                rows >= R have dY = 0; R_order = 0 or R: LINEAR_DW itself
+ *
  * Everything is validated before any launch: unknown op, n_dims / n_bufs not the operator's, a negative size (or one
  * beyond int32), a size of 0 (the launchers do not guard an empty grid; only R of the three LINEAR operators, n of FILL and
  * SCALE, and F / Co of SM_NODES_IN may be 0), a flag that is not 0 / 1, parts outside 1 .. 4 or part outside [0, parts),
  * a geometry with n_graphs, config_size, n_pad or e_pad below 1 -> GNNMP_ERR_ARG; a required buffer, or a geometry or one
  * of its arrays, NULL -> GNNMP_ERR_NULL; D of a geometry operator not an embed size of the explorer (32, 64), or a
- * geometry whose n_pad / e_pad is not a multiple of 32 -> GNNMP_ERR_DIMS. */
+ * geometry whose n_pad / e_pad is not a multiple of 32 -> GNNMP_ERR_DIMS.
+ * The operators of the two batched paths add: B < 1 or A outside [0, B] (A, P, Nn, Ec and out_stride may be 0), n_it outside
+ * 1 .. GNNMP_TRAIN_BATCH_MAX_LOOP (n_dims must be 3 + n_it), an ascending pair in rows[] or rows_next > rows_it (rows_next may be
+ * 0), R_order inside (0, R) -> GNNMP_ERR_ARG; D of FINAL_CAT / SEED_DH not 32 or 64, an entry of rows[], rows_it or rows_next
+ * that is not a multiple of 256, an it_stride that is not a multiple of 4, or a buffer of FINAL_CAT / SEED_DH that is not
+ * 16-byte aligned (rows are moved in 16-byte pieces) -> GNNMP_ERR_DIMS.
+ * New operators are appended in front of GNNMP_TOP_COUNT and existing ones keep their numbers, so adding one is a compatible
+ * change: gnnmp_abi_version stays. */
 enum {
     GNNMP_TOP_LINEAR = 0, GNNMP_TOP_LINEAR_DX, GNNMP_TOP_LINEAR_DW, GNNMP_TOP_RELU_BWD, GNNMP_TOP_FILL,
     GNNMP_TOP_NODE_IN, GNNMP_TOP_EDGE_IN, GNNMP_TOP_H0, GNNMP_TOP_H0_BWD, GNNMP_TOP_CONCAT, GNNMP_TOP_SPLIT,
@@ -626,7 +663,11 @@ enum {
     GNNMP_TOP_SEGMENT_MAX_BWD, GNNMP_TOP_SCORES_OUT, GNNMP_TOP_SCORES_IN, GNNMP_TOP_SM_NODES_IN, GNNMP_TOP_BN_FWD,
     GNNMP_TOP_BN_BWD, GNNMP_TOP_SM_MSG_IN, GNNMP_TOP_SM_MSG_IN_BWD, GNNMP_TOP_SM_SCATTER_ADD,
     GNNMP_TOP_SM_SCATTER_ADD_BWD, GNNMP_TOP_ADD_ROWS, GNNMP_TOP_SM_PATH_UPDATE, GNNMP_TOP_SM_PATH_UPDATE_BWD,
-    GNNMP_TOP_SM_COORDS_BWD, GNNMP_TOP_SCALE, GNNMP_TOP_COUNT
+    GNNMP_TOP_SM_COORDS_BWD, GNNMP_TOP_SCALE,
+    GNNMP_TOP_SM_NODES_IN_SEG, GNNMP_TOP_BN_SEG_FWD, GNNMP_TOP_BN_SEG_BWD, GNNMP_TOP_BN_SEG_DGB, GNNMP_TOP_SM_MSG_IN_SEG,
+    GNNMP_TOP_SM_MSG_IN_BWD_SEG, GNNMP_TOP_SM_SCATTER_ADD_SEG, GNNMP_TOP_SM_SCATTER_ADD_BWD_SEG, GNNMP_TOP_SM_ADD_PATH_SEG,
+    GNNMP_TOP_SM_ADD_PATH_BWD_SEG, GNNMP_TOP_SM_PATH_UPDATE_SEG, GNNMP_TOP_SM_PATH_UPDATE_BWD_SEG, GNNMP_TOP_SM_COORDS_BWD_SEG,
+    GNNMP_TOP_FINAL_CAT, GNNMP_TOP_SEED_DH, GNNMP_TOP_LINEAR_DW_ORDER, GNNMP_TOP_COUNT
 };
 
 /* The padded index space of a batch as the training path sees it (TrainGeom of kernels.hpp): device pointers into the
@@ -651,7 +692,7 @@ int gnnmp_train_op(int op, const int64_t* dims, int n_dims, void* const* bufs, i
                    const gnnmp_train_geom* geom_or_null, float scalar, void* hip_stream);
 /* Floats of LINEAR_DW's scratch (negative status on negative sizes). */
 int64_t gnnmp_train_dw_scratch_floats(int64_t R, int64_t K, int64_t O);
-/* Which kernel LINEAR / LINEAR_DX / LINEAR_DW dispatch to at dims [R, K, O, ...]: 1 = fp32 MFMA, 0 = plain; asked of the
+/* Which kernel LINEAR / LINEAR_DX / LINEAR_DW / LINEAR_DW_ORDER dispatch to at dims [R, K, O, ...]: 1 = fp32 MFMA, 0 = plain; asked of the
  * launchers' own predicate.  GNNMP_ERR_ARG for another op or bad dims. */
 int gnnmp_train_op_path(int op, const int64_t* dims, int n_dims);
 

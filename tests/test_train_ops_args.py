@@ -1,8 +1,10 @@
 """The test hooks of the training operators (gnnmp_train_op and friends, include/gnnmp.h) validate everything before any
 launch, so all of this runs without a GPU -- and the CPU half of the BatchNorm bar of tests/test_train_ops_gpu.py: the
-reference pair (torch float32 batch norm against float64) itself stays inside 1e-5 * scale on the unit-scale inputs."""
+reference pair (torch float32 batch norm against float64) itself stays inside 1e-5 * scale on the unit-scale inputs.  The host
+references of the batched operators check themselves here too: with one problem, active, each is the one-problem reference."""
 import ctypes
 
+import numpy as np
 import pytest
 
 from gnnmp import _lib
@@ -22,12 +24,24 @@ GOOD = {
     'SM_MSG_IN': ([32, 9], 5, False), 'SM_MSG_IN_BWD': ([32, 9], 5, False), 'SM_SCATTER_ADD': ([32, 9], 4, False),
     'SM_SCATTER_ADD_BWD': ([32, 9], 4, False), 'ADD_ROWS': ([7], 3, False), 'SM_PATH_UPDATE': ([3, 2], 3, False),
     'SM_PATH_UPDATE_BWD': ([3, 2], 3, False), 'SM_COORDS_BWD': ([3, 2], 2, False), 'SCALE': ([7], 2, False),
+    # the batched paths: [B, A, P, Nn, Ec, D or C, ...] and the four prefix arrays in front of the launcher's buffers
+    'SM_NODES_IN_SEG': ([2, 1, 5, 9, 64, 7], 8, False), 'BN_SEG_FWD': ([2, 1, 5, 9, 64, 32, 1, 192], 10, False),
+    'BN_SEG_BWD': ([2, 1, 5, 9, 64, 32], 10, False), 'BN_SEG_DGB': ([3, 2, 32], 3, False),
+    'SM_MSG_IN_SEG': ([2, 1, 5, 9, 64, 32], 9, False), 'SM_MSG_IN_BWD_SEG': ([2, 1, 5, 9, 64, 32], 9, False),
+    'SM_SCATTER_ADD_SEG': ([2, 1, 5, 9, 64, 32], 8, False), 'SM_SCATTER_ADD_BWD_SEG': ([2, 1, 5, 9, 64, 32], 8, False),
+    'SM_ADD_PATH_SEG': ([2, 1, 5, 9, 64, 32], 7, False), 'SM_ADD_PATH_BWD_SEG': ([2, 1, 5, 9, 64, 32], 6, False),
+    'SM_PATH_UPDATE_SEG': ([2, 1, 5, 9, 64, 7], 7, False), 'SM_PATH_UPDATE_BWD_SEG': ([2, 1, 5, 9, 64, 7], 7, False),
+    'SM_COORDS_BWD_SEG': ([2, 1, 5, 9, 64, 7], 6, False), 'FINAL_CAT': ([32, 16384, 2, 512, 256], 3, False),
+    'SEED_DH': ([512, 256, 32], 3, False), 'LINEAR_DW_ORDER': ([5, 3, 2, 9], 5, False),
 }
+SEG_OPS = [op for op in GOOD if op.endswith('_SEG') or op in ('BN_SEG_FWD', 'BN_SEG_BWD')]
 
 # (op, index in dims) where 0 is legal: flags, `part` of SPLIT, and the sizes whose launcher returns early or reads no row.  With
 # one of these at 0 the argument set would be VALID, so it is never sent with fake addresses.
 ZERO_OK = {('LINEAR', 0), ('LINEAR', 3), ('LINEAR_DX', 0), ('LINEAR_DX', 3), ('LINEAR_DW', 0), ('FILL', 0), ('SCALE', 0),
-           ('SM_NODES_IN', 1), ('SM_NODES_IN', 2), ('SPLIT', 3), ('SPLIT', 4), ('BN_FWD', 2)}
+           ('SM_NODES_IN', 1), ('SM_NODES_IN', 2), ('SPLIT', 3), ('SPLIT', 4), ('BN_FWD', 2),
+           ('BN_SEG_FWD', 6), ('BN_SEG_FWD', 7), ('SEED_DH', 1), ('LINEAR_DW_ORDER', 0), ('LINEAR_DW_ORDER', 3)}
+ZERO_OK |= {(op, i) for op in SEG_OPS for i in (1, 2, 3, 4)}          # A, P, Nn, Ec: every segmented launcher guards an empty range
 
 
 def fake_geom(**kw):
@@ -55,7 +69,7 @@ def test_bad_arguments_fail_before_any_launch(op):
     assert _lib.train_op_raw(op, dims + [1], bufs, geom) == ERR_ARG           # wrong number of dims / buffers
     assert _lib.train_op_raw(op, dims, bufs + [FAKE], geom) == ERR_ARG
     assert _lib.train_op_raw(op, dims, bufs[:-1], geom) == ERR_ARG
-    optional = {'LINEAR': {2}, 'LINEAR_DW': {3}}.get(op, set())
+    optional = {'LINEAR': {2}, 'LINEAR_DW': {3}, 'LINEAR_DW_ORDER': {3}, 'BN_SEG_FWD': {9}}.get(op, set())
     for i in range(nb):                                          # a required buffer that is NULL
         if i in optional:                                        # a complete, valid argument set must never be sent with fake addresses
             continue
@@ -140,3 +154,136 @@ def test_batchnorm_reference_pair_is_tight_on_unit_scale_inputs(N, D):
         _, _, own, scale = H.bn_pair('unit', N, D, relu)
         for k in H.BN_TENSORS:
             assert own[k] <= 1e-5 * scale[k] + 1e-6, (k, own[k], scale[k])
+
+
+# ======================================================================================================================
+# the batched paths: B problems with the prefix [0, A) active; a loop count per graph
+# ======================================================================================================================
+@pytest.mark.parametrize('op', SEG_OPS)
+def test_segmented_operators_reject_a_bad_active_count(op):
+    dims, nb, _ = GOOD[op]
+    bufs = [FAKE] * nb
+    for B, A in ((2, 3), (1, 2), (0, 0), (-1, 0), (2, -1)):
+        assert _lib.train_op_raw(op, [B, A] + dims[2:], bufs) == ERR_ARG, (B, A)
+    for i in (2, 3, 4):                                          # negative totals
+        d = list(dims)
+        d[i] = -5
+        assert _lib.train_op_raw(op, d, bufs) == ERR_ARG, i
+    for i in range(4):                                           # all four prefix arrays are required
+        b = list(bufs)
+        b[i] = None
+        assert _lib.train_op_raw(op, dims, b) == ERR_NULL, i
+
+
+def test_loop_count_operators_reject_bad_row_tables():
+    b3 = [FAKE] * 3
+    cat = lambda D, stride, rows, n_it=None, bufs=b3: _lib.train_op_raw('FINAL_CAT', [D, stride, len(rows) if n_it is None else n_it] + rows, bufs)
+    assert cat(32, 16384, [256, 512]) == ERR_ARG                 # ascending
+    assert cat(32, 16384, [512, 512, 768]) == ERR_ARG
+    assert cat(32, 16384, [300, 256]) == ERR_DIMS                # not multiples of 256
+    assert cat(32, 16384, [512, 100]) == ERR_DIMS
+    assert cat(32, 16384, [], n_it=0) == ERR_ARG                 # n_it outside 1 .. GNNMP_TRAIN_BATCH_MAX_LOOP
+    assert cat(32, 16384, [256] * (_lib.TRAIN_BATCH_MAX_LOOP + 1)) == ERR_ARG
+    assert cat(32, 16384, [512, 256], n_it=1) == ERR_ARG         # a table longer / shorter than n_it
+    assert cat(32, 16384, [512, 256], n_it=3) == ERR_ARG
+    assert _lib.train_op_raw('FINAL_CAT', [32, 16384], b3) == ERR_ARG
+    assert cat(32, 16386, [512, 256]) == ERR_DIMS                # it_stride not a multiple of 4
+    for D in (16, 48, 128):
+        assert cat(D, 16384, [512, 256]) == ERR_DIMS
+    assert cat(32, 16384, [512, 256], bufs=[FAKE, FAKE + 4, FAKE]) == ERR_DIMS      # rows are moved in 16-byte pieces
+    assert cat(32, 16384, [512, 256], bufs=[FAKE, None, FAKE]) == ERR_NULL
+    seed = lambda *d: _lib.train_op_raw('SEED_DH', list(d), b3)
+    assert seed(256, 512, 32) == ERR_ARG                         # rows_next beyond rows_it
+    assert seed(300, 256, 32) == ERR_DIMS and seed(512, 100, 32) == ERR_DIMS
+    assert seed(512, 256, 128) == ERR_DIMS and seed(512, 256, 0) == ERR_ARG
+    assert _lib.train_op_raw('SEED_DH', [512, 256, 64], [FAKE + 8, FAKE, FAKE]) == ERR_DIMS
+
+
+def test_linear_dw_order_rejects_an_order_inside_the_rows():
+    for R_order in (1, 4):
+        assert _lib.train_op_raw('LINEAR_DW_ORDER', [5, 3, 2, R_order], [FAKE] * 5) == ERR_ARG
+    assert _lib.train_op_raw('LINEAR_DW_ORDER', [5, 3, 2, -1], [FAKE] * 5) == ERR_ARG
+    for K, O in H.DW_ORDER_PAIRS:                                # the same launcher: the same dispatch
+        assert _lib.train_op_path('LINEAR_DW_ORDER', 256, K, O) == _lib.train_op_path('LINEAR_DW', 256, K, O) == H.expected_path('LINEAR_DW', K, O)
+    assert {H.expected_path('LINEAR_DW', K, O) for K, O in H.DW_ORDER_PAIRS} == {'mfma', 'plain'}
+    assert any(H.dw_slice_width(R) != H.dw_slice_width(Ro) for R, Ro in H.DW_ORDER_ROWS)       # an order that changes the slices
+
+
+def test_ragged_batch_of_the_segmented_operators():
+    s = H.seg_ragged_batch(1)
+    assert s['B'] == 6 and s['P'] == 92 and s['Nn'] == 614 and s['sizes'].sum(1).tolist() == [2, 10, 293, 256, 11, 42]
+    for b in range(s['B']):                                      # the edge-space start of the kNN stage, spelled out
+        assert s['e0'][b] == ((int(s['edge_ptr'][b]) + 10 * int(s['path_ptr'][b]) + 31) // 32) * 32 + 32 * b and s['e0'][b] % 32 == 0
+    u = s['used']
+    assert (s['e_dst'][u] < s['sizes'][s['slot_b'][u], 0]).all() and (s['e_src'][u] < s['sizes'][s['slot_b'][u]].sum(1)).all()
+    e = np.nonzero(u & (s['slot_b'] == 2))[0]
+    assert len({(int(s['e_src'][i]), int(s['e_dst'][i])) for i in e}) < e.size                  # duplicate edges
+
+
+@pytest.mark.parametrize('P,F,Co,n', [(5, 4, 3, 30), (2, 0, 0, -1), (33, 7, 0, 0), (3, 0, 6, 7)])
+def test_segmented_references_are_the_one_problem_references_at_one_problem(P, F, Co, n):
+    rng = np.random.default_rng(P * 100 + F)
+    f = lambda *sh: rng.standard_normal(sh).astype(np.float32)
+    s = H.seg_edges(H.seg_layout([(P, F, Co)], [4]), [n], rng)
+    Nn, Ec, C, D, ne = s['Nn'], s['Ec'], 3, 8, int(s['n_edges'][0])
+    assert Nn == P + F + Co and s['e0'][0] == 0 and s['cap'][0] == Ec
+    src, dst = s['e_src'], s['e_dst']
+    sj, ti = src[:ne], dst[:ne]
+    cur, fr, co, old = f(P, C), f(F, C), f(Co, C), f(Nn, C + 3)
+    got, mask = H.nodes_in_seg_ref(s, 1, 2.5, cur, fr, co, old)
+    assert np.array_equal(got, H.sm_nodes_in_ref(cur, fr, co, 2.5)) and mask.all()
+    got, mask = H.nodes_in_seg_ref(s, 0, 2.5, cur, fr, co, old)
+    assert np.array_equal(got, old) and not mask.any()
+    X = f(Nn, D)
+    assert np.array_equal(H.msg_in_seg_ref(s, 1, X), H.sm_msg_in_ref(src, dst, ne, X))
+    assert not H.msg_in_seg_ref(s, 0, X).any()
+    dZ = f(Ec, 3 * D)
+    z = dZ[:ne]
+    acc, mag, fan, mask = H.msg_in_bwd_seg_ref(s, 1, dZ)
+    a1, m1 = H.segment_sum_ref(Nn, D, [(sj, z[:, :D]), (sj, z[:, D:2 * D]), (ti, z[:, 2 * D:]), (ti, -z[:, :D])])
+    assert np.array_equal(acc, a1) and np.array_equal(mag, m1) and mask.all()
+    assert fan == (int((np.bincount(sj, minlength=Nn) + np.bincount(ti, minlength=Nn)).max()) if ne else 1)
+    M = f(Ec, D)
+    acc, mag, fan = H.scatter_add_seg_ref(s, 1, M)
+    a1, m1 = H.segment_sum_ref(Nn, D, [(ti, M[:ne])])
+    assert np.array_equal(acc, a1[:P]) and np.array_equal(mag, m1[:P]) and not a1[P:].any()
+    dS = f(P, D)
+    ref = np.zeros((Ec, D), np.float32)
+    ref[:ne] = dS[ti]
+    assert np.array_equal(H.scatter_add_bwd_seg_ref(s, 1, dS), ref) and not H.scatter_add_bwd_seg_ref(s, 0, dS).any()
+    Y, oldp = f(P, D), f(P, D)
+    got, mask = H.add_path_seg_ref(s, 1, X, Y, oldp)
+    assert np.array_equal(got, X[:P] + Y) and mask.all()
+    assert np.array_equal(H.add_path_bwd_seg_ref(s, 1, Y), np.concatenate([Y, np.zeros((F + Co, D), np.float32)]))
+    prev, prop = f(P, C), f(P, C)
+    assert np.array_equal(H.path_update_seg_ref(s, 1, prev, prop), H.sm_path_update_ref(prev, prop))
+    assert np.array_equal(H.path_update_seg_ref(s, 0, prev, prop), prev)
+    dp, dq = H.path_update_bwd_seg_ref(s, 1, prev)
+    assert np.array_equal(dp + dq, prev) and np.array_equal(dp, H.sm_path_update_ref(np.zeros_like(prev), prev))
+    dp, dq = H.path_update_bwd_seg_ref(s, 0, prev)
+    assert not dp.any() and np.array_equal(dq, prev)
+    dXin, oldc = f(Nn, C + 3), f(P, C)
+    got, mask = H.coords_bwd_seg_ref(s, 1, dXin, oldc)
+    assert np.array_equal(got, oldc + dXin[:P, :C]) and mask.all()
+    part, dg, db = f(1, 1, 2, D), f(D), f(D)
+    g1, b1 = H.bn_seg_dgb_ref(part, dg, db)
+    assert np.array_equal(g1, dg + part[0, 0, 0]) and np.array_equal(b1, db + part[0, 0, 1]) and g1.dtype == np.float32
+
+
+def test_loop_count_references():
+    rng = np.random.default_rng(3)
+    f = lambda *sh: rng.standard_normal(sh).astype(np.float32)
+    NC, Hs = f(256, 4), f(1, 256, 4)
+    assert np.array_equal(H.final_cat_ref([256], NC, Hs), np.concatenate([NC, Hs[0]], 1))       # one iteration: model.py:143 as it stands
+    rows = [768, 512, 512, 256]
+    NC, Hs = f(768, 4), f(4, 768, 4)
+    got = H.final_cat_ref(rows, NC, Hs)
+    assert np.array_equal(got[:256, 4:], Hs[3, :256]) and np.array_equal(got[256:512, 4:], Hs[2, 256:512])
+    assert np.array_equal(got[512:, 4:], Hs[0, 512:]) and np.array_equal(got[:, :4], NC)
+    d_dec, dXin = f(512, 4), f(512, 16)
+    assert np.array_equal(H.seed_dh_ref(0, d_dec, dXin), d_dec) and np.array_equal(H.seed_dh_ref(512, d_dec, dXin), dXin[:, 12:])
+    got = H.seed_dh_ref(256, d_dec, dXin)
+    assert np.array_equal(got[:256], dXin[:256, 12:]) and np.array_equal(got[256:], d_dec[256:])
+    for t in H.FINAL_CAT_TABLES:
+        assert 1 <= len(t) <= 64 and all(r % 256 == 0 for r in t) and all(a >= b for a, b in zip(t, t[1:]))
+    assert len(H.FINAL_CAT_TABLES[2]) == 64

@@ -14,6 +14,10 @@ kernels branch.  For every case:
     deviation 1e-2) are the regression test of a fault this module found: with the column mean carried in float32 the kernels
     were 7.2e-3 off in y (bar 1.6e-3) and 0.38 off in dgamma (bar 0.31); they now carry it in double.
 
+The launchers of the two batched paths (the `_seg` operators of the smoother, FINAL_CAT / SEED_DH / LINEAR_DW_ORDER of the
+explorer) follow at the end of the file: their contracts -- problems past their loop count are absent, sums inside a problem keep
+the one-problem kernel's order, R_order reproduces the longer call -- are bit-exact statements and are tested as such.
+
 The worst err / bound per operator and the dispatch path of the three GEMM launchers are printed (pytest -s shows them;
 profiles/train_ops_unit.txt is that output from the MI355X)."""
 import ctypes
@@ -597,4 +601,294 @@ def test_smoother_gathers(C):
             n_, t_, d_, o = c.inp(ne), c.inp(dst), c.inp(dS), c.out('dM', (np.float32, (cap, D)))
             got = c.run(lambda a: op('SM_SCATTER_ADD_BWD', [D, cap], [a(n_), a(t_), a(d_), a(o)]))
             w.exact('SM_SCATTER_ADD_BWD', (P, C, n_edges), got['dM'], ref)
+    w.report()
+
+
+# ======================================================================================================================
+# the batched smoother path: B problems per call, the prefix [0, A) active (the `_seg` launchers)
+# ======================================================================================================================
+# What an operator does with a problem past its loop count is stated through the writable masks and bit equality: "left alone"
+# = outside the mask (the image check of Case.run), "zero" = +0.0 bit for bit, "handed through" = the input's bits.  The inputs of
+# such problems, the edge slots not in use and the old contents of every `+=` target are random non-zero numbers.
+def _seg_case(s):
+    c = Case()
+    return c, [c.inp(s[k]) for k in ('path_ptr', 'free_ptr', 'coll_ptr', 'edge_ptr')]
+
+
+def _seg_dims(s, A, *rest):
+    return [s['B'], A, s['P'], s['Nn'], s['Ec']] + list(rest)
+
+
+def _problem(s, b):
+    """node rows, path rows and edge slots of problem b"""
+    return (slice(int(s['n0'][b]), int(s['n0'][b + 1])), slice(int(s['path_ptr'][b]), int(s['path_ptr'][b + 1])),
+            slice(int(s['e0'][b]), int(s['e0'][b] + s['cap'][b])))
+
+
+@pytest.mark.parametrize('D', [32, 128])
+def test_segmented_feature_rows(D):
+    s = H.seg_ragged_batch(D)
+    rng = np.random.default_rng(300 + D)
+    f = lambda *sh: rng.standard_normal(sh).astype(np.float32)
+    w = Worst()
+    B, P, Nn, Ec = s['B'], s['P'], s['Nn'], s['Ec']
+    X, dZ, dX_old, M, dS, Y, Hh_old = f(Nn, D), f(Ec, 3 * D), f(Nn, D), f(Ec, D), f(P, D), f(P, D), f(P, D)
+    # the one-problem operators on every problem's own rows and edge segment: the summation order the segmented ones promise
+    one_dx, one_S = [], []
+    for b in range(B):
+        nr, pr, er = _problem(s, b)
+        ne = s['n_edges'][b:b + 1]
+        c = Case()
+        n_, s_, t_, z_, o = c.inp(ne), c.inp(s['e_src'][er]), c.inp(s['e_dst'][er]), c.inp(dZ[er]), c.out('dX', dX_old[nr])
+        one_dx.append(c.run(lambda a: op('SM_MSG_IN_BWD', [D, nr.stop - nr.start], [a(n_), a(s_), a(t_), a(z_), a(o)]))['dX'])
+        c = Case()
+        n_, t_, m_, o = c.inp(ne), c.inp(s['e_dst'][er]), c.inp(M[er]), c.out('S', np.zeros((pr.stop - pr.start, D), np.float32))
+        one_S.append(c.run(lambda a: op('SM_SCATTER_ADD', [D, pr.stop - pr.start], [a(n_), a(t_), a(m_), a(o)]))['S'])      # += onto 0
+    for A in H.SEG_ACTIVE:
+        dims = _seg_dims(s, A, D)
+        node_on, path_on = s['node_b'] < A, s['path_b'] < A
+        c, p = _seg_case(s)
+        n_, s_, t_, x_ = c.inp(s['n_edges']), c.inp(s['e_src']), c.inp(s['e_dst']), c.inp(X)
+        o = c.out('out', (np.float32, (Ec, 3 * D)))
+        got = c.run(lambda a: op('SM_MSG_IN_SEG', dims, [a(q) for q in p] + [a(n_), a(s_), a(t_), a(x_), a(o)]))
+        w.exact('SM_MSG_IN_SEG', (A, D), got['out'], H.msg_in_seg_ref(s, A, X))
+        acc, mag, fan, mask = H.msg_in_bwd_seg_ref(s, A, dZ)
+        c, p = _seg_case(s)
+        n_, s_, t_, z_ = c.inp(s['n_edges']), c.inp(s['e_src']), c.inp(s['e_dst']), c.inp(dZ)
+        o = c.out('dX', dX_old, writable=mask)
+        got = c.run(lambda a: op('SM_MSG_IN_BWD_SEG', dims, [a(q) for q in p] + [a(n_), a(s_), a(t_), a(z_), a(o)]))['dX']
+        w.bounded('SM_MSG_IN_BWD_SEG', (A, D), got[node_on], (dX_old + acc)[node_on], (H.gamma(fan) * mag + H.U * np.abs(dX_old))[node_on])
+        for b in range(A):
+            w.exact('SM_MSG_IN_BWD_SEG', (A, D, 'problem', b, 'against SM_MSG_IN_BWD'), got[_problem(s, b)[0]], one_dx[b])
+        acc, mag, fan = H.scatter_add_seg_ref(s, A, M)
+        c, p = _seg_case(s)
+        n_, t_, m_ = c.inp(s['n_edges']), c.inp(s['e_dst']), c.inp(M)
+        o = c.out('S', (np.float32, (P, D)))
+        got = c.run(lambda a: op('SM_SCATTER_ADD_SEG', dims, [a(q) for q in p] + [a(n_), a(t_), a(m_), a(o)]))['S']
+        w.bounded('SM_SCATTER_ADD_SEG', (A, D), got[path_on], acc[path_on], (H.gamma(fan) * mag)[path_on])
+        w.exact('SM_SCATTER_ADD_SEG', (A, D, 'absent problems'), got[~path_on], np.zeros((int((~path_on).sum()), D), np.float32))
+        for b in range(A):
+            w.exact('SM_SCATTER_ADD_SEG', (A, D, 'problem', b, 'against SM_SCATTER_ADD'), got[_problem(s, b)[1]], one_S[b])
+        c, p = _seg_case(s)
+        n_, t_, d_ = c.inp(s['n_edges']), c.inp(s['e_dst']), c.inp(dS)
+        o = c.out('dM', (np.float32, (Ec, D)))
+        got = c.run(lambda a: op('SM_SCATTER_ADD_BWD_SEG', dims, [a(q) for q in p] + [a(n_), a(t_), a(d_), a(o)]))['dM']
+        w.exact('SM_SCATTER_ADD_BWD_SEG', (A, D), got, H.scatter_add_bwd_seg_ref(s, A, dS))
+        ref, mask = H.add_path_seg_ref(s, A, X, Y, Hh_old)
+        c, p = _seg_case(s)
+        x_, y_ = c.inp(X), c.inp(Y)
+        o = c.out('out', Hh_old, writable=mask)
+        got = c.run(lambda a: op('SM_ADD_PATH_SEG', dims, [a(q) for q in p] + [a(x_), a(y_), a(o)]))['out']
+        w.exact('SM_ADD_PATH_SEG', (A, D), got, ref)
+        c, p = _seg_case(s)
+        d_ = c.inp(dS)
+        o = c.out('dX', (np.float32, (Nn, D)))
+        got = c.run(lambda a: op('SM_ADD_PATH_BWD_SEG', dims, [a(q) for q in p] + [a(d_), a(o)]))['dX']
+        w.exact('SM_ADD_PATH_BWD_SEG', (A, D), got, H.add_path_bwd_seg_ref(s, A, dS))
+    w.report()
+
+
+@pytest.mark.parametrize('C', [2, 7, 14])
+def test_segmented_coordinate_rows(C):
+    s = H.seg_ragged_batch(C)
+    rng = np.random.default_rng(400 + C)
+    f = lambda *sh: rng.standard_normal(sh).astype(np.float32)
+    w = Worst()
+    P, Nn, scale = s['P'], s['Nn'], 2.5
+    cur, fr, co, Xin_old = f(P, C), f(s['F'], C), f(s['Co'], C), f(Nn, C + 3)
+    prop, dn, dXin, dprev_old = f(P, C), f(P, C), f(Nn, C + 3), f(P, C)
+    for A in H.SEG_ACTIVE:
+        dims = _seg_dims(s, A, C)
+        ref, mask = H.nodes_in_seg_ref(s, A, scale, cur, fr, co, Xin_old)
+        c, p = _seg_case(s)
+        a0, a1, a2 = c.inp(cur), c.inp(fr), c.inp(co)
+        o = c.out('out', Xin_old, writable=mask)
+        got = c.run(lambda a: op('SM_NODES_IN_SEG', dims, [a(q) for q in p] + [a(a0), a(a1), a(a2), a(o)], scalar=scale))['out']
+        w.exact('SM_NODES_IN_SEG', (A, C), got, ref)
+        c, p = _seg_case(s)
+        a0, a1 = c.inp(cur), c.inp(prop)
+        o = c.out('next', (np.float32, (P, C)))
+        got = c.run(lambda a: op('SM_PATH_UPDATE_SEG', dims, [a(q) for q in p] + [a(a0), a(a1), a(o)]))['next']
+        w.exact('SM_PATH_UPDATE_SEG', (A, C), got, H.path_update_seg_ref(s, A, cur, prop))
+        c, p = _seg_case(s)
+        a0 = c.inp(dn)
+        o1, o2 = c.out('dprop', (np.float32, (P, C))), c.out('dprev', (np.float32, (P, C)))
+        got = c.run(lambda a: op('SM_PATH_UPDATE_BWD_SEG', dims, [a(q) for q in p] + [a(a0), a(o1), a(o2)]))
+        r1, r2 = H.path_update_bwd_seg_ref(s, A, dn)
+        w.exact('SM_PATH_UPDATE_BWD_SEG', (A, C, 'proposal'), got['dprop'], r1)
+        w.exact('SM_PATH_UPDATE_BWD_SEG', (A, C, 'prev'), got['dprev'], r2)
+        ref, mask = H.coords_bwd_seg_ref(s, A, dXin, dprev_old)
+        c, p = _seg_case(s)
+        a0 = c.inp(dXin)
+        o = c.out('dprev', dprev_old, writable=mask)
+        got = c.run(lambda a: op('SM_COORDS_BWD_SEG', dims, [a(q) for q in p] + [a(a0), a(o)]))['dprev']
+        w.exact('SM_COORDS_BWD_SEG', (A, C), got, ref)
+    w.report()
+
+
+@pytest.mark.parametrize('kind', ['unit', 'cancel'])
+def test_segmented_batchnorm(kind):
+    """Per active problem bit-equal to BN_FWD / BN_BWD on its rows alone (dgamma / dbeta from zero), and -- so that the test
+    does not rest on the sibling kernel alone -- inside the bar of test_batchnorm against float64, own = torch's float32 result
+    on the same rows.  Absent problems: y, stats and out_stats untouched, dx and part +0.0."""
+    s = H.seg_ragged_batch(7)
+    B, Nn, L, it = s['B'], s['Nn'], 3, 1
+    w, fail = Worst(), []
+    worst = {k: (0.0, None) for k in H.BN_TENSORS}
+    for D in (32, 128):
+        inp = H.bn_inputs(kind, Nn, D, seed=5000 + D + (7 if kind == 'cancel' else 0))
+        rng = np.random.default_rng(D)
+        f = lambda *sh: rng.standard_normal(sh).astype(np.float32)
+        y_old, st_old, ost_old = f(Nn, D), f(B, 3, D), f(B, L, 2, D)
+        zero = np.zeros(D, np.float32)
+        stride = L * 2 * D
+        for relu in (0, 1):
+            one, r64, own, scale = [], [], [], []
+            for b in range(B):
+                nr = _problem(s, b)[0]
+                N = nr.stop - nr.start
+                c = Case()
+                x, g, be, dy = c.inp(inp['x'][nr]), c.inp(inp['gamma']), c.inp(inp['beta']), c.inp(inp['dy'][nr])
+                y, st, dx = c.out('y', (np.float32, (N, D))), c.out('stats', (np.float32, (3, D))), c.out('dx', (np.float32, (N, D)))
+                dg, db = c.out('dgamma', zero), c.out('dbeta', zero)
+
+                def launch(a):
+                    op('BN_FWD', [N, D, relu], [a(x), a(g), a(be), a(y), a(st)])
+                    op('BN_BWD', [N, D], [a(x), a(dy), a(g), a(st), a(dx), a(dg), a(db)])
+                one.append(c.run(launch))
+                args = (inp['x'][nr], inp['gamma'], inp['beta'], relu, inp['dy'][nr], zero, zero)
+                r64.append(H.bn_ref(*args))
+                r32 = H.bn_torch32(*args)
+                own.append({k: float(np.max(np.abs(r32[k].astype(np.float64) - r64[b][k]))) for k in H.BN_TENSORS})
+                scale.append({k: float(np.max(np.abs(r64[b][k]))) for k in H.BN_TENSORS})
+            for A in H.SEG_ACTIVE:
+                with_out = A != 4                                 # out_stats may be NULL
+                node_on = np.broadcast_to((s['node_b'] < A)[:, None], (Nn, D))
+                prob_on = np.arange(B) < A
+                c, p = _seg_case(s)
+                x, g, be, dy = c.inp(inp['x']), c.inp(inp['gamma']), c.inp(inp['beta']), c.inp(inp['dy'])
+                y = c.out('y', y_old, writable=node_on)
+                st = c.out('stats', st_old, writable=np.broadcast_to(prob_on[:, None, None], (B, 3, D)))
+                om = np.zeros((B, L, 2, D), bool)
+                om[:A, it] = with_out
+                ost = c.out('out_stats', ost_old, writable=om)
+                dx, part = c.out('dx', (np.float32, (Nn, D))), c.out('part', (np.float32, (B, 2, D)))
+
+                def launch(a):
+                    op('BN_SEG_FWD', _seg_dims(s, A, D, relu, stride), [a(q) for q in p] + [a(x), a(g), a(be), a(y), a(st),
+                                                                                              a(ost + it * 2 * D) if with_out else None])
+                    op('BN_SEG_BWD', _seg_dims(s, A, D), [a(q) for q in p] + [a(x), a(dy), a(g), a(st), a(dx), a(part)])
+                got = c.run(launch)
+                tag = (kind, A, D, relu)
+                w.exact('BN_SEG_BWD', tag + ('dx of absent problems',), got['dx'][~node_on[:, 0]], np.zeros((int((~node_on[:, 0]).sum()), D), np.float32))
+                w.exact('BN_SEG_BWD', tag + ('part of absent problems',), got['part'][A:], np.zeros((B - A, 2, D), np.float32))
+                for b in range(A):
+                    nr = _problem(s, b)[0]
+                    o1 = one[b]
+                    mine = dict(y=got['y'][nr], mean=got['stats'][b, 0], invstd=got['stats'][b, 1], var=got['stats'][b, 2], dx=got['dx'][nr],
+                                dgamma=got['part'][b, 0], dbeta=got['part'][b, 1])
+                    w.exact('BN_SEG_FWD', tag + (b, 'y'), mine['y'], o1['y'])
+                    w.exact('BN_SEG_FWD', tag + (b, 'stats'), got['stats'][b], o1['stats'])
+                    if with_out:
+                        w.exact('BN_SEG_FWD', tag + (b, 'out_stats'), got['out_stats'][b, it], o1['stats'][[0, 2]])
+                    w.exact('BN_SEG_BWD', tag + (b, 'dx'), mine['dx'], o1['dx'])
+                    w.exact('BN_SEG_BWD', tag + (b, 'part'), got['part'][b], np.stack([o1['dgamma'], o1['dbeta']]))
+                    for k in H.BN_TENSORS:
+                        assert np.isfinite(mine[k]).all(), (k, tag, b)
+                        err = float(np.max(np.abs(mine[k].astype(np.float64) - r64[b][k])))
+                        bar = max(1e-4 * scale[b][k], 4 * own[b][k]) + 1e-6
+                        rel = err / bar
+                        if rel > worst[k][0]:
+                            worst[k] = (rel, tag + (b, 'err %.3e own %.3e bar %.3e' % (err, own[b][k], bar)))
+                        if err > bar:
+                            fail.append((k, tag, b, 'err %.3e > bar %.3e (own %.3e, scale %.3e)' % (err, bar, own[b][k], scale[b][k])))
+    for k in H.BN_TENSORS:
+        print('[train_ops] BN_SEG %-6s %-7s worst err/bar %.3e at %s' % (kind, k, worst[k][0], worst[k][1]))
+    assert not fail, fail[:20]
+    w.report()
+
+
+def test_segmented_batchnorm_dgamma_dbeta():
+    w = Worst()
+    L, B = 3, 6
+    for D in (32, 128):
+        rng = np.random.default_rng(600 + D)
+        part, dg_old, db_old = (rng.standard_normal(sh).astype(np.float32) for sh in ((L, B, 2, D), (D,), (D,)))
+        c = Case()
+        p_, g_, b_ = c.inp(part), c.out('dgamma', dg_old), c.out('dbeta', db_old)
+        got = c.run(lambda a: op('BN_SEG_DGB', [L, B, D], [a(p_), a(g_), a(b_)]))
+        rg, rb = H.bn_seg_dgb_ref(part, dg_old, db_old)
+        w.exact('BN_SEG_DGB', (D, 'dgamma'), got['dgamma'], rg)
+        w.exact('BN_SEG_DGB', (D, 'dbeta'), got['dbeta'], rb)
+    w.report()
+
+
+# ======================================================================================================================
+# the explorer's path with a loop count per graph
+# ======================================================================================================================
+@pytest.mark.parametrize('D', [32, 64])
+def test_final_cat(D):
+    w = Worst()
+    for t, rows in enumerate(H.FINAL_CAT_TABLES):
+        rng = np.random.default_rng(700 + D + t)
+        n_it, R = len(rows), rows[0]
+        stride = R * D + 192                                     # the slabs lie apart, the sentinel between them
+        NC, Hs = rng.standard_normal((R, D)).astype(np.float32), rng.standard_normal((n_it, R, D)).astype(np.float32)
+        slabs = np.full(n_it * stride, SENT, np.uint32).view(np.float32)
+        for i in range(n_it):
+            slabs[i * stride:i * stride + R * D] = Hs[i].reshape(-1)
+        c = Case()
+        n_, h_, o = c.inp(NC), c.inp(slabs), c.out('out', (np.float32, (R, 2 * D)))
+        got = c.run(lambda a: op('FINAL_CAT', [D, stride, n_it] + list(rows), [a(n_), a(h_), a(o)]))['out']
+        w.exact('FINAL_CAT', (D, n_it, R), got, H.final_cat_ref(rows, NC, Hs))
+    w.report()
+
+
+@pytest.mark.parametrize('D', [32, 64])
+def test_seed_dh(D):
+    w = Worst()
+    R = 1024
+    rng = np.random.default_rng(800 + D)
+    d_dec, dXin = rng.standard_normal((R, D)).astype(np.float32), rng.standard_normal((R, 4 * D)).astype(np.float32)
+    for nxt in (0, 256, 768, 1024):
+        c = Case()
+        d_, x_, o = c.inp(d_dec), c.inp(dXin), c.out('dH', (np.float32, (R, D)))
+        got = c.run(lambda a: op('SEED_DH', [R, nxt, D], [a(d_), a(x_), a(o)]))['dH']
+        w.exact('SEED_DH', (D, R, nxt), got, H.seed_dh_ref(nxt, d_dec, dXin))
+    w.report()
+
+
+def test_linear_dw_order():
+    """dW / db of a call over the first R rows in the order of R_order rows: bit-equal to LINEAR_DW over R_order rows whose dY rows
+    >= R are zero (X is random there), and inside LINEAR_DW's bound of float64.  Where the order changes the width of the second
+    stage's slices the result is NOT that of LINEAR_DW at R rows: at least one case shows it."""
+    w = Worst()
+    seen, differs = set(), 0
+    for i, (K, O) in enumerate(H.DW_ORDER_PAIRS):
+        path = _lib.train_op_path('LINEAR_DW_ORDER', 256, K, O)
+        assert path == H.expected_path('LINEAR_DW', K, O) == _lib.train_op_path('LINEAR_DW', 256, K, O)
+        seen.add(path)
+        for j, (R, Ro) in enumerate(H.DW_ORDER_ROWS):
+            X, W0, b0, _, rng = _gemm_inputs(Ro, K, O, 30000 + 10 * i + j)
+            dY = rng.standard_normal((R, O)).astype(np.float32)
+            dY_all = np.concatenate([dY, np.zeros((Ro - R, O), np.float32)])
+
+            def run(name, dims, dy_rows, x_rows):
+                c = Case()
+                dy, x, dw, db = c.inp(dy_rows), c.inp(x_rows), c.out('dW', W0), c.out('db', b0)
+                sc = c.out('scratch', np.full(_lib.train_dw_scratch_floats(len(dy_rows), K, O), np.nan, np.float32))
+                return c.run(lambda a: op(name, dims, [a(dy), a(x), a(dw), a(db), a(sc)]))
+            got = run('LINEAR_DW_ORDER', [R, K, O, Ro], dY, X[:R])
+            full = run('LINEAR_DW', [Ro, K, O], dY_all, X)
+            w.exact('LINEAR_DW_ORDER', (R, Ro, K, O, 'dW'), got['dW'], full['dW'])
+            w.exact('LINEAR_DW_ORDER', (R, Ro, K, O, 'db'), got['db'], full['db'])
+            rW, bW, rb, bb = H.linear_dw_ref(dY, X[:R], W0, b0)
+            w.bounded('LINEAR_DW_ORDER', (R, Ro, K, O, 'dW'), got['dW'], rW, bW, path)
+            w.bounded('LINEAR_DW_ORDER', (R, Ro, K, O, 'db'), got['db'], rb, bb, path)
+            if H.dw_slice_width(R) != H.dw_slice_width(Ro):
+                plain = run('LINEAR_DW', [R, K, O], dY, X[:R])
+                differs += int(not np.array_equal(plain['dW'].view(np.uint32), got['dW'].view(np.uint32)))
+    assert seen == {'mfma', 'plain'}
+    print('[train_ops] LINEAR_DW_ORDER      cases whose bits differ from LINEAR_DW over the R rows alone: %d' % differs)
+    assert differs > 0
     w.report()

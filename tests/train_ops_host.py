@@ -220,3 +220,208 @@ def segment_sum_ref(Npad, D, terms):
         np.add.at(acc, nodes, rows.astype(np.float64))
         np.add.at(mag, nodes, np.abs(rows.astype(np.float64)))
     return acc, mag
+
+
+# ---- the batched smoother path: B problems per call, the prefix [0, A) active -------------------------------------
+# Restated from the module, not from the kernels: nodes = cat(path, free / scale, collided / scale) with a one-hot kind
+# (model_smoother.py:118-135), z = cat(x_j - x_i, x_j, x_i) summed into the target (:32-37), path[1:-1] = proposal[1:-1] (:139),
+# every problem on its own rows.  A problem past its loop count (b >= A) takes no part: its outputs are left alone, zero, or
+# its state handed through, as include/gnnmp.h says per operator.
+SM_K = 10                                    # kNN edges per waypoint (model_smoother.py:125)
+SEG_SIZES = ((2, 0, 0), (3, 4, 3), (33, 200, 60), (12, 244, 0), (2, 5, 4), (40, 1, 1))      # (P, F, Co) per problem
+SEG_CALLER_EDGES = (0, 5, 100, 37, 0, 64)    # E_b of edge_ptr: only the slot layout depends on it
+SEG_N_EDGES = (-1, 20, 300, 0, -1, 100)      # slots in use; -1 = the whole segment
+SEG_ACTIVE = (6, 4, 1)
+BAD_ID = 1 << 28
+
+
+def round32(x):
+    return (int(x) + 31) & ~31
+
+
+def seg_layout(sizes, caller_edges):
+    """Prefix arrays of a batch and where every problem's rows and edge slots start: node rows are stacked [path_b; free_b;
+    collided_b] problem by problem, edge slots start at round32(edge_ptr[b] + 10 path_ptr[b]) + 32 b (the kNN stage's padded edge
+    space); Ec = the slots the product's workspace holds."""
+    sizes = np.asarray(sizes, np.int64).reshape(-1, 3)
+    B = len(sizes)
+    pp, fp, cp = (np.concatenate([[0], np.cumsum(sizes[:, i])]) for i in range(3))
+    ep = np.concatenate([[0], np.cumsum(np.asarray(caller_edges, np.int64))])
+    n0 = pp + fp + cp
+    e0 = np.array([round32(ep[b] + SM_K * pp[b]) + 32 * b for b in range(B)], np.int64)
+    Ec = round32(ep[B] + SM_K * pp[B] + 64 * B + 32)
+    assert (np.diff(e0) >= 0).all() and e0[-1] < Ec
+    s = dict(B=B, sizes=sizes, path_ptr=pp.astype(np.int32), free_ptr=fp.astype(np.int32), coll_ptr=cp.astype(np.int32),
+             edge_ptr=ep.astype(np.int32), n0=n0, e0=e0, cap=np.append(e0[1:], Ec) - e0, P=int(pp[B]), F=int(fp[B]), Co=int(cp[B]),
+             Nn=int(n0[B]), Ec=Ec)
+    # node row of every path / free / collided row, problem and local index of every path row
+    s['path_rows'] = np.concatenate([n0[b] + np.arange(sizes[b, 0]) for b in range(B)]).astype(np.int64)
+    s['free_rows'] = np.concatenate([n0[b] + sizes[b, 0] + np.arange(sizes[b, 1]) for b in range(B)]).astype(np.int64)
+    s['coll_rows'] = np.concatenate([n0[b] + sizes[b, 0] + sizes[b, 1] + np.arange(sizes[b, 2]) for b in range(B)]).astype(np.int64)
+    s['path_b'] = np.repeat(np.arange(B), sizes[:, 0])
+    s['path_local'] = np.concatenate([np.arange(p) for p in sizes[:, 0]]).astype(np.int64)
+    s['node_b'] = np.repeat(np.arange(B), sizes.sum(1))
+    s['slot_b'] = np.searchsorted(e0, np.arange(Ec), side='right') - 1
+    return s
+
+
+def seg_edges(s, n_edges, rng):
+    """Edge slots of the layout `s`: problem b uses its first n_edges[b] slots (-1 = all of them), sources anywhere among its
+    node rows, targets among its path rows except the last (a path row without an incoming edge); slots 0 and 1 are duplicates
+    and, where there is room, 40 slots share one target.  Slots not in use hold an id nothing may follow."""
+    B, Ec = s['B'], s['Ec']
+    ne = np.array([s['cap'][b] if n_edges[b] < 0 else n_edges[b] for b in range(B)], np.int32)
+    assert (ne <= s['cap']).all()
+    src, dst = np.full(Ec, BAD_ID, np.int32), np.full(Ec, BAD_ID, np.int32)
+    for b in range(B):
+        P, N, n, e = int(s['sizes'][b, 0]), int(s['sizes'][b].sum()), int(ne[b]), int(s['e0'][b])
+        src[e:e + n], dst[e:e + n] = rng.integers(0, N, n), rng.integers(0, max(P - 1, 1), n)
+        if n >= 2:
+            src[e + 1], dst[e + 1] = src[e], dst[e]
+        if n >= 60 and P > 2:
+            dst[e + 10:e + 50] = P // 2
+    s = dict(s, n_edges=ne, e_src=src, e_dst=dst)
+    s['used'] = np.arange(Ec) - s['e0'][s['slot_b']] < ne[s['slot_b']]
+    return s
+
+
+def seg_ragged_batch(seed):
+    """The ragged batch of the segmented operators: N = 2 without samples; 293 node rows (the 256-stride row loops wrap, the path
+    rows cross a 32-row tile); exactly 256 node rows and no edge; full, partly used and empty edge segments."""
+    s = seg_edges(seg_layout(SEG_SIZES, SEG_CALLER_EDGES), SEG_N_EDGES, np.random.default_rng(seed))
+    u = s['used']
+    into = np.bincount(s['path_ptr'][s['slot_b'][u]] + s['e_dst'][u], minlength=s['P'])
+    assert into.max() > 32 and (into == 0).any() and (s['n_edges'] == 0).any() and (s['n_edges'] == s['cap']).any()
+    assert ((s['n_edges'] > 0) & (s['n_edges'] < s['cap'])).any() and (s['e_src'][~u] == BAD_ID).all()
+    return s
+
+
+def _seg_sel(s, A):
+    """slots in use of active problems -> (slot ids, node row of the source, node row of the target, path row of the target)"""
+    e = np.nonzero(s['used'] & (s['slot_b'] < A))[0]
+    b = s['slot_b'][e]
+    return e, s['n0'][b] + s['e_src'][e], s['n0'][b] + s['e_dst'][e], s['path_ptr'][b] + s['e_dst'][e]
+
+
+def nodes_in_seg_ref(s, A, scale, cur, free_pts, coll, old):
+    C = cur.shape[1]
+    x = np.zeros((s['Nn'], C + 3), np.float32)
+    x[s['path_rows'], :C], x[s['path_rows'], C] = cur, 1
+    x[s['free_rows'], :C], x[s['free_rows'], C + 1] = free_pts / np.float32(scale), 1
+    x[s['coll_rows'], :C], x[s['coll_rows'], C + 2] = coll / np.float32(scale), 1
+    on = (s['node_b'] < A)[:, None]
+    return np.where(on, x, old), np.broadcast_to(on, x.shape)
+
+
+def msg_in_seg_ref(s, A, X):
+    e, js, it, _ = _seg_sel(s, A)
+    out = np.zeros((s['Ec'], 3 * X.shape[1]), np.float32)
+    out[e] = np.concatenate([X[js] - X[it], X[js], X[it]], 1)
+    return out
+
+
+def msg_in_bwd_seg_ref(s, A, dZ):
+    """float64 sum, absolute sum, largest number of edges at one node, rows the operator adds to"""
+    D = dZ.shape[1] // 3
+    e, js, it, _ = _seg_sel(s, A)
+    z = dZ[e]
+    acc, mag = segment_sum_ref(s['Nn'], D, [(js, z[:, :D]), (js, z[:, D:2 * D]), (it, z[:, 2 * D:]), (it, -z[:, :D])])
+    fan = int((np.bincount(js, minlength=s['Nn']) + np.bincount(it, minlength=s['Nn'])).max()) if e.size else 1
+    return acc, mag, fan, np.broadcast_to((s['node_b'] < A)[:, None], acc.shape)
+
+
+def scatter_add_seg_ref(s, A, M):
+    e, _, _, pt = _seg_sel(s, A)
+    acc, mag = segment_sum_ref(s['P'], M.shape[1], [(pt, M[e])])
+    return acc, mag, int(np.bincount(pt, minlength=s['P']).max()) if e.size else 1
+
+
+def scatter_add_bwd_seg_ref(s, A, dS):
+    e, _, _, pt = _seg_sel(s, A)
+    out = np.zeros((s['Ec'], dS.shape[1]), np.float32)
+    out[e] = dS[pt]
+    return out
+
+
+def add_path_seg_ref(s, A, X, Y, old):
+    on = (s['path_b'] < A)[:, None]
+    return np.where(on, X[s['path_rows']] + Y, old), np.broadcast_to(on, Y.shape)
+
+
+def add_path_bwd_seg_ref(s, A, dH):
+    out = np.zeros((s['Nn'], dH.shape[1]), np.float32)
+    on = s['path_b'] < A
+    out[s['path_rows'][on]] = dH[on]
+    return out
+
+
+def _seg_inner(s, A):
+    return ((s['path_b'] < A) & (s['path_local'] >= 1) & (s['path_local'] <= s['sizes'][s['path_b'], 0] - 2))[:, None]
+
+
+def path_update_seg_ref(s, A, prev, proposal):
+    return np.where(_seg_inner(s, A), proposal, prev)
+
+
+def path_update_bwd_seg_ref(s, A, d_next):
+    inner = _seg_inner(s, A)
+    return np.where(inner, d_next, np.float32(0)), np.where(inner, np.float32(0), d_next)
+
+
+def coords_bwd_seg_ref(s, A, dXin, old):
+    on = (s['path_b'] < A)[:, None]
+    return np.where(on, old + dXin[s['path_rows'], :old.shape[1]], old), np.broadcast_to(on, old.shape)
+
+
+def bn_seg_dgb_ref(part, dgamma_old, dbeta_old):
+    """part [L, B, 2, D] -> float32 sums in the documented order: iterations last to first, problems ascending"""
+    dg, db = dgamma_old.copy(), dbeta_old.copy()
+    for it in range(part.shape[0] - 1, -1, -1):
+        for b in range(part.shape[1]):
+            dg, db = dg + part[it, b, 0], db + part[it, b, 1]
+    return dg, db
+
+
+# the one-problem forms (the module's own call), against which the segmented references are checked at B = 1
+def sm_nodes_in_ref(cur, free_pts, coll, scale):
+    P, F, Co, C = len(cur), len(free_pts), len(coll), cur.shape[1]
+    info = np.zeros((P + F + Co, 3), np.float32)
+    info[:P, 0], info[P:P + F, 1], info[P + F:, 2] = 1, 1, 1
+    return np.concatenate([np.concatenate([cur, free_pts / np.float32(scale), coll / np.float32(scale)]), info], 1)
+
+
+def sm_msg_in_ref(src, dst, n, X):
+    out = np.zeros((len(src), 3 * X.shape[1]), np.float32)
+    out[:n] = np.concatenate([X[src[:n]] - X[dst[:n]], X[src[:n]], X[dst[:n]]], 1)
+    return out
+
+
+def sm_path_update_ref(prev, proposal):
+    out = prev.copy()
+    out[1:-1] = proposal[1:-1]
+    return out
+
+
+# ---- the explorer's path with a loop count per graph -------------------------------------------------------------
+def final_cat_ref(rows, NC, Hs):
+    """rows[it] = rows of the graphs still running in iteration it (descending); Hs [n_it, rows[0], D].  Row n's graph ran
+    L(n) = #{it: rows[it] > n} iterations, and the decoder reads cat(node_code, h after its last one) (model.py:143)."""
+    n = np.arange(rows[0])
+    L = (np.asarray(rows)[:, None] > n[None, :]).sum(0)
+    return np.concatenate([NC, Hs[L - 1, n]], 1)
+
+
+def seed_dh_ref(rows_next, d_dec, dXin):
+    D = d_dec.shape[1]
+    return np.where((np.arange(len(d_dec)) >= rows_next)[:, None], d_dec, dXin[:, 3 * D:4 * D])
+
+
+FINAL_CAT_TABLES = ([256], [1280, 1024, 1024, 512, 256], [768] * 20 + [512] * 22 + [256] * 22)
+DW_ORDER_PAIRS = ((32, 1), (8, 32), (160, 32), (128, 64))
+DW_ORDER_ROWS = ((256, 256), (256, 2304), (1024, 2304), (300, 1300))
+DW_BLOCK_ROWS = 128                          # rows per partial sum of LINEAR_DW's first stage (train_kernels.hip kDwRows)
+
+
+def dw_slice_width(R):
+    """blocks per slice of LINEAR_DW's second stage at R rows: eight slices over ceil(R / 128) partial sums"""
+    return ((R + DW_BLOCK_ROWS - 1) // DW_BLOCK_ROWS + 7) // 8
