@@ -173,6 +173,7 @@ def lib():
                                         vp, vp, vp, vp, vp, sz, vp]
     L.gnnmp_maze_sample.argtypes = [ctypes.POINTER(MazeSampleBatch), vp, vp, vp, vp, vp, vp]
     L.gnnmp_maze_steer.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.gnnmp_stick_steer.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.gnnmp_episode_label_maze.argtypes = [ctypes.POINTER(EpisodeGraphs), ctypes.c_int32, ctypes.c_int32, vp, vp, vp, vp, vp]
     L.gnnmp_episode_workspace_bytes.argtypes = [ctypes.POINTER(EpisodeGraphs), ctypes.POINTER(sz)]
     L.gnnmp_episode_paths.argtypes = [ctypes.POINTER(EpisodeGraphs), vp, vp, vp, vp, vp, vp, sz, vp]

@@ -177,14 +177,16 @@ struct MazeParams {
 };
 hipError_t launch_maze_explore(const MazeParams& p, hipStream_t st);
 
-// collision-checked steering of the smoothing stage (smoother.py:194-216) for 2-D mazes
+// collision-checked steering of the smoothing stage (smoother.py:194-216) for 2-D mazes (dim = 2) and the stick robot (dim = 3)
 struct MazeSteerParams {
     int B, w;
     const double* maps;                   // [B, w, w]
     const int* path_ptr;                  // [B + 1]
-    const float *old_path, *new_path;     // [sumP, 2]
-    float *out_path, *tmp;                // [sumP, 2]
+    const float *old_path, *new_path;     // [sumP, dim]
+    float *out_path, *tmp;                // [sumP, dim]
     long long* checks;                    // [B], incremented
+    int dim = 2;
+    int* status = nullptr;                // dim = 3: [B], 0 = ok, 1 = MazeEnv.interpolate's orientation assert would have fired
 };
 hipError_t launch_maze_steer(const MazeSteerParams& p, hipStream_t st);
 

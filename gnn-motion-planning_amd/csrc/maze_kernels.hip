@@ -182,6 +182,95 @@ __device__ bool stick_edge_fp(MazeCtx& m, const float* s, const float* t) {     
     return true;
 }
 
+// ---- the same stick queries for a whole wave (steering of the 3-DoF maze).  An edge query interpolates up to ~190
+// sticks (K = int(d / 0.015)), each a float64 cos / sin and a short bisection: the interior configurations k = 1 .. K - 1
+// go to the lanes, 64 per pass.  Every lane counts its own checks and stops at its own first blocked query; the first
+// failing k decides the edge, and the edge's count is what the sequential loop would have spent: all of the k below it plus
+// the failing k's own.  Passes after a failing pass are not run.  The bisection stack is per lane: a stick is 0.2 long, its
+// ends at most 0.283 apart in L1, so only segments of levels 0 .. 2 split (0.283 / 8 < RRT_EPS) and the depth-first walk
+// never holds more than four segments; the stack has one slot to spare.  LDS layout [component][slot][lane]: conflict-free.
+constexpr int kLaneStackSlots = 5;
+
+__device__ __forceinline__ bool lane_point_fp64(const MazeCtx& m, double x, double y, int& cnt) {
+    if (!maze_valid64(x, y)) return false;
+    cnt += 1;
+    const int idx = maze_cell64(x, m.w) * m.w + maze_cell64(y, m.w);
+    return m.occ ? m.occ[idx] == 0 : m.map[idx] == 0.0;
+}
+// stk: this lane's column of the LDS stack
+__device__ __forceinline__ bool lane_segment_fp64(const MazeCtx& m, double* stk, double ax, double ay, double bx, double by,
+                                                  int& cnt) {
+#define LANE_STK(c, s) stk[((c) * kLaneStackSlots + (s)) * 64]
+    int sp = 1;
+    LANE_STK(0, 0) = ax; LANE_STK(1, 0) = ay; LANE_STK(2, 0) = bx; LANE_STK(3, 0) = by;
+    while (sp > 0) {
+        --sp;
+        const double lx = LANE_STK(0, sp), ly = LANE_STK(1, sp), rx = LANE_STK(2, sp), ry = LANE_STK(3, sp);
+        const int dc = abs(maze_cell64(lx, m.w) - maze_cell64(rx, m.w)) + abs(maze_cell64(ly, m.w) - maze_cell64(ry, m.w));
+        const double l1 = fabs(lx - rx) + fabs(ly - ry);
+        if (dc > 1 && l1 > 0.05) {
+            const double mx = (lx + rx) / 2.0, my = (ly + ry) / 2.0;
+            if (!lane_point_fp64(m, mx, my, cnt)) return false;
+            if (sp + 2 > kLaneStackSlots) return false;          // cannot happen: see the depth bound above
+            LANE_STK(0, sp) = mx; LANE_STK(1, sp) = my; LANE_STK(2, sp) = rx; LANE_STK(3, sp) = ry; ++sp;
+            LANE_STK(0, sp) = lx; LANE_STK(1, sp) = ly; LANE_STK(2, sp) = mx; LANE_STK(3, sp) = my; ++sp;
+        }
+    }
+    return true;
+#undef LANE_STK
+}
+__device__ __forceinline__ bool lane_stick_state_fp(const MazeCtx& m, double* stk, const float (&c)[3], int& cnt) {
+    if (!maze_valid3(c[0], c[1], c[2])) return false;
+    double ax, ay, bx, by;
+    stick_ends(c[0], c[1], c[2], ax, ay, bx, by);
+    if (!lane_point_fp64(m, ax, ay, cnt) || !lane_point_fp64(m, bx, by, cnt)) return false;
+    return lane_segment_fp64(m, stk, ax, ay, bx, by, cnt);
+}
+__device__ __forceinline__ bool wave_uniform(bool x) { return __builtin_amdgcn_readfirstlane(x ? 1 : 0) != 0; }
+
+// _edge_fp(s, t), state.size == 3, by all 64 lanes of the wave; s and t are the same in every lane, and so are the
+// result and `checks`.  The two end configurations are checked by every lane alike (the reference's order, one count).
+__device__ __forceinline__ bool stick_edge_wave(const MazeCtx& m, double* stk, int lane, const float (&s)[3], const float (&t)[3],
+                                long long& checks) {
+    if (!maze_valid3(s[0], s[1], s[2]) || !maze_valid3(t[0], t[1], t[2])) return false;
+    int c_ends = 0;
+    const bool ends_ok = wave_uniform(lane_stick_state_fp(m, stk, s, c_ends) && lane_stick_state_fp(m, stk, t, c_ends));
+    checks += __builtin_amdgcn_readfirstlane(c_ends);
+    if (!ends_ok) return false;
+    const float d0 = f_sub(t[0], s[0]), d1 = f_sub(t[1], s[1]);
+    float d2 = f_sub(t[2], s[2]);
+    if (fabs((double)d2) > 0.4) d2 = (float)(d2 > 0.f ? (double)d2 - 0.8 : (double)d2 + 0.8);
+    const float a0 = fabsf(f_sub(t[0], s[0])), a1 = fabsf(f_sub(t[1], s[1]));
+    const float a2r = fabsf(f_sub(t[2], s[2]));
+    const double w2 = fabs((double)a2r - 0.8);
+    const float a2 = (float)((double)a2r < w2 ? (double)a2r : w2);
+    const float dist = f_sqrt(f_add(f_add(f_mul(a0, a0), f_mul(a1, a1)), f_mul(a2, a2)));
+    const int K = __builtin_amdgcn_readfirstlane((int)f_div(dist, 0.015f));
+    for (int base = 1; base < K; base += 64) {
+        const int k = base + lane;
+        int cnt = 0;
+        bool good = true;
+        if (k < K) {
+            const float r = (float)((double)k * 1.0 / (double)K);
+            const float cx = f_add(s[0], f_mul(r, d0)), cy = f_add(s[1], f_mul(r, d1)), cz = f_add(s[2], f_mul(r, d2));
+            double ax, ay, bx, by;
+            stick_ends(cx, cy, cz, ax, ay, bx, by);
+            // the 2-D _edge_fp of the two ends
+            good = maze_valid64(ax, ay) && maze_valid64(bx, by) &&
+                   lane_point_fp64(m, ax, ay, cnt) && lane_point_fp64(m, bx, by, cnt) &&
+                   lane_segment_fp64(m, stk, ax, ay, bx, by, cnt);
+        }
+        const unsigned long long bad = __builtin_amdgcn_ballot_w64(!good);
+        const int first = bad ? __builtin_ctzll(bad) : 63;
+        int sum = lane <= first ? cnt : 0;
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off, 64);
+        checks += __builtin_amdgcn_readfirstlane(sum);
+        if (bad) return false;
+    }
+    return true;
+}
+
 }  // namespace
 
 // diagnostics build (-DGNNMP_MAZE_TRACE, tools/diag/maze_trace.py): cycles per phase of the greedy loop, per problem
@@ -497,26 +586,52 @@ __global__ __launch_bounds__(256) void maze_explore_kernel(MazeParams p) {
 // in the reference, so every operation below is the explicitly rounded float32 one (no fma contraction):
 //   norm(x)     = sqrt(x0*x0 + x1*x1)       (np.linalg.norm: sqrt(dot) / sqrt(add.reduce(x*x)))
 //   interpolate = a + (b - a) * (RRT_EPS / dist), python-float constants weak-cast to float32 (NEP 50)
-// One wavefront per problem; the walk itself is sequential (lane 0), like the reference's.
+// One wavefront per problem; the walk itself is sequential, like the reference's.
 // ---------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ float maze_norm2(float dx, float dy) {
     return f_sqrt(f_add(f_mul(dx, dx), f_mul(dy, dy)));
 }
+// The stick robot's waypoints have three coordinates, and for three elements the two norms of the reference differ:
+//   norm(x, axis=-1) = sqrt(add.reduce(x * x)) = sqrt((x0*x0 + x1*x1) + x2*x2), all float32        (K, maze_norm3_rows)
+//   norm(x)          = sqrt(x.dot(x)), and the float32 dot of a short vector adds the float32 products in a float64
+//                      accumulator and rounds the sum once (OpenBLAS sdot, the loop over the elements past the last
+//                      block of 32).  For two elements that is the float32 sum; for three it is not.     (maze_norm3)
+__device__ __forceinline__ float maze_norm3_rows(float dx, float dy, float dz) {
+    return f_sqrt(f_add(f_add(f_mul(dx, dx), f_mul(dy, dy)), f_mul(dz, dz)));
+}
+__device__ __forceinline__ float maze_norm3(float dx, float dy, float dz) {
+    const double acc = ((double)f_mul(dx, dx) + (double)f_mul(dy, dy)) + (double)f_mul(dz, dz);
+    return f_sqrt((float)acc);
+}
 
+// DIM = 2: the point robot; lane 0 walks (an edge check is one short bisection).
+// DIM = 3: the stick robot (MazeEnv(dim=3)): the walk over waypoints and rounds is the same sequence, carried by all 64 lanes
+// alike (every lane holds the same waypoints and takes the same decisions), and every edge check spreads its interpolated
+// sticks over the lanes (stick_edge_wave).  The candidate is MazeEnv.interpolate (maze_env.py:151-172): displacement
+// wrapped by one period when |dz| > 0.4, old + diff * ratio, result wrapped again; the wraps go through float64 and back
+// (float32 element -= float64 scalar).  Both asserts of interpolate are kept: if one would fire, the problem's status is
+// 1, its out_path is old_path and its checks entry is left alone.  The path is steered in place in out_path: the left
+// neighbour of this round and the waypoint's own old value travel in registers, the right neighbour is read before the
+// step that rewrites it.
+template <int DIM>
 __global__ __launch_bounds__(64) void maze_steer_kernel(MazeSteerParams p) {
     const int b = blockIdx.x, lane = threadIdx.x;
     const int p0 = p.path_ptr[b], P = p.path_ptr[b + 1] - p0;
-    const float* oldp = p.old_path + (size_t)p0 * 2;
-    const float* newp = p.new_path + (size_t)p0 * 2;
-    float* cur = p.out_path + (size_t)p0 * 2;
-    float* nxt = p.tmp + (size_t)p0 * 2;
+    const float* oldp = p.old_path + (size_t)p0 * DIM;
+    const float* newp = p.new_path + (size_t)p0 * DIM;
+    float* cur = p.out_path + (size_t)p0 * DIM;
     // K = int(ceil((norm(old - new, axis=-1) / RRT_EPS).max()))
     float mx = 0.0f;
     for (int i = lane; i < P; i += 64) {
-        const float n = maze_norm2(f_sub(oldp[2 * i], newp[2 * i]), f_sub(oldp[2 * i + 1], newp[2 * i + 1]));
+        float n;
+        if constexpr (DIM == 2)
+            n = maze_norm2(f_sub(oldp[2 * i], newp[2 * i]), f_sub(oldp[2 * i + 1], newp[2 * i + 1]));
+        else
+            n = maze_norm3_rows(f_sub(oldp[3 * i], newp[3 * i]), f_sub(oldp[3 * i + 1], newp[3 * i + 1]),
+                                f_sub(oldp[3 * i + 2], newp[3 * i + 2]));
         mx = fmaxf(mx, f_div(n, 0.05f));
-        cur[2 * i] = oldp[2 * i];
-        cur[2 * i + 1] = oldp[2 * i + 1];
+#pragma unroll
+        for (int c = 0; c < DIM; ++c) cur[DIM * i + c] = oldp[DIM * i + c];
     }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off, 64));
@@ -524,34 +639,93 @@ __global__ __launch_bounds__(64) void maze_steer_kernel(MazeSteerParams p) {
     __shared__ unsigned char occ_lds[kMazeLdsCells];
     MazeCtx m;
     maze_ctx_init(m, p.maps + (size_t)b * p.w * p.w, p.w, occ_lds, lane);      // includes the fence + barrier
-    if (lane != 0 || P < 3) return;
-    for (int r = 0; r < K; ++r) {
-        float diff = 0.0f;
-        nxt[0] = cur[0]; nxt[1] = cur[1];
-        nxt[2 * (P - 1)] = cur[2 * (P - 1)]; nxt[2 * (P - 1) + 1] = cur[2 * (P - 1) + 1];
-        for (int i = 1; i < P - 1; ++i) {
-            const float ox = cur[2 * i], oy = cur[2 * i + 1], tx = newp[2 * i], ty = newp[2 * i + 1];
-            const float dist = maze_norm2(f_sub(ox, tx), f_sub(oy, ty));
-            float cx = tx, cy = ty;
-            if (!(dist < 0.05f)) {
-                const float ratio = f_div(0.05f, dist);
-                cx = f_add(ox, f_mul(f_sub(tx, ox), ratio));
-                cy = f_add(oy, f_mul(f_sub(ty, oy), ratio));
+    if constexpr (DIM == 2) {
+        float* nxt = p.tmp + (size_t)p0 * 2;
+        if (lane != 0 || P < 3) return;
+        for (int r = 0; r < K; ++r) {
+            float diff = 0.0f;
+            nxt[0] = cur[0]; nxt[1] = cur[1];
+            nxt[2 * (P - 1)] = cur[2 * (P - 1)]; nxt[2 * (P - 1) + 1] = cur[2 * (P - 1) + 1];
+            for (int i = 1; i < P - 1; ++i) {
+                const float ox = cur[2 * i], oy = cur[2 * i + 1], tx = newp[2 * i], ty = newp[2 * i + 1];
+                const float dist = maze_norm2(f_sub(ox, tx), f_sub(oy, ty));
+                float cx = tx, cy = ty;
+                if (!(dist < 0.05f)) {
+                    const float ratio = f_div(0.05f, dist);
+                    cx = f_add(ox, f_mul(f_sub(tx, ox), ratio));
+                    cy = f_add(oy, f_mul(f_sub(ty, oy), ratio));
+                }
+                // nxt[i-1] is this round's value, the right neighbour still last round's
+                const bool ok = maze_edge_fp(m, nxt[2 * (i - 1)], nxt[2 * (i - 1) + 1], cx, cy) &&
+                                maze_edge_fp(m, cur[2 * (i + 1)], cur[2 * (i + 1) + 1], cx, cy);
+                if (ok) {
+                    nxt[2 * i] = cx; nxt[2 * i + 1] = cy;
+                    diff = f_add(diff, maze_norm2(f_sub(cx, tx), f_sub(cy, ty)));
+                } else {
+                    nxt[2 * i] = ox; nxt[2 * i + 1] = oy;
+                }
             }
-            // nxt[i-1] is this round's value, the right neighbour still last round's
-            const bool ok = maze_edge_fp(m, nxt[2 * (i - 1)], nxt[2 * (i - 1) + 1], cx, cy) &&
-                            maze_edge_fp(m, cur[2 * (i + 1)], cur[2 * (i + 1) + 1], cx, cy);
-            if (ok) {
-                nxt[2 * i] = cx; nxt[2 * i + 1] = cy;
-                diff = f_add(diff, maze_norm2(f_sub(cx, tx), f_sub(cy, ty)));
-            } else {
-                nxt[2 * i] = ox; nxt[2 * i + 1] = oy;
-            }
+            for (int i = 0; i < 2 * P; ++i) cur[i] = nxt[i];
+            if (diff < 1e-5f) break;
         }
-        for (int i = 0; i < 2 * P; ++i) cur[i] = nxt[i];
-        if (diff < 1e-5f) break;
+        p.checks[b] += m.checks;
+    } else {
+        __shared__ double s_lane_stack[4 * kLaneStackSlots * 64];
+        double* stk = s_lane_stack + lane;
+        long long checks = 0;
+        bool tripped = false;
+        const int rounds = P < 3 ? 0 : __builtin_amdgcn_readfirstlane(K);
+        for (int r = 0; r < rounds && !tripped; ++r) {
+            float diff = 0.0f;
+            float left[3] = {cur[0], cur[1], cur[2]};
+            float own[3] = {cur[3], cur[4], cur[5]};
+            for (int i = 1; i < P - 1; ++i) {
+                const float right[3] = {cur[3 * (i + 1)], cur[3 * (i + 1) + 1], cur[3 * (i + 1) + 2]};      // last round's
+                const float tgt[3] = {newp[3 * i], newp[3 * i + 1], newp[3 * i + 2]};
+                const float dist = maze_norm3(f_sub(own[0], tgt[0]), f_sub(own[1], tgt[1]), f_sub(own[2], tgt[2]));
+                float cand[3] = {tgt[0], tgt[1], tgt[2]};
+                if (!(dist < 0.05f)) {
+                    const float ratio = f_div(0.05f, dist);
+                    const float dx = f_sub(tgt[0], own[0]), dy = f_sub(tgt[1], own[1]);
+                    float dz = f_sub(tgt[2], own[2]);
+                    if (fabs((double)dz) > 0.4) dz = (float)(dz > 0.f ? (double)dz - 0.8 : (double)dz + 0.8);
+                    tripped = !(fabs((double)dz) <= 0.4);
+                    cand[0] = f_add(own[0], f_mul(dx, ratio));
+                    cand[1] = f_add(own[1], f_mul(dy, ratio));
+                    float cz = f_add(own[2], f_mul(dz, ratio));
+                    if (fabs((double)cz) > 0.4) cz = (float)(cz > 0.f ? (double)cz - 0.8 : (double)cz + 0.8);
+                    tripped = tripped || !(fabs((double)cz) <= 0.4);
+                    cand[2] = cz;
+                    tripped = wave_uniform(tripped);
+                    if (tripped) break;
+                }
+                // `left` is this round's value, `right` still last round's
+                bool ok = true;
+#pragma nounroll
+                for (int e = 0; e < 2 && ok; ++e) {
+                    const float from[3] = {e ? right[0] : left[0], e ? right[1] : left[1], e ? right[2] : left[2]};
+                    ok = stick_edge_wave(m, stk, lane, from, cand, checks);
+                }
+                if (ok) diff = f_add(diff, maze_norm3(f_sub(cand[0], tgt[0]), f_sub(cand[1], tgt[1]), f_sub(cand[2], tgt[2])));
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    left[c] = ok ? cand[c] : own[c];
+                    own[c] = right[c];
+                }
+                if (lane == 0) { cur[3 * i] = left[0]; cur[3 * i + 1] = left[1]; cur[3 * i + 2] = left[2]; }
+            }
+            // lane 0's waypoints of this round are read by every lane in the next
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "agent");
+            __builtin_amdgcn_wave_barrier();
+            if (diff < 1e-5f) break;
+        }
+        if (tripped) {
+            for (int i = lane; i < 3 * P; i += 64) cur[i] = oldp[i];
+        } else if (lane == 0) {
+            p.checks[b] += checks;
+        }
+        if (lane == 0) p.status[b] = tripped ? 1 : 0;
     }
-    p.checks[b] += m.checks;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -658,7 +832,8 @@ hipError_t launch_maze_sample(const MazeSampleParams& p, hipStream_t st) {
 
 hipError_t launch_maze_steer(const MazeSteerParams& p, hipStream_t st) {
     if (p.B <= 0) return hipSuccess;
-    hipLaunchKernelGGL(maze_steer_kernel, dim3(p.B), dim3(64), 0, st, p);
+    if (p.dim == 3) hipLaunchKernelGGL(maze_steer_kernel<3>, dim3(p.B), dim3(64), 0, st, p);
+    else hipLaunchKernelGGL(maze_steer_kernel<2>, dim3(p.B), dim3(64), 0, st, p);
     return hipGetLastError();
 }
 

@@ -743,7 +743,6 @@ def explore_maze_batch(problems, model, device, batch=500, k=30, loop=5, model_s
                     torch.from_numpy(optr).to(device), int(ocount.max()))
     scores = model.forward_batch(gb, loop)
     tm = mark('explorer_forward', tm)
-    w = int(np.asarray(problems[0]['map']).shape[0])
     if dsamp is not None:
         maps, goal64 = dsamp['maps'], dsamp['goal64']
     else:
@@ -755,7 +754,7 @@ def explore_maze_batch(problems, model, device, batch=500, k=30, loop=5, model_s
     tm = mark('greedy_explore', tm)
     smoothed = {}
     if model_s is not None and any(success):
-        smoothed = _smooth_maze_batch(model_s, [b for b in range(B) if success[b]], v, nptr, n_free, path, plen, maps, w,
+        smoothed = _smooth_maze_batch(model_s, [b for b in range(B) if success[b]], v, nptr, n_free, path, plen, maps,
                                       smooth_iters, device)
         tm = mark('smoothing', tm)
     out = []
@@ -780,14 +779,48 @@ def explore_maze_batch(problems, model, device, batch=500, k=30, loop=5, model_s
     return out
 
 
-def _smooth_maze_batch(model_s, sel, v, nptr, n_free, path, plen, maps, w, iters, device):
-    """Smoothing stage of the solved problems ``sel`` entirely on the device: per iteration one batched
-    smoother forward (loop = 1) and one ``gnnmp_maze_steer`` launch; one D2H copy at the end.
-    Samples handed to the network: the first 500 free and 500 collided points (smoother.py:52-64)."""
+def steer_maze_batch(old_path, new_path, path_ptr, maps, *, checks=None, status=None, tmp=None):
+    """Collision-checked steering of the smoothing stage (``proposed_path_smootherv2``, smoother.py:194-216) for a ragged
+    batch of paths on the device, one launch on the current stream.  ``old_path`` / ``new_path``: float32 ``[sumP, dim]``
+    (the waypoints and the smoother's proposals), ``path_ptr``: int32 ``[B + 1]``, ``maps``: float64 ``[B, w, w]``; all on the
+    same device.  The width of ``old_path`` picks the kernel: 2 = point robot (``gnnmp_maze_steer``), 3 = stick robot
+    (``gnnmp_stick_steer``).  Returns ``(out_path, checks, status)`` as device tensors: the steered paths, the collision
+    checks spent per problem (int64) and a status word per problem (int32; 0 = ok, 1 = one of the two orientation
+    asserts of the stick robot's ``interpolate`` would have fired -- displacement or interpolated orientation still out of
+    range after one wrap: that problem's path comes back unchanged and its checks entry is not incremented).  A caller that
+    steers repeatedly may pass its own ``checks`` (incremented in place), ``status`` (overwritten) and ``tmp`` (scratch of
+    the paths' shape)."""
     from . import _lib
+    dim = int(old_path.shape[1])
+    if dim not in (2, 3):
+        raise ValueError('steer_maze_batch: waypoints of width 2 or 3, got %d' % dim)
+    B = int(path_ptr.shape[0]) - 1
+    old_path, new_path = old_path.contiguous(), new_path.contiguous()
+    maps = maps.contiguous()
+    out = torch.empty_like(old_path)
+    tmp = torch.empty_like(old_path) if tmp is None else tmp
+    checks = torch.zeros(B, dtype=torch.int64, device=old_path.device) if checks is None else checks
+    status = torch.zeros(B, dtype=torch.int32, device=old_path.device) if status is None else status
+    L = _lib.lib()
+    with torch.cuda.device(old_path.device):
+        st = torch.cuda.current_stream().cuda_stream
+        args = (B, int(old_path.shape[0]), int(maps.shape[1]), maps.data_ptr(), path_ptr.data_ptr(), old_path.data_ptr(),
+                new_path.data_ptr(), out.data_ptr(), tmp.data_ptr(), checks.data_ptr())
+        if dim == 2:
+            _lib.check(L.gnnmp_maze_steer(*args, st), 'gnnmp_maze_steer')
+        else:
+            _lib.check(L.gnnmp_stick_steer(*args, status.data_ptr(), st), 'gnnmp_stick_steer')
+    return out, checks, status
+
+
+def _smooth_maze_batch(model_s, sel, v, nptr, n_free, path, plen, maps, iters, device):
+    """Smoothing stage of the solved problems ``sel`` entirely on the device: per iteration one batched
+    smoother forward (loop = 1) and one steering launch (:func:`steer_maze_batch`; 2-D or stick robot by the width of
+    ``v``); one D2H copy at the end.  Samples handed to the network: the first 500 free and 500 collided points
+    (smoother.py:52-64).  Raises ``RuntimeError`` for a stick-robot proposal the reference's ``interpolate`` asserts on."""
     from .smoother import SmoothBatch
-    total_n = int(v.shape[0])
-    v_ext = torch.cat((v, torch.zeros(1, 2, device=device)))          # row total_n: the reference's zero filler row
+    total_n, dim = int(v.shape[0]), int(v.shape[1])
+    v_ext = torch.cat((v, torch.zeros(1, dim, device=device)))        # row total_n: the reference's zero filler row
     widx, fidx, cidx, pc, fc, cc, ec = [], [], [], [], [], [], []
     for b in sel:
         nb = nptr[b + 1] - nptr[b]
@@ -801,18 +834,18 @@ def _smooth_maze_batch(model_s, sel, v, nptr, n_free, path, plen, maps, w, iters
                                  pc, fc, cc, ec)
     maps_sel = maps[torch.tensor(sel, device=device)].contiguous()
     checks = torch.zeros(len(sel), dtype=torch.int64, device=device)
+    status = torch.zeros(max(iters, 1), len(sel), dtype=torch.int32, device=device)      # one row per iteration
     tmp = torch.empty_like(sb.path)
-    L = _lib.lib()
     with torch.cuda.device(device):
-        st = torch.cuda.current_stream().cuda_stream
-        for _ in range(iters):
+        for it in range(iters):
             new = model_s.forward_batch(sb, 1)
-            out = torch.empty_like(sb.path)
-            _lib.check(L.gnnmp_maze_steer(len(sel), int(sb.path.shape[0]), w, maps_sel.data_ptr(), sb.path_ptr.data_ptr(),
-                                          sb.path.data_ptr(), new.data_ptr(), out.data_ptr(), tmp.data_ptr(),
-                                          checks.data_ptr(), st), 'gnnmp_maze_steer')
-            sb.path = out
-    final, checks = sb.path.cpu().numpy(), checks.cpu().tolist()
+            sb.path = steer_maze_batch(sb.path, new, sb.path_ptr, maps_sel, checks=checks, status=status[it], tmp=tmp)[0]
+    # the counts and the status words come back in one copy beside the waypoints'
+    final = sb.path.cpu().numpy()
+    checks, status = torch.stack((checks, status.amax(0).to(torch.int64))).cpu().tolist()
+    if any(status):
+        raise RuntimeError('smoothing: MazeEnv.interpolate asserts on a proposal of problem(s) %s (orientation more than 1.2 '
+                           'from its waypoint, or still outside +-0.4 after one wrap)' % [b for b, s in zip(sel, status) if s])
     res, o = {}, 0
     for i, b in enumerate(sel):
         res[b] = (final[o:o + plen[b]], int(checks[i]))
@@ -868,11 +901,14 @@ def _device_round(states, model, device, k, loop, fresh):
 
 
 def eval_gnn_device_rounds(env, indexes, model, model_s=None, seed=1234, batch=500, t_max=500, k=30, device='cuda', loop=5,
-                           chunk=64, rows_out=None):
+                           chunk=64, rows_out=None, details_out=None):
     """:func:`eval_gnn` (eval_gnn.py:96-145) with the planner on the device for the GENERAL loop of ``explore``
     (eval_gnn.py:191-247): when the frontier dies the problem gets ``batch`` more samples, the explorer runs again on
     the larger graph and the search tree carries over -- up to ``t_max`` free samples -- for ``Maze2D`` and ``Maze3D``
-    environments (``model_s`` = None: the reference's smoother='none' branch, as maze3 has no shipped smoother).
+    environments.  ``model_s`` = None is the reference's smoother='none' branch; with a smoother the solved problems of
+    either environment go through the smoothing stage on the device (maze3 has no shipped smoother checkpoint: a
+    ``ModelSmoother`` with ``config_size=3`` trained here serves), and a stick-robot proposal the reference's
+    ``interpolate`` asserts on raises ``RuntimeError``.
 
     The reference draws every sample from ONE global numpy stream, problem after problem, and a problem that needs a
     second round draws it before the next problem's first.  Batched rounds keep that order by speculation: a chunk of
@@ -880,7 +916,10 @@ def eval_gnn_device_rounds(env, indexes, model, model_s=None, seed=1234, batch=5
     the stream position right after ITS first sampling, finished on its own (device rounds with the tree carried over),
     and the problems behind it -- whose samples came from the wrong stream position -- are sampled and explored again
     from the position the sequential loop would have reached.  Per-problem outcomes therefore equal the one-by-one loop's
-    (tests/test_planner_rounds_gpu.py against rows recorded from the unmodified reference)."""
+    (tests/test_planner_rounds_gpu.py against rows recorded from the unmodified reference).
+
+    ``rows_out`` receives one row of figures per problem, ``details_out`` one dict per problem: ``success``, ``env``,
+    ``v`` (float32 node rows, free ones first), ``n_free``, ``path``, ``smooth_path`` and ``c_smooth``."""
     model.eval()                       # eval_gnn.py:109-110
     if model_s is not None:
         model_s.eval()
@@ -932,7 +971,7 @@ def eval_gnn_device_rounds(env, indexes, model, model_s=None, seed=1234, batch=5
         todo = todo[done:]
     out = [results[i] for i in indexes]
     smoothed = {}
-    if model_s is not None and dim == 2:
+    if model_s is not None:
         sel = [b for b, st in enumerate(out) if st['success']]
         if sel:
             vcat = torch.cat([torch.from_numpy(st['v']) for st in out]).to(device)
@@ -942,7 +981,7 @@ def eval_gnn_device_rounds(env, indexes, model, model_s=None, seed=1234, batch=5
                 path[nptr[b]:nptr[b] + len(st['path_nodes'])] = st['path_nodes']
             maps = torch.tensor(np.asarray([np.asarray(st['env'].map, dtype=np.float64) for st in out])).to(device)
             smoothed = _smooth_maze_batch(model_s, sel, vcat, nptr, [len(st['free']) for st in out], path,
-                                          [len(st['path_nodes']) for st in out], maps, int(maps.shape[1]), 5, device)
+                                          [len(st['path_nodes']) for st in out], maps, 5, device)
     sol = []
     for b, st in enumerate(out):
         p = st['v'][st['path_nodes']] if st['success'] else np.zeros((0, dim), dtype=np.float32)
@@ -951,6 +990,9 @@ def eval_gnn_device_rounds(env, indexes, model, model_s=None, seed=1234, batch=5
         sol.append((int(st['success']), path_cost(p), path_cost(sp), c_explore, cs, len(p), len(st['explored']), st['rounds']))
         if rows_out is not None:
             rows_out.append(sol[-1][:7])
+        if details_out is not None:
+            details_out.append({'success': st['success'], 'env': st['env'], 'v': st['v'], 'n_free': len(st['free']),
+                                'path': p, 'smooth_path': sp, 'c_smooth': cs})
     n_success = sum(s[0] for s in sol)
     return {'n_success': n_success, 'collision_explore': float(np.mean([s[3] for s in sol])),
             'collision': float(np.mean([s[3] + s[4] for s in sol])),

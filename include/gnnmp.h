@@ -20,7 +20,7 @@
  *       create_data's edge construction                       eval_gnn.py:159-164
  *   gnnmp_maze_sample
  *       explore()'s rejection sampling (classification + compaction)   eval_gnn.py:180-184, environment/maze_env.py
- *   gnnmp_maze_steer
+ *   gnnmp_maze_steer / gnnmp_stick_steer
  *       proposed_path_smootherv2 (steering of the smoothing stage)  smoother.py:194-216
  *   gnnmp_maze_explore_workspace_bytes / gnnmp_maze_explore / gnnmp_maze_explore_ex
  *       explore()'s greedy loop + MazeEnv._edge_fp            eval_gnn.py:198-233, environment/maze_env.py:270-326
@@ -449,6 +449,19 @@ int gnnmp_maze_explore_ex(const gnnmp_maze_batch* batch, int32_t dim, const gnnm
 int gnnmp_maze_steer(int32_t n_problems, int32_t total_path, int32_t width, const double* maps, const int32_t* path_ptr,
                      const float* old_path, const float* new_path, float* out_path, float* tmp, int64_t* checks,
                      void* hip_stream);
+
+/* The same steering for the 3-DoF stick robot, MazeEnv(dim=3): waypoints are float32 [.,3]; the candidate of a waypoint is
+ * MazeEnv.interpolate (maze_env.py:151-172, orientation wrapped across +-0.4), every edge check is the stick's
+ * (maze_env.py:316-347).  The contract is gnnmp_maze_steer's (device pointers, out_path may NOT alias old_path / new_path,
+ * checks INCREMENTED, one launch on the stream); tmp [total_path, 3] float32 must be given like the 2-D entry's, but the
+ * stick kernel steers in place in out_path and never touches it.  Plus status [B] (int32), written for every problem:
+ * 0 = steered; 1 = one of the two asserts of the reference's interpolate would have fired, where the reference raises: the
+ * displacement's orientation still exceeds 0.4 after one wrap (a proposal more than 1.2 in orientation from its waypoint),
+ * or the interpolated orientation still lies outside +-0.4 after one wrap (for example a waypoint whose own orientation is
+ * out of range).  That problem's out_path is its old_path and its checks entry is left as it was. */
+int gnnmp_stick_steer(int32_t n_problems, int32_t total_path, int32_t width, const double* maps, const int32_t* path_ptr,
+                      const float* old_path, const float* new_path, float* out_path, float* tmp, int64_t* checks,
+                      int32_t* status, void* hip_stream);
 
 /* Rejection sampling of the explore stage for 2-D mazes (eval_gnn.py:180-184 through MazeEnv.sample_n_points / uniform_sample,
  * environment/maze_env.py): the raw draws stay with the host's numpy generator (`attempts` is the stream of uniform(-1, 1) pairs in
