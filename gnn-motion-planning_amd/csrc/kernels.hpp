@@ -201,8 +201,11 @@ struct MazeSampleParams {
     int* used;                            // out [B]: attempts consumed (= collision checks of the sampling)
     long long* cursor;                    // in / out: index of the next unconsumed attempt
     int* ok;                              // out: 0 = the stream ran out before the last problem had its n free samples
+    long long* checks = nullptr;          // stick robot only, out [B]: collision checks of the draws consumed (0 .. 9 per draw)
 };
 hipError_t launch_maze_sample(const MazeSampleParams& p, hipStream_t st);
+// the stick robot's (MazeEnv(dim=3)): attempts [M, 3], init / goal states [B, 3], node rows of width 3, checks required
+hipError_t launch_stick_sample(const MazeSampleParams& p, hipStream_t st);
 
 // ---- supervision of the explorer's training step (train_episode_kernels.hip, train_explorer.py:124-176)
 struct EpLabelParams {                    // (a) edge_free / edge_cost of construct_graph for maze problems

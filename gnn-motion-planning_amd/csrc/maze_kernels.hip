@@ -149,6 +149,13 @@ __device__ __forceinline__ void stick_ends(float x, float y, float z, double& ax
     ax = (double)x - ox; ay = (double)y - oy;
     bx = (double)x + ox; by = (double)y + oy;
 }
+// the same for a float64 configuration (the raw draws of the sampler: nothing passes through float32)
+__device__ __forceinline__ void stick_ends(double x, double y, double z, double& ax, double& ay, double& bx, double& by) {
+    const double theta = z / 0.4 * 3.141592653589793;
+    const double ox = 0.1 * cos(theta), oy = 0.1 * sin(theta);
+    ax = x - ox; ay = y - oy;
+    bx = x + ox; by = y + oy;
+}
 __device__ bool stick_state_fp(MazeCtx& m, float x, float y, float z) {        // _stick_in_free_space
     if (!maze_valid3(x, y, z)) return false;
     double ax, ay, bx, by;
@@ -824,9 +831,159 @@ __global__ __launch_bounds__(1024) void maze_sample_kernel(MazeSampleParams p) {
     if (tid == 0) { *p.cursor = cur; *p.ok = 1; }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// The same for the 3-DoF stick robot (MazeEnv(dim=3)): a draw is a configuration (x, y, z) of [-1, 1)^2 x [-0.4, 0.4) and its
+// classification is _stick_in_free_space on the float64 draw (maze_env.py:279-291): end a, end b, then the bisection between
+// them, every in-bounds point query one collision check, evaluation stopping at the first blocked query.  The stick is 0.2
+// long, so its ends are at most 0.2 * sqrt(2) = 0.283 apart in L1; a segment splits only while that exceeds RRT_EPS = 0.05 and
+// it halves per level (0.141, 0.071, 0.035): a fourth level never opens, at any map width.  The walk is therefore three fixed
+// levels in registers -- midpoints in the order M, L, LL, LR, R, RL, RR, at most 2 + 7 = 9 checks per draw -- with no stack.
+// The structure is maze_sample_kernel's; the scan carries one more quantity, the check counts, because a problem's count is
+// the sum over the draws it CONSUMED (up to and including its n-th free one), not over the 1024-draw step they sat in.
+// ---------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ bool seg_splits(int w, double lx, double ly, double rx, double ry) {
+    const int dc = abs(maze_cell64(lx, w) - maze_cell64(rx, w)) + abs(maze_cell64(ly, w) - maze_cell64(ry, w));
+    const double l1 = fabs(lx - rx) + fabs(ly - ry);
+    return dc > 1 && l1 > 0.05;
+}
+// level 2 (a quarter of the stick): its halves are shorter than RRT_EPS and never split
+__device__ __forceinline__ bool stick_seg2(const MazeCtx& m, double lx, double ly, double rx, double ry, int& cnt) {
+    if (!seg_splits(m.w, lx, ly, rx, ry)) return true;
+    return lane_point_fp64(m, (lx + rx) / 2.0, (ly + ry) / 2.0, cnt);
+}
+__device__ __forceinline__ bool stick_seg1(const MazeCtx& m, double lx, double ly, double rx, double ry, int& cnt) {
+    if (!seg_splits(m.w, lx, ly, rx, ry)) return true;
+    const double mx = (lx + rx) / 2.0, my = (ly + ry) / 2.0;
+    if (!lane_point_fp64(m, mx, my, cnt)) return false;
+    return stick_seg2(m, lx, ly, mx, my, cnt) && stick_seg2(m, mx, my, rx, ry, cnt);
+}
+// _stick_in_free_space of a float64 configuration; cnt receives the collision checks it spends (0 .. 9)
+__device__ __forceinline__ bool stick_draw_fp64(const MazeCtx& m, double x, double y, double z, int& cnt) {
+    if (!maze_valid64(x, y) || !(z >= -0.4 && z <= 0.4)) return false;
+    double ax, ay, bx, by;
+    stick_ends(x, y, z, ax, ay, bx, by);
+    if (!lane_point_fp64(m, ax, ay, cnt) || !lane_point_fp64(m, bx, by, cnt)) return false;
+    if (!seg_splits(m.w, ax, ay, bx, by)) return true;
+    const double mx = (ax + bx) / 2.0, my = (ay + by) / 2.0;
+    if (!lane_point_fp64(m, mx, my, cnt)) return false;
+    return stick_seg1(m, ax, ay, mx, my, cnt) && stick_seg1(m, mx, my, bx, by, cnt);
+}
+
+__global__ __launch_bounds__(1024) void stick_sample_kernel(MazeSampleParams p) {
+    __shared__ unsigned char occ[kMazeLdsCells];
+    __shared__ int wsum[16], csum[16];
+    __shared__ int s_tstar, s_cstar;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long long cur0 = *p.cursor;
+    long long cur = cur0;
+    int node0 = 0;
+    const bool in_lds = p.w * p.w <= kMazeLdsCells;
+    if (tid == 0) p.node_ptr[0] = 0;
+    for (int b = 0; b < p.B; ++b) {
+        const double* map = p.maps + (size_t)b * p.w * p.w;
+        __syncthreads();                                        // the previous problem's map is no longer in use
+        if (in_lds)
+            for (int i = tid; i < p.w * p.w; i += 1024) occ[i] = map[i] == 0.0 ? 0 : 1;
+        if (tid == 0) s_tstar = -1;
+        __syncthreads();
+        MazeCtx m;
+        m.map = map; m.occ = in_lds ? occ : nullptr; m.w = p.w; m.checks = 0; m.stack = nullptr;
+        int free_before = 0, rej_before = 0, rej_total = 0, used = 0;
+        long long checks = 0;
+        for (long long off = 0;; off += 1024) {
+            const long long idx = cur + off + tid;
+            const bool in = idx < p.M;
+            double x = 0.0, y = 0.0, z = 0.0;
+            int cnt = 0;
+            bool isfree = false;
+            if (in) {
+                x = p.attempts[3 * idx]; y = p.attempts[3 * idx + 1]; z = p.attempts[3 * idx + 2];
+                isfree = stick_draw_fp64(m, x, y, z, cnt);
+            }
+            // inclusive block scans of the free flags (ballot + popcount) and of the check counts (shuffles) inside a wave,
+            // the sixteen wave totals of each through LDS
+            const unsigned long long bal = __builtin_amdgcn_ballot_w64(isfree);
+            const int incl_w = __builtin_popcountll(bal & (~0ull >> (63 - lane)));
+            int cincl_w = cnt;
+#pragma unroll
+            for (int d = 1; d < 64; d <<= 1) {
+                const int up = __shfl_up(cincl_w, d, 64);
+                if (lane >= d) cincl_w += up;
+            }
+            if (lane == 0) wsum[wave] = __builtin_popcountll(bal);
+            if (lane == 63) csum[wave] = cincl_w;
+            __syncthreads();
+            int before = 0, F = 0, cbefore = 0, C = 0;
+#pragma unroll
+            for (int w2 = 0; w2 < 16; ++w2) {
+                const int f = wsum[w2], c = csum[w2];
+                before += w2 < wave ? f : 0; F += f;
+                cbefore += w2 < wave ? c : 0; C += c;
+            }
+            const int incl = before + incl_w;                   // free draws among this step's draws 0 .. tid
+            if (isfree && free_before + incl == p.n) {          // the n-th free draw of the problem
+                s_tstar = tid;
+                s_cstar = cbefore + cincl_w;                    // checks of this step's draws 0 .. tid
+            }
+            __syncthreads();
+            const int tstar = s_tstar;
+            const bool done = tstar >= 0;
+            const int limit = done ? tstar : 1023;
+            if (in && tid <= limit) {
+                if (isfree) {
+                    const size_t row = (size_t)node0 + 2 + free_before + incl - 1;
+                    p.v[3 * row] = (float)x; p.v[3 * row + 1] = (float)y; p.v[3 * row + 2] = (float)z;
+                } else {
+                    const int rr = rej_before + (tid + 1 - incl) - 1;        // rank among the problem's rejected draws
+                    if (rr < p.n) {
+                        const size_t row = (size_t)node0 + 2 + p.n + rr;
+                        p.v[3 * row] = (float)x; p.v[3 * row + 1] = (float)y; p.v[3 * row + 2] = (float)z;
+                    }
+                }
+            }
+            if (done) {
+                // every thread derives the same totals: rejected draws and checks up to and including position tstar
+                const int free_upto = p.n - free_before;                     // free draws of this step up to tstar
+                rej_total = rej_before + (tstar + 1 - free_upto);
+                used = (int)off + tstar + 1;
+                checks += s_cstar;
+                break;
+            }
+            if (cur + off + 1024 >= p.M) {                      // the stream ran out (workgroup-uniform)
+                if (tid == 0) { *p.ok = 0; *p.cursor = cur0; p.node_ptr[b + 1] = -1; }      // nothing is consumed
+                return;
+            }
+            free_before += F;
+            rej_before += 1024 - F;
+            checks += C;
+            __syncthreads();                                    // wsum / csum / s_tstar are rewritten by the next step
+        }
+        const int Nb = 2 + p.n + (rej_total < p.n ? rej_total : p.n);
+        if (tid == 0) {
+            const double* is = p.init_states + 3 * (size_t)b;
+            const double* gs = p.goal_states + 3 * (size_t)b;
+            float* r0 = p.v + 3 * (size_t)node0;
+            r0[0] = (float)is[0]; r0[1] = (float)is[1]; r0[2] = (float)is[2];
+            r0[3] = (float)gs[0]; r0[4] = (float)gs[1]; r0[5] = (float)gs[2];
+            p.node_ptr[b + 1] = node0 + Nb;
+            p.used[b] = used;
+            p.checks[b] = checks;
+        }
+        cur += used;
+        node0 += Nb;
+    }
+    if (tid == 0) { *p.cursor = cur; *p.ok = 1; }
+}
+
 hipError_t launch_maze_sample(const MazeSampleParams& p, hipStream_t st) {
     if (p.B <= 0) return hipSuccess;
     hipLaunchKernelGGL(maze_sample_kernel, dim3(1), dim3(1024), 0, st, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_stick_sample(const MazeSampleParams& p, hipStream_t st) {
+    if (p.B <= 0) return hipSuccess;
+    hipLaunchKernelGGL(stick_sample_kernel, dim3(1), dim3(1024), 0, st, p);
     return hipGetLastError();
 }
 

@@ -28,17 +28,21 @@ class AttemptStream:
     start, advance by the attempts actually consumed).  Saves the per-problem get_state / set_state round trips
     (~0.2 ms each) of :meth:`Maze2D.sample_n_points_arrays`."""
 
-    def __init__(self, block=1 << 15):
+    def __init__(self, block=1 << 15, limits=None):
+        """``limits``: half-widths of the sampled box, one per coordinate of a draw -- ``LIMITS`` (two columns, the default)
+        for the point robot, ``LIMITS3`` (three) for the stick robot, whose ``uniform_sample`` draws three doubles at a time."""
         self._state0 = np.random.get_state()
         self._block = block
-        self._buf = np.zeros((0, 2))
+        self._limits = LIMITS if limits is None else np.asarray(limits, dtype=np.float64)
+        self.width = int(self._limits.shape[0])
+        self._buf = np.zeros((0, self.width))
         self._pos = 0
         self.consumed = 0
 
     def peek(self, m):
-        """The next m attempts [m, 2] (not yet consumed)."""
+        """The next m attempts [m, width] (not yet consumed)."""
         while self._buf.shape[0] - self._pos < m:
-            fresh = np.random.uniform(-LIMITS, LIMITS, (max(self._block, m), 2))
+            fresh = np.random.uniform(-self._limits, self._limits, (max(self._block, m), self.width))
             self._buf = np.concatenate((self._buf[self._pos:], fresh))
             self._pos = 0
         return self._buf[self._pos:self._pos + m]
@@ -50,14 +54,15 @@ class AttemptStream:
     def close(self):
         np.random.set_state(self._state0)
         left = self.consumed
-        while left > 0:                                       # two doubles per attempt, same order as the draws above
+        while left > 0:                                       # `width` doubles per attempt, same order as the draws above
             step = min(left, 1 << 20)
-            np.random.uniform(-LIMITS, LIMITS, (step, 2))
+            np.random.uniform(-self._limits, self._limits, (step, self.width))
             left -= step
 
 
 class Maze2D:
     RRT_EPS = RRT_EPS
+    SAMPLE_LIMITS = LIMITS                  # the box uniform_sample draws from (an AttemptStream's ``limits``)
 
     def __init__(self, maps, init_states, goal_states):
         self.dim = 2
@@ -219,6 +224,8 @@ LIMITS3 = np.array([1., 1., 8. * RRT_EPS])   # environment/env_config.py:5
 
 
 class Maze3D(Maze2D):
+    SAMPLE_LIMITS = LIMITS3
+
     def __init__(self, maps, init_states, goal_states):
         super().__init__(maps, init_states, goal_states)
         self.dim = 3
@@ -236,8 +243,72 @@ class Maze3D(Maze2D):
         free, rej = self.sample_n_points(n, need_negative=True)
         return np.array(free).reshape(-1, 3), np.array(rej).reshape(-1, 3)
 
+    def classify_draws(self, pts):
+        """:meth:`_state_fp` of every row of ``pts`` [m, 3] float64 at once: (free [m] bool, checks [m] int64), the flag and the
+        growth of ``collision_check_count`` one call per row would give (the counter itself is left alone).  Same float64
+        operations in the same short-circuit order -- end a, end b, then the bisection's midpoints, left half before right
+        half, nothing after the first blocked query -- with a mask per query instead of a branch.  A stick is STICK_LENGTH
+        = 0.2 long, so its ends are at most 0.283 apart in L1 and the bisection (split while that exceeds RRT_EPS, halving per
+        level: 0.141, 0.071, 0.035) has at most three levels: seven midpoints M, L, LL, LR, R, RL, RR, nine checks a draw."""
+        pts = np.asarray(pts, dtype=np.float64).reshape(-1, 3)
+        w, grid = self.width, self.map
+        checks = np.zeros(pts.shape[0], dtype=np.int64)
+
+        def cells(p):
+            c = ((p + 1.0) * w / 2.0).astype(int)
+            c[c > w - 1] = w - 1
+            return c
+
+        def query(p, asked):                                  # _point_fp of the rows in `asked`; False elsewhere
+            inside = asked & (p >= -1.0).all(axis=1) & (p <= 1.0).all(axis=1)
+            checks[inside] += 1
+            c = np.clip(cells(p), 0, w - 1)                   # (rows outside the bounds are masked: any valid index serves)
+            return inside & (grid[c[:, 0], c[:, 1]] == 0)
+
+        def splits(l, r):                                     # the condition of _segment_fp
+            cl, cr = cells(l), cells(r)
+            far = np.abs(cl[:, 0] - cr[:, 0]) + np.abs(cl[:, 1] - cr[:, 1]) > 1
+            return far & (np.abs(l[:, 0] - r[:, 0]) + np.abs(l[:, 1] - r[:, 1]) > RRT_EPS)
+
+        def halve(l, r, parent, alive):
+            """Midpoint query of the segments that `parent` opened and that split; -> (midpoint, opened, still alive)."""
+            opened = alive & parent & splits(l, r)
+            mid = (l + r) / 2.0
+            return mid, opened, alive & (query(mid, opened) | ~opened)
+
+        theta = pts[:, 2] / LIMITS3[2] * np.pi
+        half = STICK_LENGTH / 2. * np.stack((np.cos(theta), np.sin(theta)), axis=1)
+        a, b = pts[:, :2] - half, pts[:, :2] + half
+        alive = (pts >= -LIMITS3).all(axis=1) & (pts <= LIMITS3).all(axis=1)
+        alive = query(a, alive)
+        alive = query(b, alive)
+        m, s_m, alive = halve(a, b, alive, alive)
+        ml, s_l, alive = halve(a, m, s_m, alive)
+        alive = halve(a, ml, s_l, alive)[2]
+        alive = halve(ml, m, s_l, alive)[2]
+        mr, s_r, alive = halve(m, b, s_m, alive)
+        alive = halve(m, mr, s_r, alive)[2]
+        alive = halve(mr, b, s_r, alive)[2]
+        return alive, checks
+
     def sample_n_points_stream(self, stream, n):
-        raise NotImplementedError('the look-ahead sampler is 2-D only; Maze3D samples one configuration at a time')
+        """:meth:`sample_n_points` (``need_negative=True``) on an :class:`AttemptStream` of three-column draws shared by
+        consecutive problems: the peeked block is classified at once (:meth:`classify_draws`); same free and rejected draws,
+        same ``collision_check_count`` and, after ``stream.close()``, same global generator state as the one-by-one loop.
+        Returns (free [n, 3], rejected [m, 3]) float64."""
+        m = max(8 * n, 64)                                    # 5 .. 10 draws per free configuration on the shipped mazes
+        while True:
+            pts = stream.peek(m)
+            free_mask, checks = self.classify_draws(pts)
+            idx = np.flatnonzero(free_mask)
+            if idx.size >= n:
+                used = int(idx[n - 1]) + 1
+                break
+            m *= 2
+        pts, free_mask = pts[:used], free_mask[:used]
+        stream.consume(used)
+        self.collision_check_count += int(checks[:used].sum())
+        return pts[free_mask], pts[~free_mask]
 
     # The orientation coordinate lives on a circle of circumference ORIENT_PERIOD = 2 * LIMITS3[2] (a numpy float64 scalar:
     # under NEP 50 it promotes float32 operands to float64 before the result is stored back into the float32 row, which

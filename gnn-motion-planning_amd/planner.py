@@ -365,21 +365,36 @@ _COST_ACC = np.asarray(sum([np.float32(1.0)])).dtype
 def _collect(res, wall, t_explore, sol, paths, smooth_paths, rows_out):
     for r in res:
         paths.append(r['path'] if r['success'] else [])
-        smooth_paths.append(r['smooth_path'] if r['success'] else [])
-        sol.append((r['success'], _path_cost_rows(paths[-1]), _path_cost_rows(smooth_paths[-1]), r['c_explore'], r['c_smooth'],
-                    wall, t_explore))
+        # without a smoother (the reference's smoother='none' branch, eval_gnn.py): smooth_path = path, c_smooth = 0
+        smooth_paths.append(r.get('smooth_path', r['path']) if r['success'] else [])
+        sol.append((r['success'], _path_cost_rows(paths[-1]), _path_cost_rows(smooth_paths[-1]), r['c_explore'],
+                    r.get('c_smooth', 0), wall, t_explore))
         if rows_out is not None:
             rows_out.append(sol[-1][:5] + (len(paths[-1]), len(r['explored'])))
+
+
+def _maze_class(dim):
+    """Host environment of a maze problem by the width of its configurations: 2 = point robot, 3 = stick robot."""
+    from .maze2d import Maze2D, Maze3D
+    if int(dim) not in (2, 3):
+        raise ValueError('maze problems have configurations of width 2 or 3, got %d' % dim)
+    return Maze3D if int(dim) == 3 else Maze2D
+
+
+def _problems_dim(problems):
+    return int(np.asarray(problems[0]['init_state']).size)
 
 
 def skip_maze_sampling(env, indexes, batch=500):
     """Advance the global numpy RNG exactly as the planner's sampling of the problems ``indexes`` would (nothing
     else in the default single-forward planner draws random numbers): lets rank r of a sharded evaluation start its
-    block at the stream position the sequential reference loop would have reached (0.07 ms per skipped problem)."""
-    from .maze2d import AttemptStream, Maze2D
-    stream = AttemptStream()
+    block at the stream position the sequential reference loop would have reached (0.07 ms per skipped problem of the point
+    robot; the stick robot's vectorised classification, ``Maze3D.sample_n_points_stream``, costs more)."""
+    from .maze2d import AttemptStream
+    cls = _maze_class(env.config_dim)
+    stream = AttemptStream(limits=cls.SAMPLE_LIMITS)
     for i in indexes:
-        e = Maze2D(np.asarray(env.maps[i])[None], np.asarray(env.init_states[i])[None], np.asarray(env.goal_states[i])[None])
+        e = cls(np.asarray(env.maps[i])[None], np.asarray(env.init_states[i])[None], np.asarray(env.goal_states[i])[None])
         e.init_new_problem(0)
         e.sample_n_points_stream(stream, batch)
     stream.close()
@@ -416,10 +431,11 @@ def _worker_stream(dev, i):
 
 def eval_gnn_device(env, indexes, model, model_s, seed=1234, batch=500, k=30, device='cuda', loop=5, chunk=128,
                     rows_out=None, shard=None, workers=2, device_sampling=True):
-    """:func:`eval_gnn` for 2-D maze environments with the planner itself on the device
+    """:func:`eval_gnn` for maze environments (``Maze2D`` or the stick robot's ``Maze3D``) with the planner itself on the device
     (:func:`explore_maze_batch`, ``chunk`` problems per device pass): same return tuple as ``eval_gnn``
     (eval_gnn.py:96-145), same per-problem decisions and collision-check counts as the one-by-one loop at the
-    reference's default configuration (smoothing on, batch == t_max: one explorer forward per problem).
+    reference's default configuration (smoothing on, batch == t_max: one explorer forward per problem).  ``model_s`` = None
+    is the reference's smoother='none' branch: the smoothed path is the path and no smoothing checks are spent.
     The time entries are the batch wall time spread evenly over the problems of a chunk.  ``rows_out``: optional
     list that receives one (success, path cost, smoothed cost, c_explore, c_smooth, path length, explored) per problem.
     ``shard = (rank, world)``: evaluate only this rank's contiguous block of ``indexes`` (``dist.shard_range``) after
@@ -459,8 +475,8 @@ def eval_gnn_device(env, indexes, model, model_s, seed=1234, batch=500, k=30, de
         pr = [dict(map=env.maps[i], init_state=env.init_states[i], goal_state=env.goal_states[i])
               for i in indexes[span[0]:span[1]]]
         # device_sampling: only the uniform draws come from the host (numpy's global generator, this one thread); classification,
-        # n-th-free search and the node rows are the device's (gnnmp_maze_sample) -- same samples, same check counts, same stream
-        # position afterwards as the host sampler (tests/test_maze_sample_gpu.py)
+        # n-th-free search and the node rows are the device's (gnnmp_maze_sample / gnnmp_stick_sample) -- same samples, same check
+        # counts, same stream position afterwards as the host sampler (tests/test_maze_sample_gpu.py, test_stick_sample_gpu.py)
         return pr, (sample_maze_problems_device(pr, batch, k, dev) if device_sampling else sample_maze_problems(pr, batch, k))
 
     # INVARIANT: one stream -- and with it one workspace of each module (EncoderProcessDecoder / ModelSmoother._workspace key
@@ -552,19 +568,22 @@ def eval_gnn_device(env, indexes, model, model_s, seed=1234, batch=500, k=30, de
 def sample_maze_problems(problems, batch, k):
     """Host part of :func:`explore_maze_batch`: the reference's rejection sampling for every problem in order
     (``explore``: eval_gnn.py:180-184), consuming the global numpy RNG exactly like the one-by-one loop.  Returns
-    (envs, node rows per problem [free incl. init / goal; collided], n_free, k1)."""
+    (envs, node rows per problem [free incl. init / goal; collided], n_free, k1).  Point-robot or stick-robot problems, by the
+    width of ``init_state``."""
     from .graph_build import k1_of
-    from .maze2d import AttemptStream, Maze2D
+    from .maze2d import AttemptStream
     envs, vs, n_free, k1s = [], [], [], []
-    stream = AttemptStream()
+    dim = _problems_dim(problems) if problems else 2
+    cls = _maze_class(dim)
+    stream = AttemptStream(limits=cls.SAMPLE_LIMITS)
     for pr in problems:
-        env = Maze2D(np.asarray(pr['map'])[None], np.asarray(pr['init_state'])[None], np.asarray(pr['goal_state'])[None])
+        env = cls(np.asarray(pr['map'])[None], np.asarray(pr['init_state'])[None], np.asarray(pr['goal_state'])[None])
         env.init_new_problem(0)
         free, coll = env.sample_n_points_stream(stream, batch)                # same stream as sample_n_points
         coll = coll[:len(free)]                                               # eval_gnn.py:182 (before init / goal join)
         nf = len(free) + 2
-        vrows = np.concatenate((np.asarray(env.init_state, dtype=np.float64).reshape(1, 2),
-                                np.asarray(env.goal_state, dtype=np.float64).reshape(1, 2), free, coll)).astype(np.float32)
+        vrows = np.concatenate((np.asarray(env.init_state, dtype=np.float64).reshape(1, dim),
+                                np.asarray(env.goal_state, dtype=np.float64).reshape(1, dim), free, coll)).astype(np.float32)
         envs.append(env)
         vs.append(torch.from_numpy(vrows))
         n_free.append(nf)
@@ -574,7 +593,9 @@ def sample_maze_problems(problems, batch, k):
 
 
 
-_DRAWS_PER_FREE = [3.0]          # running estimate of uniform draws per free sample (sizes the block handed to the device)
+# running estimates of uniform draws per free sample (they size the block handed to the device): [point robot, stick robot].
+# A stick needs both ends and the cells between them free: 5 .. 10 draws per free configuration on the shipped maze3 problems.
+_DRAWS_PER_FREE = [3.0, 8.0]
 
 
 def sample_maze_problems_device(problems, batch, k, device):
@@ -584,48 +605,58 @@ def sample_maze_problems_device(problems, batch, k, device):
     device classifies every draw, finds each problem's ``batch``-th free draw in stream order and writes the float32 node
     rows [start, goal, free ..., rejected[:batch] ...] (eval_gnn.py:180-184) where the graph builder reads them.  The global
     generator is left where one-by-one sampling would have left it.  Returns a dict for ``explore_maze_batch(presampled=...)``:
-    the node rows never visit the host on their way to the explorer."""
+    the node rows never visit the host on their way to the explorer.  Stick-robot problems (``init_state`` of width 3) go through
+    ``gnnmp_stick_sample``: three-column draws, rows of width 3, and a draw costs 0 .. 9 collision checks instead of one, so
+    the device's per-problem check counts, not the draw counts, go into each env's ``collision_check_count``."""
     import ctypes
     from . import _lib
     from .graph_build import k1_of
-    from .maze2d import AttemptStream, Maze2D
+    from .maze2d import AttemptStream
     B = len(problems)
     dev = torch.device(device)
+    dim = _problems_dim(problems)
+    cls = _maze_class(dim)
     envs = []
     for pr in problems:
-        env = Maze2D(np.asarray(pr['map'])[None], np.asarray(pr['init_state'])[None], np.asarray(pr['goal_state'])[None])
+        env = cls(np.asarray(pr['map'])[None], np.asarray(pr['init_state'])[None], np.asarray(pr['goal_state'])[None])
         env.init_new_problem(0)
         envs.append(env)
     w = int(np.asarray(problems[0]['map']).shape[0])
     maps = torch.from_numpy(np.ascontiguousarray(np.asarray([np.asarray(pr['map'], dtype=np.float64) for pr in problems]))).to(dev)
-    init64 = torch.from_numpy(np.ascontiguousarray(np.asarray([np.asarray(e.init_state, dtype=np.float64).reshape(2) for e in envs]))).to(dev)
-    goal64 = torch.from_numpy(np.ascontiguousarray(np.asarray([np.asarray(e.goal_state, dtype=np.float64).reshape(2) for e in envs]))).to(dev)
-    v = torch.empty(B * (2 + 2 * batch), 2, dtype=torch.float32, device=dev)
+    init64 = torch.from_numpy(np.ascontiguousarray(np.asarray([np.asarray(e.init_state, dtype=np.float64).reshape(dim) for e in envs]))).to(dev)
+    goal64 = torch.from_numpy(np.ascontiguousarray(np.asarray([np.asarray(e.goal_state, dtype=np.float64).reshape(dim) for e in envs]))).to(dev)
+    v = torch.empty(B * (2 + 2 * batch), dim, dtype=torch.float32, device=dev)
     node_ptr = torch.empty(B + 1, dtype=torch.int32, device=dev)
     used = torch.empty(B, dtype=torch.int32, device=dev)
+    checks = torch.empty(B, dtype=torch.int64, device=dev) if dim == 3 else None
     state = torch.zeros(2, dtype=torch.int64, device=dev)                  # [cursor, ok (int32 in the low half)]
-    stream = AttemptStream()
-    m = int(B * batch * _DRAWS_PER_FREE[0] * 1.25) + 2048
+    stream = AttemptStream(limits=cls.SAMPLE_LIMITS)
+    m = int(B * batch * _DRAWS_PER_FREE[dim - 2] * 1.25) + 2048
     with torch.cuda.device(dev):
         while True:
             att = torch.from_numpy(stream.peek(m)).to(dev)
             state.zero_()
             sb = _lib.MazeSampleBatch(B, w, int(batch), int(att.shape[0]), att.data_ptr(), maps.data_ptr(), init64.data_ptr(),
                                       goal64.data_ptr())
-            _lib.check(_lib.lib().gnnmp_maze_sample(ctypes.byref(sb), state.data_ptr(), v.data_ptr(), node_ptr.data_ptr(),
-                                                    used.data_ptr(), state.data_ptr() + 8, torch.cuda.current_stream().cuda_stream),
-                       'gnnmp_maze_sample')
+            st = torch.cuda.current_stream().cuda_stream
+            if dim == 3:
+                _lib.check(_lib.lib().gnnmp_stick_sample(ctypes.byref(sb), state.data_ptr(), v.data_ptr(), node_ptr.data_ptr(),
+                                                         used.data_ptr(), checks.data_ptr(), state.data_ptr() + 8, st),
+                           'gnnmp_stick_sample')
+            else:
+                _lib.check(_lib.lib().gnnmp_maze_sample(ctypes.byref(sb), state.data_ptr(), v.data_ptr(), node_ptr.data_ptr(),
+                                                        used.data_ptr(), state.data_ptr() + 8, st), 'gnnmp_maze_sample')
             cursor, ok = state.cpu().tolist()                                # the one wait of the sampling
             if ok & 0xffffffff:
                 break
             m *= 2                                                           # the block was too short: nothing was consumed
-    used_h = used.cpu().numpy()
+    used_h = (checks if dim == 3 else used).cpu().numpy()                    # collision checks of the sampling, per problem
     nptr = node_ptr.cpu().numpy().astype(np.int64)
     stream.consume(int(cursor))
     stream.close()                                                           # global RNG: as if sampled one by one
-    _DRAWS_PER_FREE[0] = max(1.5, 0.5 * _DRAWS_PER_FREE[0] + 0.5 * float(cursor) / max(B * batch, 1))
+    _DRAWS_PER_FREE[dim - 2] = max(1.5, 0.5 * _DRAWS_PER_FREE[dim - 2] + 0.5 * float(cursor) / max(B * batch, 1))
     for e, u in zip(envs, used_h):
-        e.collision_check_count += int(u)                                    # maze_env.py: one check per draw
+        e.collision_check_count += int(u)                                    # maze_env.py: one check per draw (point robot)
     nf = int(batch) + 2
     return {'envs': envs, 'v': v[:int(nptr[-1])], 'node_ptr': node_ptr, 'node_ptr_host': nptr, 'n_free': [nf] * B,
             'k1s': [k1_of(k, nf)] * B, 'maps': maps, 'goal64': goal64}
@@ -694,7 +725,7 @@ def maze_explore_device(v, node_ptr, edge_ptr, n_free, ei, scores, maps, goal64,
 @torch.no_grad()
 def explore_maze_batch(problems, model, device, batch=500, k=30, loop=5, model_s=None, smooth_iters=5, timings=None,
                        presampled=None):
-    """Many 2-D maze problems at once: sampling on the host (the reference's numpy RNG
+    """Many maze problems (point robot or stick robot, by the width of ``init_state``) at once: sampling on the host (the reference's numpy RNG
     stream, one problem after the other), then -- in ONE pass on the device -- kNN graphs
     (graph_kernels.hip), explorer forward (batched), greedy expansion + collision checks
     (maze_kernels.hip) and, when ``model_s`` is given, the smoothing stage of the solved problems
@@ -773,7 +804,7 @@ def explore_maze_batch(problems, model, device, batch=500, k=30, loop=5, model_s
                     'c_explore': envs[b].collision_check_count + int(checks[b]),
                     'path': vs_np[b][nodes], 'free': None, 'env': envs[b], 'v': vs[b], 'n_free': n_free[b]})
         if model_s is not None:
-            sp, cs = smoothed.get(b, (np.zeros((0, 2), dtype=np.float32), 0))
+            sp, cs = smoothed.get(b, (np.zeros((0, int(v.shape[1])), dtype=np.float32), 0))
             out[-1].update(smooth_path=sp, c_smooth=cs)
     mark('results', tm)
     return out

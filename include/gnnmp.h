@@ -20,6 +20,8 @@
  *       create_data's edge construction                       eval_gnn.py:159-164
  *   gnnmp_maze_sample
  *       explore()'s rejection sampling (classification + compaction)   eval_gnn.py:180-184, environment/maze_env.py
+ *   gnnmp_stick_sample
+ *       the same for MazeEnv(dim=3): _stick_in_free_space per draw     environment/maze_env.py:279-314
  *   gnnmp_maze_steer / gnnmp_stick_steer
  *       proposed_path_smootherv2 (steering of the smoothing stage)  smoother.py:194-216
  *   gnnmp_maze_explore_workspace_bytes / gnnmp_maze_explore / gnnmp_maze_explore_ex
@@ -476,13 +478,31 @@ int gnnmp_stick_steer(int32_t n_problems, int32_t total_path, int32_t width, con
 typedef struct {
     int32_t n_problems, width, n_free;
     int64_t n_attempts;
-    const double* attempts;      /* [n_attempts, 2]                                           */
+    const double* attempts;      /* [n_attempts, 2]  (gnnmp_stick_sample: 3 columns here ...) */
     const double* maps;          /* [B, width, width]                                         */
-    const double* init_states;   /* [B, 2]                                                    */
+    const double* init_states;   /* [B, 2]           (... and in these two)                   */
     const double* goal_states;   /* [B, 2]                                                    */
 } gnnmp_maze_sample_batch;
 int gnnmp_maze_sample(const gnnmp_maze_sample_batch* batch, int64_t* cursor, float* v_out, int32_t* node_ptr_out,
                       int32_t* used_out, int32_t* ok_out, void* hip_stream);
+
+/* The same for the 3-DoF stick robot, MazeEnv(dim=3).  The batch struct is gnnmp_maze_sample's with every row three wide:
+ * attempts [n_attempts, 3] float64 is the host's np.random.uniform(-LIMITS, LIMITS, ...) stream with LIMITS = (1, 1, 0.4) in draw
+ * order, init_states / goal_states are [B, 3], v_out rows are (x, y, z) float32 and v_out must hold n_problems * (2 + 2 * n_free)
+ * of them.  A draw is free iff _stick_in_free_space holds for the float64 draw (maze_env.py:279-291), entirely in float64:
+ * theta = z / 0.4 * pi, ends = centre -+ 0.1 * (cos theta, sin theta); end a is queried, then end b, then the midpoints of
+ * _iterative_check_segment (maze_env.py:301-314: split while the end cells are more than one grid step apart and the ends more than
+ * 0.05 apart in L1, left half before right half), stopping at the first blocked query.  An end outside [-1, 1]^2 fails without a
+ * check; every in-bounds point query is one check, so a draw costs 0 .. 9 (a stick is 0.2 long: its bisection has at most three
+ * levels, seven midpoints).  cos / sin are the device's float64 library functions: against numpy an outcome can differ only for a
+ * stick end within an ulp of a cell boundary.
+ * The contract is gnnmp_maze_sample's: problems are walked in stream order, *cursor (device, in / out) is the first unconsumed draw,
+ * used_out [B] the draws consumed per problem, node_ptr_out [B + 1] the row offsets, *ok_out = 0 with *cursor unchanged (and
+ * node_ptr_out[b + 1] = -1 for the problem the stream ended in) when the stream runs out.  Added: checks_out [B] (int64), the
+ * collision checks of the draws problem b CONSUMED -- those up to and including its n_free-th free one -- which is what
+ * MazeEnv.collision_check_count grows by during sample_n_points.  One launch on hip_stream, no synchronisation, no allocation. */
+int gnnmp_stick_sample(const gnnmp_maze_sample_batch* batch, int64_t* cursor, float* v_out, int32_t* node_ptr_out,
+                       int32_t* used_out, int64_t* checks_out, int32_t* ok_out, void* hip_stream);
 
 /* ------------------------------------------------------------------------------------------
  * Supervision of the explorer's training step (train_explorer.py:124-176): edge labels, shortest paths to the goal,
