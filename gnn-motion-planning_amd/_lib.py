@@ -66,6 +66,22 @@ class MazeSampleBatch(ctypes.Structure):
                 ('goal_states', ctypes.c_void_p)]
 
 
+class MazeRoundsState(ctypes.Structure):
+    _fields_ = [('n_problems', ctypes.c_int32), ('cap', ctypes.c_int32), ('pair_cap', ctypes.c_int32),
+                ('free_pool', ctypes.c_void_p), ('coll_pool', ctypes.c_void_p), ('n_free', ctypes.c_void_p),
+                ('n_coll', ctypes.c_void_p), ('tree_explored', ctypes.c_void_p), ('tree_prev', ctypes.c_void_p),
+                ('tree_n_explored', ctypes.c_void_p), ('tree_pairs', ctypes.c_void_p), ('tree_n_pairs', ctypes.c_void_p),
+                ('tree_success', ctypes.c_void_p), ('tree_path_len', ctypes.c_void_p), ('tree_path', ctypes.c_void_p),
+                ('tree_checks', ctypes.c_void_p)]
+
+
+class MazeStreamsBatch(ctypes.Structure):
+    _fields_ = [('n_problems', ctypes.c_int32), ('width', ctypes.c_int32), ('n_free', ctypes.c_int32), ('cap', ctypes.c_int32),
+                ('n_attempts', ctypes.c_int64), ('attempts', ctypes.c_void_p), ('att_ptr', ctypes.c_void_p),
+                ('att_ptr_host', ctypes.c_void_p), ('maps', ctypes.c_void_p), ('init_states', ctypes.c_void_p),
+                ('goal_states', ctypes.c_void_p), ('active', ctypes.c_void_p)]
+
+
 class EpisodeGraphs(ctypes.Structure):
     _fields_ = [('n_problems', ctypes.c_int32), ('total_nodes', ctypes.c_int32), ('total_edges', ctypes.c_int32),
                 ('node_ptr', ctypes.c_void_p), ('edge_ptr', ctypes.c_void_p), ('edge_index', ctypes.c_void_p)]
@@ -173,6 +189,11 @@ def lib():
                                         vp, vp, vp, vp, vp, sz, vp]
     L.gnnmp_maze_sample.argtypes = [ctypes.POINTER(MazeSampleBatch), vp, vp, vp, vp, vp, vp]
     L.gnnmp_stick_sample.argtypes = [ctypes.POINTER(MazeSampleBatch), vp, vp, vp, vp, vp, vp, vp]
+    L.gnnmp_maze_sample_streams.argtypes = [ctypes.POINTER(MazeStreamsBatch), ctypes.c_int32, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.gnnmp_maze_rounds_gather.argtypes = [ctypes.POINTER(MazeRoundsState), ctypes.c_int32, vp, ctypes.c_int32, ctypes.c_int64, vp, vp, vp, vp,
+                                           ctypes.POINTER(MazeResume), vp]
+    L.gnnmp_maze_rounds_carry.argtypes = [ctypes.POINTER(MazeRoundsState), ctypes.c_int32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                          vp, vp, vp, vp]
     L.gnnmp_maze_steer.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, vp, vp, vp, vp, vp, vp, vp, vp]
     L.gnnmp_stick_steer.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.gnnmp_episode_label_maze.argtypes = [ctypes.POINTER(EpisodeGraphs), ctypes.c_int32, ctypes.c_int32, vp, vp, vp, vp, vp]

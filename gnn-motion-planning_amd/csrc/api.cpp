@@ -1535,6 +1535,84 @@ extern "C" int gnnmp_stick_sample(const gnnmp_maze_sample_batch* b, int64_t* cur
     return GNNMP_OK;
 }
 
+extern "C" int gnnmp_maze_sample_streams(const gnnmp_maze_streams_batch* b, int32_t dim, float* free_pool, int32_t* n_free,
+                                         float* coll_pool, int32_t* n_coll, int32_t* used_out, int64_t* checks_out,
+                                         int32_t* status_out, void* hip_stream) {
+    if (dim != 2 && dim != 3) return GNNMP_ERR_DIMS;
+    if (!b || !free_pool || !n_free || !coll_pool || !n_coll || !used_out || !checks_out || !status_out) return GNNMP_ERR_NULL;
+    if (!b->attempts || !b->att_ptr || !b->maps || !b->init_states || !b->goal_states) return GNNMP_ERR_NULL;
+    if (b->n_problems < 1 || b->width < 1 || b->n_free < 1 || b->cap < b->n_free || b->n_attempts < 0) return GNNMP_ERR_ARG;
+    if (b->att_ptr_host) {
+        if (b->att_ptr_host[0] < 0 || b->att_ptr_host[b->n_problems] > b->n_attempts) return GNNMP_ERR_ARG;
+        for (int i = 0; i < b->n_problems; ++i)
+            if (b->att_ptr_host[i + 1] < b->att_ptr_host[i]) return GNNMP_ERR_ARG;
+    }
+    MazeStreamsParams p;
+    p.B = b->n_problems; p.w = b->width; p.n = b->n_free; p.cap = b->cap; p.dim = dim;
+    p.attempts = b->attempts; p.M = b->n_attempts; p.att_ptr = reinterpret_cast<const long long*>(b->att_ptr);
+    p.maps = b->maps; p.init_states = b->init_states; p.goal_states = b->goal_states; p.active = b->active;
+    p.free_pool = free_pool; p.coll_pool = coll_pool; p.n_free = n_free; p.n_coll = n_coll;
+    p.used = used_out; p.checks = reinterpret_cast<long long*>(checks_out); p.status = status_out;
+    HIP_TRY(launch_maze_sample_streams(p, static_cast<hipStream_t>(hip_stream)));
+    return GNNMP_OK;
+}
+
+namespace {
+int rounds_state_check(const gnnmp_maze_rounds_state* s, bool trees) {
+    if (!s) return GNNMP_ERR_NULL;
+    if (!s->free_pool || !s->coll_pool || !s->n_free || !s->n_coll) return GNNMP_ERR_NULL;
+    if (trees && (!s->tree_explored || !s->tree_prev || !s->tree_n_explored || !s->tree_pairs || !s->tree_n_pairs)) return GNNMP_ERR_NULL;
+    if (s->n_problems < 1 || s->cap < 1 || s->pair_cap < 1 || (long long)s->n_problems * s->pair_cap > (1ll << 30)) return GNNMP_ERR_ARG;
+    return GNNMP_OK;
+}
+}  // namespace
+
+extern "C" int gnnmp_maze_rounds_gather(const gnnmp_maze_rounds_state* s, int32_t dim, const uint8_t* active, int32_t n_active,
+                                        int64_t v_rows, float* v_out, int32_t* node_ptr_out, int32_t* n_free_out, int32_t* slot_out,
+                                        const gnnmp_maze_resume* r, void* hip_stream) {
+    if (dim != 2 && dim != 3) return GNNMP_ERR_DIMS;
+    if (!v_out || !node_ptr_out || !n_free_out || !slot_out) return GNNMP_ERR_NULL;
+    if (r && (!r->n_explored || !r->explored || !r->prev || !r->n_pairs || !r->pair_ptr)) return GNNMP_ERR_NULL;
+    if (const int rc = rounds_state_check(s, r != nullptr)) return rc;
+    if (v_rows < 0 || n_active < 1 || n_active > s->n_problems) return GNNMP_ERR_ARG;
+    MazeGatherParams p;
+    p.A = n_active; p.B = s->n_problems; p.dim = dim; p.cap = s->cap; p.pair_cap = s->pair_cap; p.v_rows = v_rows;
+    p.free_pool = s->free_pool; p.coll_pool = s->coll_pool; p.n_free = s->n_free; p.n_coll = s->n_coll; p.active = active;
+    p.v = v_out; p.node_ptr = node_ptr_out; p.n_free_out = n_free_out; p.slot_of = slot_out;
+    p.tree_explored = s->tree_explored; p.tree_prev = s->tree_prev; p.tree_n_explored = s->tree_n_explored;
+    p.tree_n_pairs = s->tree_n_pairs;
+    // (the resume struct is const for its reader, gnnmp_maze_explore_ex; here its arrays are the outputs)
+    p.res_n_explored = r ? const_cast<int*>(r->n_explored) : nullptr; p.res_explored = r ? const_cast<int*>(r->explored) : nullptr;
+    p.res_prev = r ? const_cast<int*>(r->prev) : nullptr; p.res_n_pairs = r ? const_cast<int*>(r->n_pairs) : nullptr;
+    p.res_pair_ptr = r ? const_cast<int*>(r->pair_ptr) : nullptr;
+    HIP_TRY(launch_maze_rounds_gather(p, static_cast<hipStream_t>(hip_stream)));
+    return GNNMP_OK;
+}
+
+extern "C" int gnnmp_maze_rounds_carry(const gnnmp_maze_rounds_state* s, int32_t n_active, const int32_t* slot_of,
+                                       const int32_t* node_ptr, const int32_t* edge_ptr, const int32_t* success,
+                                       const int32_t* n_explored, const int32_t* explored, const int32_t* prev,
+                                       const int32_t* n_pairs, const int32_t* explored_edges, const int32_t* path_len,
+                                       const int32_t* path, const int64_t* checks, int32_t* status_out, void* hip_stream) {
+    if (!node_ptr || !edge_ptr || !success || !n_explored || !explored || !prev || !n_pairs || !explored_edges || !path_len ||
+        !path || !checks || !status_out)
+        return GNNMP_ERR_NULL;
+    if (const int rc = rounds_state_check(s, true)) return rc;
+    if (!s->tree_success || !s->tree_path_len || !s->tree_path || !s->tree_checks) return GNNMP_ERR_NULL;
+    if (n_active < 1 || n_active > s->n_problems) return GNNMP_ERR_ARG;
+    MazeCarryParams p;
+    p.A = n_active; p.B = s->n_problems; p.cap = s->cap; p.pair_cap = s->pair_cap;
+    p.slot_of = slot_of; p.node_ptr = node_ptr; p.edge_ptr = edge_ptr;
+    p.success = success; p.n_explored = n_explored; p.explored = explored; p.prev = prev; p.n_pairs = n_pairs;
+    p.pairs = explored_edges; p.path_len = path_len; p.path = path; p.checks = reinterpret_cast<const long long*>(checks);
+    p.tree_explored = s->tree_explored; p.tree_prev = s->tree_prev; p.tree_n_explored = s->tree_n_explored;
+    p.tree_pairs = s->tree_pairs; p.tree_n_pairs = s->tree_n_pairs; p.tree_success = s->tree_success;
+    p.tree_path_len = s->tree_path_len; p.tree_path = s->tree_path; p.tree_checks = reinterpret_cast<long long*>(s->tree_checks);
+    p.status = status_out;
+    HIP_TRY(launch_maze_rounds_carry(p, static_cast<hipStream_t>(hip_stream)));
+    return GNNMP_OK;
+}
+
 // =============================================================================================
 // training path of the explorer (train_explorer.py:156-186)
 // =============================================================================================

@@ -207,6 +207,46 @@ hipError_t launch_maze_sample(const MazeSampleParams& p, hipStream_t st);
 // the stick robot's (MazeEnv(dim=3)): attempts [M, 3], init / goal states [B, 3], node rows of width 3, checks required
 hipError_t launch_stick_sample(const MazeSampleParams& p, hipStream_t st);
 
+// resample rounds for a whole batch, every problem on its own sample stream (maze_kernels.hip, eval_gnn.py:191-247)
+struct MazeStreamsParams {
+    int B, w, n, cap, dim;                // problems, map width, free draws to append, pool capacity (rows behind init / goal), 2 / 3
+    const double* attempts;               // [M, dim] the host's uniform draws, problem b's block at att_ptr[b]
+    long long M;
+    const long long* att_ptr;             // [B + 1]
+    const double *maps, *init_states, *goal_states;      // [B, w, w], [B, dim], [B, dim]
+    const unsigned char* active;          // [B] or nullptr (= all): 0 = the problem is skipped entirely
+    float *free_pool, *coll_pool;         // [B, cap + 2, dim] each
+    int *n_free, *n_coll;                 // [B] in / out
+    int* used;                            // out [B]: draws consumed
+    long long* checks;                    // out [B]: collision checks of the consumed draws
+    int* status;                          // out [B]: 0 done, 1 the block ended first, 2 no room in the pools / block outside attempts
+};
+hipError_t launch_maze_sample_streams(const MazeStreamsParams& p, hipStream_t st);
+
+struct MazeGatherParams {
+    int A, B, dim, cap, pair_cap;         // problems of the round (the [A] / [A + 1] outputs), slots of the store
+    long long v_rows;                     // rows v can hold
+    const float *free_pool, *coll_pool;
+    const int *n_free, *n_coll;
+    const unsigned char* active;          // [B] or nullptr
+    float* v;                             // out: free rows then collided rows of every active problem, compact
+    int *node_ptr, *n_free_out, *slot_of; // out [A + 1], [A], [A]
+    const int *tree_explored, *tree_prev, *tree_n_explored, *tree_n_pairs;      // the store ([B, cap + 2], [B, cap + 2], [B], [B])
+    int *res_explored, *res_prev, *res_n_explored, *res_n_pairs, *res_pair_ptr; // out (all or none): the round's gnnmp_maze_resume
+};
+hipError_t launch_maze_rounds_gather(const MazeGatherParams& p, hipStream_t st);
+
+struct MazeCarryParams {
+    int A, B, cap, pair_cap;              // problems of the round, slots of the store
+    const int *slot_of, *node_ptr, *edge_ptr;
+    const int *success, *n_explored, *explored, *prev, *n_pairs, *pairs, *path_len, *path;      // gnnmp_maze_explore_ex's outputs
+    const long long* checks;
+    int *tree_explored, *tree_prev, *tree_n_explored, *tree_pairs, *tree_n_pairs, *tree_success, *tree_path_len, *tree_path;
+    long long* tree_checks;
+    int* status;                          // out [A]
+};
+hipError_t launch_maze_rounds_carry(const MazeCarryParams& p, hipStream_t st);
+
 // ---- supervision of the explorer's training step (train_episode_kernels.hip, train_explorer.py:124-176)
 struct EpLabelParams {                    // (a) edge_free / edge_cost of construct_graph for maze problems
     int B, dim, w;

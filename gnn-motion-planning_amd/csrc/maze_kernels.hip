@@ -1001,6 +1001,278 @@ hipError_t launch_maze_explore(const MazeParams& p, hipStream_t st) {
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Resample rounds for a whole batch (eval_gnn.py:191-247): every problem owns its sample stream, so nothing orders the
+// problems any more and round r of all unfinished problems is one batch.  Three kernels around gnnmp_maze_explore_ex:
+//   maze_sample_streams_kernel   rejection sampling that APPENDS n free draws (and the rejected ones the reference keeps) to
+//                                per-problem pools, one workgroup per problem;
+//   maze_rounds_gather_kernel    the pools of the problems of this round -> compact node rows, node_ptr, and their search
+//                                trees at this round's node offsets (a gnnmp_maze_resume);
+//   maze_rounds_carry_kernel     the round's trees, new pairs, paths and checks -> the per-problem store.
+// ---------------------------------------------------------------------------------------------------------------------
+constexpr int kStreamCachedSteps = 32;      // free flags of the first 32 x 1024 draws stay in LDS between the two passes
+
+// Problem b classifies its own draws [att_ptr[b], att_ptr[b + 1]) in steps of 1024 like maze_sample_kernel / stick_sample_kernel.
+// Two passes: the first only finds the n-th free draw (a block that ends before it leaves the pools untouched: status 1), the
+// second ranks the consumed draws again -- from the ballots kept in LDS, classifying again only beyond kStreamCachedSteps --
+// and stores the rows.
+template <int DIM>
+__global__ __launch_bounds__(1024) void maze_sample_streams_kernel(MazeStreamsParams p) {
+    __shared__ unsigned char occ[kMazeLdsCells];
+    __shared__ unsigned long long s_bal[kStreamCachedSteps * 16];
+    __shared__ int wsum[16], csum[16];
+    __shared__ int s_tstar, s_cstar;
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (p.active && !p.active[b]) return;
+    const long long a0 = p.att_ptr[b], Mb = p.att_ptr[b + 1] - a0;
+    const int nf0 = p.n_free[b], nc0 = p.n_coll[b];
+    const int base = nf0 == 0 ? 2 : nf0;                         // round 0: init and goal come first
+    const int nf1 = base + p.n;
+    const int climit = nf0 == 0 ? p.n : nf1;                     // eval_gnn.py:180 / :243-245
+    if (nf0 < 0 || nc0 < 0 || nf1 > p.cap + 2 || a0 < 0 || a0 + (Mb > 0 ? Mb : 0) > p.M) {      // no room / not this call's draws
+        if (tid == 0) { p.status[b] = 2; p.used[b] = 0; p.checks[b] = 0; }
+        return;
+    }
+    const bool in_lds = p.w * p.w <= kMazeLdsCells;
+    const double* map = p.maps + (size_t)b * p.w * p.w;
+    if (in_lds)
+        for (int i = tid; i < p.w * p.w; i += 1024) occ[i] = map[i] == 0.0 ? 0 : 1;
+    if (tid == 0) s_tstar = -1;
+    __syncthreads();
+    MazeCtx m;
+    m.map = map; m.occ = in_lds ? occ : nullptr; m.w = p.w; m.checks = 0; m.stack = nullptr;
+    const double* att = p.attempts + (size_t)a0 * DIM;
+    auto classify = [&](long long idx, int& cnt) {
+        if constexpr (DIM == 2) {
+            const double x = att[2 * idx], y = att[2 * idx + 1];
+            cnt = 1;
+            if (!maze_valid64(x, y)) return false;               // (uniform(-1, 1) never is: keeps the lookup inside the map)
+            const int c = maze_cell64(x, p.w) * p.w + maze_cell64(y, p.w);
+            return in_lds ? occ[c] == 0 : map[c] == 0.0;
+        } else {
+            return stick_draw_fp64(m, att[3 * idx], att[3 * idx + 1], att[3 * idx + 2], cnt);
+        }
+    };
+    // ---- pass 1: where is the n-th free draw, and what do the draws up to it cost
+    int free_before = 0;
+    long long checks = 0, used = 0;
+    int step = 0;
+    for (long long off = 0;; off += 1024, ++step) {
+        const long long idx = off + tid;
+        int cnt = 0;
+        const bool isfree = idx < Mb ? classify(idx, cnt) : false;
+        const unsigned long long bal = __builtin_amdgcn_ballot_w64(isfree);
+        const int incl_w = __builtin_popcountll(bal & (~0ull >> (63 - lane)));
+        int cincl_w = cnt;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const int up = __shfl_up(cincl_w, d, 64);
+            if (lane >= d) cincl_w += up;
+        }
+        if (lane == 0) {
+            wsum[wave] = __builtin_popcountll(bal);
+            if (step < kStreamCachedSteps) s_bal[step * 16 + wave] = bal;
+        }
+        if (lane == 63) csum[wave] = cincl_w;
+        __syncthreads();
+        int before = 0, F = 0, cbefore = 0, C = 0;
+#pragma unroll
+        for (int w2 = 0; w2 < 16; ++w2) {
+            const int f = wsum[w2], c = csum[w2];
+            before += w2 < wave ? f : 0; F += f;
+            cbefore += w2 < wave ? c : 0; C += c;
+        }
+        if (isfree && free_before + before + incl_w == p.n) {    // the n-th free draw of this call
+            s_tstar = tid;
+            s_cstar = cbefore + cincl_w;
+        }
+        __syncthreads();
+        const int tstar = s_tstar;
+        if (tstar >= 0) {
+            used = off + tstar + 1;
+            checks += s_cstar;
+            break;
+        }
+        if (off + 1024 >= Mb) {                                  // the block ended first (workgroup-uniform): nothing is touched
+            if (tid == 0) { p.status[b] = 1; p.used[b] = 0; p.checks[b] = 0; }
+            return;
+        }
+        free_before += F;
+        checks += C;
+        __syncthreads();                                         // wsum / csum are rewritten by the next step
+    }
+    // ---- pass 2: rows of the consumed draws [0, used)
+    float* fpool = p.free_pool + (size_t)b * (p.cap + 2) * DIM;
+    float* cpool = p.coll_pool + (size_t)b * (p.cap + 2) * DIM;
+    int fb = 0, rb = 0;
+    step = 0;
+    for (long long off = 0; off < used; off += 1024, ++step) {
+        const long long idx = off + tid;
+        const bool in = idx < used;
+        bool isfree = false;
+        if (in) {
+            int cnt = 0;
+            isfree = step < kStreamCachedSteps ? ((s_bal[step * 16 + wave] >> lane) & 1ull) != 0 : classify(idx, cnt);
+        }
+        const unsigned long long bal = __builtin_amdgcn_ballot_w64(isfree);
+        const int incl_w = __builtin_popcountll(bal & (~0ull >> (63 - lane)));
+        __syncthreads();                                         // the previous step's wave totals have been read
+        if (lane == 0) wsum[wave] = __builtin_popcountll(bal);
+        __syncthreads();
+        int before = 0, F = 0;
+#pragma unroll
+        for (int w2 = 0; w2 < 16; ++w2) { const int f = wsum[w2]; before += w2 < wave ? f : 0; F += f; }
+        const int incl = before + incl_w;                        // free draws among this step's draws 0 .. tid
+        if (in) {
+            float* row = nullptr;
+            if (isfree) {
+                row = fpool + (size_t)(base + fb + incl - 1) * DIM;
+            } else {
+                const int rr = nc0 + rb + (tid + 1 - incl) - 1;  // place among the problem's collided rows
+                if (rr < climit) row = cpool + (size_t)rr * DIM;
+            }
+            if (row) {
+#pragma unroll
+                for (int c = 0; c < DIM; ++c) row[c] = (float)att[DIM * idx + c];
+            }
+        }
+        const long long left = used - off;
+        fb += F;
+        rb += (int)(left < 1024 ? left : 1024) - F;
+    }
+    if (tid == 0) {
+        if (nf0 == 0) {
+            const double* is = p.init_states + DIM * (size_t)b;
+            const double* gs = p.goal_states + DIM * (size_t)b;
+#pragma unroll
+            for (int c = 0; c < DIM; ++c) { fpool[c] = (float)is[c]; fpool[DIM + c] = (float)gs[c]; }
+        }
+        const long long nc1 = nc0 + (used - p.n);
+        p.n_free[b] = nf1;
+        p.n_coll[b] = (int)(nc1 < climit ? nc1 : climit);
+        p.used[b] = (int)used;
+        p.checks[b] = DIM == 2 ? used : checks;
+        p.status[b] = 0;
+    }
+}
+
+hipError_t launch_maze_sample_streams(const MazeStreamsParams& p, hipStream_t st) {
+    if (p.B <= 0) return hipSuccess;
+    if (p.dim == 3) hipLaunchKernelGGL(maze_sample_streams_kernel<3>, dim3(p.B), dim3(1024), 0, st, p);
+    else hipLaunchKernelGGL(maze_sample_streams_kernel<2>, dim3(p.B), dim3(1024), 0, st, p);
+    return hipGetLastError();
+}
+
+// One workgroup per problem slot.  The offsets of a round depend on what the sampler just found, so they are computed here:
+// workgroup b sums the row counts of the active slots before it (B is a few hundred: B * B / 2 small reads in all, no second
+// launch and nothing read back), then copies its free rows, its collided rows and -- when the store holds trees -- its
+// explored list and parents to that offset.  The [A] / [A + 1] outputs were sized by the caller: an active slot that is not
+// among the first A writes nothing.
+__global__ __launch_bounds__(256) void maze_rounds_gather_kernel(MazeGatherParams p) {
+    __shared__ int s_cnt[4], s_off[4];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (p.active && !p.active[b]) return;
+    int cnt = 0, off = 0;
+    for (int i = tid; i < b; i += 256)
+        if (!p.active || p.active[i]) { cnt += 1; off += p.n_free[i] + p.n_coll[i]; }
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) { cnt += __shfl_xor(cnt, d, 64); off += __shfl_xor(off, d, 64); }
+    if (lane == 0) { s_cnt[wave] = cnt; s_off[wave] = off; }
+    __syncthreads();
+    const int j = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+    const int n0 = s_off[0] + s_off[1] + s_off[2] + s_off[3];
+    const int F = p.n_free[b], C = p.n_coll[b];
+    const int stride = p.cap + 2;
+    const bool fits = F >= 0 && C >= 0 && F <= stride && C <= stride && (long long)n0 + F + C <= p.v_rows;
+    if (j >= p.A) return;                                        // more active slots than the caller sized [A] / [A + 1] for
+    if (tid == 0) {
+        if (j == 0) p.node_ptr[0] = 0;
+        p.node_ptr[j + 1] = n0 + F + C;
+        p.n_free_out[j] = F;
+        p.slot_of[j] = b;
+    }
+    if (!fits) return;                                           // (the caller sized v from the same counts: cannot happen)
+    const float* fpool = p.free_pool + (size_t)b * stride * p.dim;
+    const float* cpool = p.coll_pool + (size_t)b * stride * p.dim;
+    float* v = p.v + (size_t)n0 * p.dim;
+    for (int i = tid; i < F * p.dim; i += 256) v[i] = fpool[i];
+    for (int i = tid; i < C * p.dim; i += 256) v[(size_t)F * p.dim + i] = cpool[i];
+    if (p.res_n_explored) {
+        const int ne = p.tree_n_explored[b] < F ? p.tree_n_explored[b] : F;      // only free nodes are ever explored
+        for (int i = tid; i < ne; i += 256) {
+            const int a = p.tree_explored[(size_t)b * stride + i];
+            p.res_explored[n0 + i] = a;
+            if (a >= 0 && a < F) p.res_prev[n0 + a] = p.tree_prev[(size_t)b * stride + a];
+        }
+        if (tid == 0) {
+            p.res_n_explored[j] = ne;
+            p.res_n_pairs[j] = p.tree_n_pairs[b];
+            p.res_pair_ptr[j] = b * p.pair_cap;
+            if (j == p.A - 1) p.res_pair_ptr[p.A] = p.B * p.pair_cap;      // the end of the store's pair lists
+        }
+    }
+}
+
+hipError_t launch_maze_rounds_gather(const MazeGatherParams& p, hipStream_t st) {
+    if (p.B <= 0) return hipSuccess;
+    hipLaunchKernelGGL(maze_rounds_gather_kernel, dim3(p.B), dim3(256), 0, st, p);
+    return hipGetLastError();
+}
+
+// One wave per problem of the round: its tree (explored order, parents by node id), its new pairs behind the ones the store
+// holds, its path and flags go to the problem's slot.  Status bit 0: the pair list would not fit (nothing of it is appended);
+// bit 1: a node id or a count beyond the slot (those entries are skipped).  Nothing is written outside the slot.
+__global__ __launch_bounds__(64) void maze_rounds_carry_kernel(MazeCarryParams p) {
+    const int j = blockIdx.x, lane = threadIdx.x;
+    const int slot = p.slot_of ? p.slot_of[j] : j;
+    const int n0 = p.node_ptr[j];
+    const int stride = p.cap + 2;
+    int st = 0;
+    if (slot < 0 || slot >= p.B) {
+        if (lane == 0) p.status[j] = 2;
+        return;
+    }
+    const int ne = p.n_explored[j];
+    int bad = ne < 0 || ne > stride;
+    int* t_expl = p.tree_explored + (size_t)slot * stride;
+    int* t_prev = p.tree_prev + (size_t)slot * stride;
+    if (!bad) {
+        for (int i = lane; i < ne; i += 64) {
+            const int a = p.explored[n0 + i];
+            if (a < 0 || a >= stride) { bad = 1; continue; }
+            t_expl[i] = a;
+            t_prev[a] = p.prev[n0 + a];
+        }
+    }
+    const int plen = p.path_len[j];
+    if (plen < 0 || plen > stride) bad = 1;
+    else
+        for (int i = lane; i < plen; i += 64) p.tree_path[(size_t)slot * stride + i] = p.path[n0 + i];
+    if (__builtin_amdgcn_ballot_w64(bad != 0)) st |= 2;
+    const int old = p.tree_n_pairs[slot], nw = p.n_pairs[j];
+    const bool room = old >= 0 && nw >= 0 && (long long)old + nw <= p.pair_cap;
+    if (room) {
+        const int* src = p.pairs + 2 * ((size_t)2 * p.edge_ptr[j] + j);
+        int* dst = p.tree_pairs + 2 * ((size_t)slot * p.pair_cap + old);
+        for (int i = lane; i < 2 * nw; i += 64) dst[i] = src[i];
+    } else {
+        st |= 1;
+    }
+    if (lane == 0) {
+        if (!(st & 2)) { p.tree_n_explored[slot] = ne; p.tree_path_len[slot] = plen; }
+        if (room) p.tree_n_pairs[slot] = old + nw;
+        p.tree_success[slot] = p.success[j];
+        p.tree_checks[slot] += p.checks[j];
+        p.status[j] = st;
+    }
+}
+
+hipError_t launch_maze_rounds_carry(const MazeCarryParams& p, hipStream_t st) {
+    if (p.A <= 0) return hipSuccess;
+    hipLaunchKernelGGL(maze_rounds_carry_kernel, dim3(p.A), dim3(64), 0, st, p);
+    return hipGetLastError();
+}
+
 #ifdef GNNMP_MAZE_TRACE
 }  // namespace gnnmp
 // copies the counters of the last explore launch (8 per problem: cycles of build / argmax / check / kill / rescan at 100 MHz,

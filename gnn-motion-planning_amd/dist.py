@@ -315,3 +315,15 @@ class MixedJob:
             if part[5] is not None:
                 cur.wait_stream(part[5])
         return res
+
+
+def eval_streams_shard(env, indexes, model, model_s, rank, world, **kw):
+    """Rank ``rank``'s contiguous block of ``indexes`` (:func:`shard_range`) through ``planner.eval_gnn_device_streams``: every
+    problem draws from its own stream, so a rank's results do not depend on the other ranks' problems and nothing has to be
+    skipped (``planner.skip_maze_sampling`` is for the global-stream planners).  ``rows_out`` / ``details_out`` in ``kw`` receive
+    the block's rows; gather them with :func:`gather_problem_results`."""
+    from .planner import eval_gnn_device_streams
+    indexes = list(indexes)
+    lo, hi = shard_range(len(indexes), rank, world)
+    seeds = kw.pop('seeds', None)
+    return eval_gnn_device_streams(env, indexes[lo:hi], model, model_s, seeds=None if seeds is None else list(seeds)[lo:hi], **kw)

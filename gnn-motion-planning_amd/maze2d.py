@@ -143,6 +143,15 @@ class Maze2D:
         self.collision_check_count += used
         return pts[free_mask], pts[~free_mask]
 
+    def classify_draws(self, pts):
+        """:meth:`_state_fp` of every row of ``pts`` [m, 2] float64 inside the bounds at once: (free [m] bool, checks [m] int64 --
+        one per draw), the counter itself left alone (the stick robot's :meth:`Maze3D.classify_draws` has the same form)."""
+        pts = np.asarray(pts, dtype=np.float64).reshape(-1, 2)
+        w = self.width
+        cells = ((pts + 1.0) * w / 2.0).astype(int)
+        cells[cells > w - 1] = w - 1
+        return self.map[cells[:, 0], cells[:, 1]] == 0, np.ones(pts.shape[0], dtype=np.int64)
+
     def sample_n_points_stream(self, stream, n):
         """:meth:`sample_n_points_arrays` on an :class:`AttemptStream` shared by consecutive problems."""
         w = self.width

@@ -1028,3 +1028,353 @@ def eval_gnn_device_rounds(env, indexes, model, model_s=None, seed=1234, batch=5
     return {'n_success': n_success, 'collision_explore': float(np.mean([s[3] for s in sol])),
             'collision': float(np.mean([s[3] + s[4] for s in sol])),
             'solution_cost': float(sum(s[2] for s in sol if s[0])) / max(n_success, 1), 'rounds': [s[7] for s in sol]}
+
+
+# --------------------------------------------------------------------------------------------------
+# resample rounds for a whole batch: every problem on its own sample stream
+# --------------------------------------------------------------------------------------------------
+def rounds_pair_cap(batch, t_max, k):
+    """Pairs a problem can record over all its rounds (include/gnnmp.h, gnnmp_maze_rounds_carry): a greedy step kills one
+    unordered free-free edge for the rest of its round and records two pairs, and a round on F free nodes has at most
+    2 k1 F such edges -- plus the initial [0, 0]."""
+    from .graph_build import k1_of
+    cap = 1
+    for r in range(1, max(int(t_max) // int(batch), 1) + 1):
+        nf = 2 + r * int(batch)
+        cap += 4 * k1_of(k, nf) * nf
+    return cap
+
+
+class MazeRoundsStore:
+    """The device arrays of ``gnnmp_maze_rounds_state`` for B problems: sample pools, search trees, pair lists, paths and
+    counts, one fixed-size slot per problem; trees start fresh (node 0 explored, the pair [0, 0]).
+
+    Memory: a slot is ``8 * pair_cap`` bytes of pair list plus ``(cap + 2) * (8 * dim + 12)`` bytes of pools, tree and path.
+    With :func:`rounds_pair_cap`'s derived bound the pair list dominates: about 0.5 MB per problem at batch = t_max = 500,
+    k = 30, so about 120 MB for a chunk of 256 problems, and reading the results back builds a ``B x pair_cap`` boolean mask
+    on top of it.  Whoever raises ``chunk`` of :func:`eval_gnn_device_streams` pays that per problem."""
+
+    def __init__(self, B, cap, pair_cap, dim, device):
+        dev = torch.device(device)
+        self.B, self.cap, self.pair_cap, self.dim, self.device = int(B), int(cap), int(pair_cap), int(dim), dev
+        stride = self.cap + 2
+        i32 = lambda *shape: torch.zeros(*shape, dtype=torch.int32, device=dev)      # noqa: E731
+        self.free_pool = torch.zeros(B, stride, dim, dtype=torch.float32, device=dev)
+        self.coll_pool = torch.zeros(B, stride, dim, dtype=torch.float32, device=dev)
+        self.n_free, self.n_coll = i32(B), i32(B)
+        self.tree_explored, self.tree_prev, self.tree_path = i32(B, stride), i32(B, stride), i32(B, stride)
+        self.tree_pairs = i32(B, self.pair_cap, 2)
+        self.tree_n_explored = torch.ones(B, dtype=torch.int32, device=dev)
+        self.tree_n_pairs = torch.ones(B, dtype=torch.int32, device=dev)
+        self.tree_success, self.tree_path_len = i32(B), i32(B)
+        self.tree_checks = torch.zeros(B, dtype=torch.int64, device=dev)
+        self.rebind()
+
+    def rebind(self):
+        """(Re)build the C struct from the tensors (after a caller swapped one of them for its own buffer)."""
+        from . import _lib
+        self.struct = _lib.MazeRoundsState(
+            self.B, self.cap, self.pair_cap, *(t.data_ptr() for t in (
+                self.free_pool, self.coll_pool, self.n_free, self.n_coll, self.tree_explored, self.tree_prev, self.tree_n_explored,
+                self.tree_pairs, self.tree_n_pairs, self.tree_success, self.tree_path_len, self.tree_path, self.tree_checks)))
+
+
+def maze_sample_streams(store, attempts, att_ptr_host, maps, init64, goal64, n, active=None):
+    """``gnnmp_maze_sample_streams`` on a :class:`MazeRoundsStore`: append ``n`` free draws (and the rejected ones the reference
+    keeps) to every active problem's pools from its own block ``[att_ptr[b], att_ptr[b + 1])`` of ``attempts`` (float64
+    ``[M, dim]``, device).  One launch on the current stream; returns device tensors ``(used, checks, status)``."""
+    import ctypes
+    from . import _lib
+    dev = store.device
+    att_ptr_host = np.ascontiguousarray(att_ptr_host, dtype=np.int64)
+    att_ptr = torch.from_numpy(att_ptr_host).to(dev)
+    used = torch.zeros(store.B, dtype=torch.int32, device=dev)
+    checks = torch.zeros(store.B, dtype=torch.int64, device=dev)
+    status = torch.zeros(store.B, dtype=torch.int32, device=dev)
+    attempts = attempts.contiguous()
+    sb = _lib.MazeStreamsBatch(store.B, int(maps.shape[1]), int(n), store.cap, int(attempts.shape[0]), attempts.data_ptr(),
+                               att_ptr.data_ptr(), att_ptr_host.ctypes.data, maps.data_ptr(), init64.data_ptr(), goal64.data_ptr(),
+                               active.data_ptr() if active is not None else None)
+    with torch.cuda.device(dev):
+        st = torch.cuda.current_stream().cuda_stream
+        _lib.check(_lib.lib().gnnmp_maze_sample_streams(ctypes.byref(sb), store.dim, store.free_pool.data_ptr(), store.n_free.data_ptr(),
+                                                        store.coll_pool.data_ptr(), store.n_coll.data_ptr(), used.data_ptr(),
+                                                        checks.data_ptr(), status.data_ptr(), st), 'gnnmp_maze_sample_streams')
+    return used, checks, status
+
+
+def maze_rounds_gather(store, n_active, v_rows, active=None, trees=True):
+    """``gnnmp_maze_rounds_gather``: the node rows of the ``n_active`` problems with ``active[b] != 0`` (None: all) in the layout
+    the graph builder and the explorer read, and (``trees``) their search trees at the same offsets.  ``v_rows``: the rows to
+    allocate (the caller knows the counts).  Returns a dict of device tensors: v, node_ptr, n_free, slot_of and, with trees,
+    n_explored / explored / prev / n_pairs / pair_ptr."""
+    import ctypes
+    from . import _lib
+    dev = store.device
+    A, v_rows = int(n_active), int(v_rows)
+    i32 = lambda n: torch.zeros(n, dtype=torch.int32, device=dev)      # noqa: E731
+    out = {'v': torch.empty(v_rows, store.dim, dtype=torch.float32, device=dev), 'node_ptr': i32(A + 1), 'n_free': i32(A),
+           'slot_of': i32(A)}
+    rs = None
+    if trees:
+        out.update(n_explored=i32(A), explored=i32(max(v_rows, 1)), prev=i32(max(v_rows, 1)), n_pairs=i32(A), pair_ptr=i32(A + 1))
+        rs = _lib.MazeResume(out['n_explored'].data_ptr(), out['explored'].data_ptr(), out['prev'].data_ptr(),
+                             out['n_pairs'].data_ptr(), store.tree_pairs.data_ptr(), out['pair_ptr'].data_ptr())
+        out['resume'] = rs
+    with torch.cuda.device(dev):
+        st = torch.cuda.current_stream().cuda_stream
+        _lib.check(_lib.lib().gnnmp_maze_rounds_gather(ctypes.byref(store.struct), store.dim,
+                                                       active.data_ptr() if active is not None else None, A, v_rows,
+                                                       out['v'].data_ptr(), out['node_ptr'].data_ptr(), out['n_free'].data_ptr(),
+                                                       out['slot_of'].data_ptr(), ctypes.byref(rs) if rs is not None else None, st),
+                   'gnnmp_maze_rounds_gather')
+    return out
+
+
+def maze_rounds_explore(store, g, ei, edge_ptr, scores, maps, goal64, between=None):
+    """One round of the greedy expansion for the problems of a :func:`maze_rounds_gather` result ``g`` with their trees carried
+    on the device: ``gnnmp_maze_explore_ex`` in resume mode, then ``gnnmp_maze_rounds_carry`` into the store.  ``maps`` /
+    ``goal64``: rows of the round's problems.  Nothing is read back; returns the carry's status words [A] (device).
+    ``between``: called between the two launches (a timing tool records an event there)."""
+    import ctypes
+    from . import _lib
+    dev = store.device
+    v, node_ptr = g['v'], g['node_ptr']
+    A, total_n, total_e = int(node_ptr.shape[0]) - 1, int(v.shape[0]), int(ei.shape[1])
+    mb = _lib.MazeBatch(A, total_n, total_e, int(maps.shape[1]), v.data_ptr(), node_ptr.data_ptr(), edge_ptr.data_ptr(),
+                        g['n_free'].data_ptr(), ei.data_ptr(), scores.data_ptr(), maps.data_ptr(), goal64.data_ptr())
+    need = ctypes.c_size_t()
+    _lib.check(_lib.lib().gnnmp_maze_explore_workspace_bytes(ctypes.byref(mb), ctypes.byref(need)), 'maze ws')
+    ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
+    i32 = lambda n: torch.zeros(n, dtype=torch.int32, device=dev)      # noqa: E731
+    success, n_expl, expl, n_pairs, ee, plen, path, prev = i32(A), i32(A), i32(total_n), i32(A), i32(2 * (2 * total_e + A)), \
+        i32(A), i32(total_n), i32(total_n)
+    checks = torch.zeros(A, dtype=torch.int64, device=dev)
+    status = i32(A)
+    L = _lib.lib()
+    with torch.cuda.device(dev):
+        st = torch.cuda.current_stream().cuda_stream
+        _lib.check(L.gnnmp_maze_explore_ex(ctypes.byref(mb), store.dim, ctypes.byref(g['resume']), success.data_ptr(),
+                                           n_expl.data_ptr(), expl.data_ptr(), n_pairs.data_ptr(), ee.data_ptr(), plen.data_ptr(),
+                                           path.data_ptr(), checks.data_ptr(), prev.data_ptr(), ws.data_ptr(), ws.numel(), st),
+                   'gnnmp_maze_explore_ex')
+        if between is not None:
+            between()
+        _lib.check(L.gnnmp_maze_rounds_carry(ctypes.byref(store.struct), A, g['slot_of'].data_ptr(), node_ptr.data_ptr(),
+                                             edge_ptr.data_ptr(), success.data_ptr(), n_expl.data_ptr(), expl.data_ptr(),
+                                             prev.data_ptr(), n_pairs.data_ptr(), ee.data_ptr(), plen.data_ptr(), path.data_ptr(),
+                                             checks.data_ptr(), status.data_ptr(), st), 'gnnmp_maze_rounds_carry')
+    return status
+
+
+@torch.no_grad()
+def plan_maze_rounds_batch(problems, model, device, seeds, batch=500, t_max=500, k=30, loop=5, model_s=None, smooth_iters=5,
+                           timings=None):
+    """The general loop of ``explore`` (eval_gnn.py:191-247) for many maze problems at once (point robot or stick robot, by the
+    width of ``init_state``), every problem on its OWN sample stream: the draws of problem i are
+    ``np.random.RandomState(seeds[i]).uniform(-LIMITS, LIMITS, (m, dim))`` -- the values ``np.random.seed(seeds[i])`` followed by
+    the reference's one-by-one ``uniform_sample`` calls gives -- so its result is what ``np.random.seed(seeds[i]); explore(...)``
+    of that problem alone computes, whatever other problems are in the batch.  The global numpy generator is not touched.
+
+    Round r of ALL unfinished problems is one batch: rejection sampling that appends to per-problem pools
+    (``gnnmp_maze_sample_streams``), node rows and carried trees in the round's layout (``gnnmp_maze_rounds_gather``), kNN
+    graphs, one explorer forward, greedy expansion (``gnnmp_maze_explore_ex``), trees / pairs / paths back into the store
+    (``gnnmp_maze_rounds_carry``).  A problem stops on success or when ``batch + len(free) - 2 > t_max``.  Between rounds the
+    host reads two small arrays: the sampler's status / used / collided counts (they size the next block and the node rows) and
+    the success flags; the graph build reads its edge count as before.  Trees, pairs and parents never visit Python.
+    With ``model_s`` the solved problems go through the smoothing stage on the device afterwards.
+
+    Returns one dict per problem with the fields of :func:`explore_maze_batch` plus ``rounds``; ``c_explore`` = sampling checks
+    + explore checks over all rounds, ``explored_edges`` the full pair list."""
+    from .batch import GraphBatch
+    from .graph_build import build_edges_gpu, k1_of
+
+    def mark(name, t_prev):
+        if timings is None:
+            return t_prev
+        torch.cuda.current_stream().synchronize()
+        now = time.perf_counter()
+        timings[name] = timings.get(name, 0.) + now - t_prev
+        return now
+    B, n, t_max = len(problems), int(batch), int(t_max)
+    if B == 0:
+        return []
+    if len(seeds) != B:
+        raise ValueError('plan_maze_rounds_batch: one seed per problem')
+    if n < 1 or n > t_max:
+        raise ValueError('plan_maze_rounds_batch: 1 <= batch <= t_max')
+    tm = time.perf_counter()
+    dev = torch.device(device)
+    dim = _problems_dim(problems)
+    cls = _maze_class(dim)
+    limits = np.asarray(cls.SAMPLE_LIMITS, dtype=np.float64)
+    envs = []
+    for pr in problems:
+        env = cls(np.asarray(pr['map'])[None], np.asarray(pr['init_state'])[None], np.asarray(pr['goal_state'])[None])
+        env.init_new_problem(0)
+        envs.append(env)
+    cap = -(-t_max // n) * n
+    store = MazeRoundsStore(B, cap, rounds_pair_cap(n, t_max, k), dim, dev)
+    maps = torch.from_numpy(np.ascontiguousarray(np.asarray([np.asarray(pr['map'], dtype=np.float64) for pr in problems]))).to(dev)
+    init64 = torch.from_numpy(np.ascontiguousarray(np.asarray([np.asarray(e.init_state, dtype=np.float64).reshape(dim) for e in envs]))).to(dev)
+    goal64 = torch.from_numpy(np.ascontiguousarray(np.asarray([np.asarray(e.goal_state, dtype=np.float64).reshape(dim) for e in envs]))).to(dev)
+    goals32 = goal64.to(torch.float32)
+    obs = [np.asarray(e.obstacles).reshape(-1, 2) for e in envs]
+    ocount = np.array([o.shape[0] for o in obs], dtype=np.int64)
+    optr_all = np.zeros(B + 1, dtype=np.int64)
+    optr_all[1:] = np.cumsum(ocount)
+    obs_all = torch.from_numpy(np.ascontiguousarray(np.concatenate(obs), dtype=np.float32)).to(dev)
+    gens = [np.random.RandomState(int(s) & 0xffffffff) for s in seeds]
+    bufs = [np.zeros((0, dim))] * B                                      # drawn, not yet consumed
+    samp_checks = torch.zeros(B, dtype=torch.int64, device=dev)
+    n_coll_h = np.zeros(B, dtype=np.int64)
+    rounds = np.zeros(B, dtype=np.int64)
+    act = np.arange(B)
+    done_rounds = 0
+    with torch.cuda.device(dev):
+        while True:
+            # ---- sampling: a block per active problem from its own generator, longer for whoever ran out
+            pending, want = act, int(n * _DRAWS_PER_FREE[dim - 2] * 1.25) + 64
+            act_mask = np.zeros(B, dtype=np.uint8)
+            act_mask[act] = 1
+            act_mask_d = torch.from_numpy(act_mask).to(dev)
+            drawn = consumed = 0
+            while pending.size:
+                counts = np.zeros(B, dtype=np.int64)
+                for i in pending:
+                    short = want - bufs[i].shape[0]
+                    if short > 0:
+                        bufs[i] = np.concatenate((bufs[i], gens[i].uniform(-limits, limits, (short, dim))))
+                    counts[i] = bufs[i].shape[0]
+                att_ptr = np.zeros(B + 1, dtype=np.int64)
+                att_ptr[1:] = np.cumsum(counts)
+                att = torch.from_numpy(np.concatenate([bufs[i] for i in pending])).to(dev)
+                mask = np.zeros(B, dtype=np.uint8)
+                mask[pending] = 1
+                mask_d = torch.from_numpy(mask).to(dev)
+                used, checks, status = maze_sample_streams(store, att, att_ptr, maps, init64, goal64, n, active=mask_d)
+                samp_checks += checks * mask_d                           # (a problem that ran out reports 0)
+                status_h, used_h, ncoll = torch.stack((status, used, store.n_coll)).cpu().numpy()
+                if (status_h[pending] > 1).any():
+                    raise RuntimeError('gnnmp_maze_sample_streams: no room in the pools of problem(s) %s'
+                                       % pending[status_h[pending] > 1].tolist())
+                for i in pending:
+                    if status_h[i] == 0:
+                        bufs[i] = bufs[i][used_h[i]:]
+                        n_coll_h[i] = ncoll[i]
+                        drawn += n
+                        consumed += int(used_h[i])
+                pending = pending[status_h[pending] == 1]
+                want *= 2
+            _DRAWS_PER_FREE[dim - 2] = max(1.5, 0.5 * _DRAWS_PER_FREE[dim - 2] + 0.5 * consumed / max(drawn, 1))
+            tm = mark('sampling', tm)
+            # ---- this round's graphs
+            A, nf = int(act.size), 2 + (done_rounds + 1) * n
+            everyone = A == B
+            act_d = None if everyone else torch.from_numpy(act).to(dev)
+            g = maze_rounds_gather(store, A, A * nf + int(n_coll_h[act].sum()), active=None if everyone else act_mask_d)
+            k1 = torch.full((A,), k1_of(k, nf), dtype=torch.int32, device=dev)
+            ei, edge_ptr = build_edges_gpu(g['v'], g['node_ptr'], g['n_free'], k1)
+            tm = mark('graph_build', tm)
+            if everyone:
+                obs_r, optr = obs_all, optr_all
+            else:
+                oc = ocount[act]
+                optr = np.zeros(A + 1, dtype=np.int64)
+                optr[1:] = np.cumsum(oc)
+                take = np.arange(optr[-1], dtype=np.int64) + np.repeat(optr_all[act] - optr[:-1], oc)
+                obs_r = obs_all[torch.from_numpy(take).to(dev)]
+            gb = GraphBatch(g['v'], goals32 if everyone else goals32[act_d], obs_r, ei, g['node_ptr'], edge_ptr,
+                            torch.from_numpy(optr.astype(np.int32)).to(dev), int(ocount[act].max()))
+            scores = model.forward_batch(gb, loop)
+            tm = mark('explorer_forward', tm)
+            cstat = maze_rounds_explore(store, g, ei, edge_ptr, scores, maps if everyone else maps[act_d].contiguous(),
+                                        goal64 if everyone else goal64[act_d].contiguous())
+            flags = torch.cat((store.tree_success, cstat)).cpu().numpy()     # the one read that decides who continues
+            tm = mark('greedy_explore', tm)
+            if flags[B:].any():
+                raise RuntimeError('gnnmp_maze_rounds_carry: pair list or tree beyond its slot for problem(s) %s'
+                                   % act[flags[B:] != 0].tolist())
+            done_rounds += 1
+            rounds[act] = done_rounds
+            if n + nf - 2 > t_max:                                       # eval_gnn.py:239-240
+                break
+            act = act[flags[:B][act] == 0]
+            if not act.size:
+                break
+        # ---- results: the store comes back in one go
+        success, n_expl, n_pairs, plen, n_free_h, ncoll_h = torch.stack(
+            (store.tree_success, store.tree_n_explored, store.tree_n_pairs, store.tree_path_len, store.n_free, store.n_coll)).cpu().tolist()
+        chk = torch.stack((store.tree_checks, samp_checks)).cpu().tolist()
+        expl, paths = torch.stack((store.tree_explored, store.tree_path)).cpu().numpy()
+        live = torch.arange(store.pair_cap, device=dev)[None, :] < store.tree_n_pairs[:, None]
+        pairs = store.tree_pairs[live].cpu().numpy()                     # [sum n_pairs, 2], problem after problem
+        fp, cp = store.free_pool.cpu().numpy(), store.coll_pool.cpu().numpy()
+        vs_np = [np.concatenate((fp[b, :n_free_h[b]], cp[b, :ncoll_h[b]])) for b in range(B)]
+        smoothed = {}
+        if model_s is not None and any(success):
+            nptr = np.concatenate(([0], np.cumsum([x.shape[0] for x in vs_np]))).tolist()
+            g = maze_rounds_gather(store, B, nptr[-1], trees=False)
+            path_all = np.zeros(nptr[-1], dtype=np.int32)
+            for b in range(B):
+                path_all[nptr[b]:nptr[b] + plen[b]] = paths[b, :plen[b]]
+            smoothed = _smooth_maze_batch(model_s, [b for b in range(B) if success[b]], g['v'], nptr, n_free_h, path_all, plen,
+                                          maps, smooth_iters, dev)
+            tm = mark('smoothing', tm)
+    out, po = [], 0
+    for b in range(B):
+        ok = bool(success[b])
+        envs[b].collision_check_count = int(chk[1][b])
+        out.append({'success': ok, 'explored': expl[b, :n_expl[b]].copy(), 'explored_edges': pairs[po:po + n_pairs[b]],
+                    'c_explore': int(chk[0][b]) + int(chk[1][b]),
+                    'path': vs_np[b][paths[b, :plen[b]]] if ok else np.zeros((0, dim), dtype=np.float32), 'free': None,
+                    'env': envs[b], 'v': torch.from_numpy(vs_np[b]), 'n_free': n_free_h[b], 'rounds': int(rounds[b])})
+        po += n_pairs[b]
+        if model_s is not None:
+            sp, cs = smoothed.get(b, (np.zeros((0, dim), dtype=np.float32), 0))
+            out[-1].update(smooth_path=sp, c_smooth=cs)
+    mark('results', tm)
+    return out
+
+
+def stream_seeds(seed, indexes):
+    """Default per-problem seeds of :func:`eval_gnn_device_streams`: ``(seed + 0x9E3779B1 * (index + 1)) mod 2**32``."""
+    return [(int(seed) + 0x9E3779B1 * (int(i) + 1)) % (1 << 32) for i in indexes]
+
+
+def eval_gnn_device_streams(env, indexes, model, model_s=None, seed=1234, seeds=None, batch=500, t_max=500, k=30, device='cuda',
+                            loop=5, chunk=256, rows_out=None, details_out=None, timings=None):
+    """:func:`eval_gnn_device_rounds` with one sample stream PER PROBLEM (:func:`plan_maze_rounds_batch`, ``chunk`` problems per
+    batch): same return dict, ``rows_out`` / ``details_out`` filled the same way.  Problem ``indexes[i]`` draws from
+    ``np.random.RandomState(seeds[i])``; default ``seeds[i] = (seed + 0x9E3779B1 * (indexes[i] + 1)) mod 2**32``
+    (:func:`stream_seeds`).  Its outcome is what ``np.random.seed(seeds[i])`` followed by the reference's ``explore`` of that
+    problem alone gives.  The numbers therefore DIFFER from :func:`eval_gnn_device_rounds` and from the reference's ``eval_gnn``,
+    which walk one global stream problem after problem -- other samples of the same distribution -- and in exchange they do not
+    depend on the order of ``indexes``, on ``chunk`` or on how the problems are sharded over ranks: no rank has to wind a
+    generator past other ranks' problems.  The global numpy generator is left alone.  ``chunk`` bounds the device memory of
+    the per-problem store (:class:`MazeRoundsStore`: about 0.5 MB per problem at the default settings)."""
+    model.eval()                       # eval_gnn.py:109-110
+    if model_s is not None:
+        model_s.eval()
+    indexes = list(indexes)
+    seeds = stream_seeds(seed, indexes) if seeds is None else list(seeds)
+    dim = env.config_dim
+    sol = []
+    for c0 in range(0, len(indexes), max(int(chunk), 1)):
+        part = indexes[c0:c0 + max(int(chunk), 1)]
+        pr = [dict(map=env.maps[i], init_state=env.init_states[i], goal_state=env.goal_states[i]) for i in part]
+        res = plan_maze_rounds_batch(pr, model, device, seeds[c0:c0 + len(part)], batch=batch, t_max=t_max, k=k, loop=loop,
+                                     model_s=model_s, timings=timings)
+        for r in res:
+            p = r['path'] if r['success'] else np.zeros((0, dim), dtype=np.float32)
+            sp, cs = (r.get('smooth_path', p), r.get('c_smooth', 0)) if r['success'] else (p, 0)
+            sol.append((int(r['success']), path_cost(p), path_cost(sp), r['c_explore'], cs, len(p), len(r['explored']), r['rounds']))
+            if rows_out is not None:
+                rows_out.append(sol[-1][:7])
+            if details_out is not None:
+                details_out.append({'success': r['success'], 'env': r['env'], 'v': r['v'].numpy(), 'n_free': r['n_free'],
+                                    'path': p, 'smooth_path': sp, 'c_smooth': cs})
+    n_success = sum(s[0] for s in sol)
+    return {'n_success': n_success, 'collision_explore': float(np.mean([s[3] for s in sol])),
+            'collision': float(np.mean([s[3] + s[4] for s in sol])),
+            'solution_cost': float(sum(s[2] for s in sol if s[0])) / max(n_success, 1), 'rounds': [s[7] for s in sol]}

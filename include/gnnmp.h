@@ -22,6 +22,8 @@
  *       explore()'s rejection sampling (classification + compaction)   eval_gnn.py:180-184, environment/maze_env.py
  *   gnnmp_stick_sample
  *       the same for MazeEnv(dim=3): _stick_in_free_space per draw     environment/maze_env.py:279-314
+ *   gnnmp_maze_sample_streams / gnnmp_maze_rounds_gather / gnnmp_maze_rounds_carry
+ *       explore()'s resample rounds for a batch, one sample stream per problem     eval_gnn.py:191-247
  *   gnnmp_maze_steer / gnnmp_stick_steer
  *       proposed_path_smootherv2 (steering of the smoothing stage)  smoother.py:194-216
  *   gnnmp_maze_explore_workspace_bytes / gnnmp_maze_explore / gnnmp_maze_explore_ex
@@ -503,6 +505,101 @@ int gnnmp_maze_sample(const gnnmp_maze_sample_batch* batch, int64_t* cursor, flo
  * MazeEnv.collision_check_count grows by during sample_n_points.  One launch on hip_stream, no synchronisation, no allocation. */
 int gnnmp_stick_sample(const gnnmp_maze_sample_batch* batch, int64_t* cursor, float* v_out, int32_t* node_ptr_out,
                        int32_t* used_out, int64_t* checks_out, int32_t* ok_out, void* hip_stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Resample rounds for a whole batch (the general loop of explore(), eval_gnn.py:191-247): every problem owns its sample
+ * stream -- what np.random.seed(s_b) before explore() of problem b alone gives -- so a problem's result no longer depends on
+ * the problems before it, and round r of all unfinished problems is one batch around gnnmp_maze_explore_ex:
+ *   gnnmp_maze_sample_streams   sample_n_points + the two truncations of the collided list      eval_gnn.py:180, 241-245
+ *   gnnmp_maze_rounds_gather    the round's node rows (create_data's v) and the carried trees    eval_gnn.py:150-158, 235-247
+ *   gnnmp_maze_rounds_carry     the round's trees, pairs, paths and checks back into the store
+ * The per-problem state lives in caller-allocated device arrays with one fixed-size slot per problem
+ * (gnnmp_maze_rounds_state); `cap` = t_max rounded up to a multiple of the per-round sample count.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct {
+    int32_t n_problems, cap, pair_cap;
+    float* free_pool;            /* [B, cap + 2, dim]  rows 0 / 1 = init / goal state, then the free draws in draw order */
+    float* coll_pool;            /* [B, cap + 2, dim]  the rejected draws the reference keeps                            */
+    int32_t* n_free;             /* [B]  rows in use; 0 = nothing sampled yet                                           */
+    int32_t* n_coll;             /* [B]                                                                                 */
+    int32_t* tree_explored;      /* [B, cap + 2]  explored node ids in order (only free nodes are ever explored)         */
+    int32_t* tree_prev;          /* [B, cap + 2]  parent by node id                                                      */
+    int32_t* tree_n_explored;    /* [B]  a fresh tree is n_explored = 1, explored[0] = prev[0] = 0                       */
+    int32_t* tree_pairs;         /* [B, pair_cap, 2]  the (a, b) pairs recorded so far; fresh = one pair [0, 0]          */
+    int32_t* tree_n_pairs;       /* [B]                                                                                 */
+    int32_t* tree_success;       /* [B]  success flag of the problem's last round                                       */
+    int32_t* tree_path_len;      /* [B]                                                                                 */
+    int32_t* tree_path;          /* [B, cap + 2]  node ids start -> goal of a solved problem                             */
+    int64_t* tree_checks;        /* [B]  collision checks of the explore stage, summed over the rounds                   */
+} gnnmp_maze_rounds_state;
+
+/* Rejection sampling that APPENDS.  Problem b owns the draws [att_ptr[b], att_ptr[b + 1]) of attempts [n_attempts, dim]
+ * (float64, the host's uniform(-LIMITS, LIMITS) values in draw order, as for gnnmp_maze_sample / gnnmp_stick_sample; dim 2 =
+ * point robot, 3 = stick robot with gnnmp_stick_sample's classification and check counts).  One workgroup per problem, one
+ * launch on hip_stream; no allocation, no synchronisation, no atomics on global memory, deterministic.
+ * n_free[b] == 0 on entry (round 0): init / goal go to rows 0 / 1 of free_pool, the n_free free draws behind them, and the
+ * first min(rejected, n_free) rejected draws are kept (eval_gnn.py:180: the cut happens before init / goal join).
+ * Later rounds: n_free free draws are appended, and rejected draws are appended while n_coll[b] < the NEW n_free[b] (init /
+ * goal counted: (collided + new)[:len(free)], eval_gnn.py:243-245 -- the cap goes n, 2n + 2, 3n + 2, ...; a round's own
+ * rejected draws are not first cut to n).
+ * used_out [B]: draws consumed; checks_out [B]: their collision checks (dim 2: = used); status_out [B]: 0 = done; 1 = the
+ * problem's block ended before its n_free-th free draw: its pools and counts are untouched (used / checks 0) and the other
+ * problems complete -- hand that problem a longer block and call again with the others masked out; 2 = n_free more rows
+ * would not fit cap, or the block lies outside attempts: untouched as well.  active [B] (uint8) or NULL = all: a problem
+ * with 0 is skipped entirely (none of its outputs is written).  att_ptr_host: optional host copy of att_ptr; when given it
+ * is checked (ascending, inside [0, n_attempts]).
+ * Returns GNNMP_ERR_DIMS for dim not 2 / 3, GNNMP_ERR_NULL for NULL pointers, GNNMP_ERR_ARG for n_problems / width / n_free
+ * < 1, cap < n_free, n_attempts < 0 or a bad att_ptr_host; nothing is launched then.  What only the device can see (the
+ * counts, att_ptr without a host copy) is guarded by the kernel itself: status 2, never a write outside a slot. */
+typedef struct {
+    int32_t n_problems, width, n_free, cap;
+    int64_t n_attempts;
+    const double* attempts;      /* [n_attempts, dim]                                          */
+    const int64_t* att_ptr;      /* [B + 1]                                                    */
+    const int64_t* att_ptr_host; /* [B + 1] on the HOST, or NULL                               */
+    const double* maps;          /* [B, width, width]                                          */
+    const double* init_states;   /* [B, dim]                                                   */
+    const double* goal_states;   /* [B, dim]                                                   */
+    const uint8_t* active;       /* [B] or NULL                                                */
+} gnnmp_maze_streams_batch;
+int gnnmp_maze_sample_streams(const gnnmp_maze_streams_batch* batch, int32_t dim, float* free_pool, int32_t* n_free,
+                              float* coll_pool, int32_t* n_coll, int32_t* used_out, int64_t* checks_out, int32_t* status_out,
+                              void* hip_stream);
+
+/* The node rows of a round.  For the A = n_active problems with active[b] != 0 (NULL = all), in slot order: v_out = free rows
+ * then collided rows, compact; node_ptr_out [A + 1]; n_free_out [A]; slot_out [A] = the slot of the round's j-th problem -- the
+ * layout gnnmp_graph_build, gnnmp_batch and gnnmp_maze_explore_ex read.  The [A] / [A + 1] arrays are the caller's, sized from
+ * n_active: should `active` hold more set entries than that, the slots beyond the first n_active are left out (nothing of
+ * theirs is written anywhere); with fewer, the entries behind the last one keep what the caller put there.  The offsets depend on what the sampler just found,
+ * so they are summed on the device (every workgroup adds up the counts of the active slots before its own); nothing is read
+ * back.  v_rows: rows v_out can hold (a problem that would not fit is left out of v_out; its node_ptr entry is still
+ * written).  resume_out (or NULL): device arrays the caller allocated -- n_explored [A], explored [v_rows], prev [v_rows],
+ * n_pairs [A], pair_ptr [A + 1] (pair_ptr[j] = slot * pair_cap: the slots are not adjacent, so pair_ptr[A] = n_problems *
+ * pair_cap only closes the array); `pairs` is ignored -- that receive the trees of the store at this round's offsets:
+ * together with pairs = state->tree_pairs they ARE the gnnmp_maze_resume of the round's gnnmp_maze_explore_ex call (with the
+ * fresh tree above in the store, round 0 runs in resume mode too and every round's explored_edges hold only its new
+ * pairs).  One launch.  GNNMP_ERR_DIMS / GNNMP_ERR_NULL / GNNMP_ERR_ARG (n_problems < 1, cap < 1, pair_cap < 1 or
+ * n_problems * pair_cap beyond 2^30, v_rows < 0, n_active outside [1, n_problems]). */
+int gnnmp_maze_rounds_gather(const gnnmp_maze_rounds_state* state, int32_t dim, const uint8_t* active, int32_t n_active,
+                             int64_t v_rows, float* v_out, int32_t* node_ptr_out, int32_t* n_free_out, int32_t* slot_out,
+                             const gnnmp_maze_resume* resume_out_or_null, void* hip_stream);
+
+/* After gnnmp_maze_explore_ex (resume mode, prev_out given) on the round's n_active problems: problem j's tree (explored
+ * order; parents by node id -- free-node ids are stable across rounds, only node_ptr moves), path and flags replace those of
+ * slot slot_of[j] (NULL = j), its checks are added, and its new pairs -- n_pairs[j] of them at int offset
+ * 2 * (2 * edge_ptr[j] + j) of explored_edges -- are appended to the slot's pair list.  The next gnnmp_maze_rounds_gather
+ * places the trees at the next round's offsets.
+ * Capacity of the pair list: a step of the greedy loop picks a live cell (a, b) with a explored, b a free node not yet
+ * explored, and whatever the outcome the unordered pair {a, b} is dead for the rest of the round; it records 2 pairs.  A
+ * round on F free nodes with k1 neighbours has at most 2 * k1 * F unordered free-free edges (k1 per node from each of the two
+ * kNN graphs), so pair_cap = 1 + sum over the rounds of 4 * k1_r * F_r always suffices: a derived bound, not the edge
+ * counts.  status_out [n_active]: bit 0 = the new pairs did not fit pair_cap (none appended: the caller raises), bit 1 = a
+ * node id or count beyond cap + 2 (skipped).  Nothing is ever written outside the slot.  One wave per problem, one launch. */
+int gnnmp_maze_rounds_carry(const gnnmp_maze_rounds_state* state, int32_t n_active, const int32_t* slot_of,
+                            const int32_t* node_ptr, const int32_t* edge_ptr, const int32_t* success,
+                            const int32_t* n_explored, const int32_t* explored, const int32_t* prev, const int32_t* n_pairs,
+                            const int32_t* explored_edges, const int32_t* path_len, const int32_t* path, const int64_t* checks,
+                            int32_t* status_out, void* hip_stream);
 
 /* ------------------------------------------------------------------------------------------
  * Supervision of the explorer's training step (train_explorer.py:124-176): edge labels, shortest paths to the goal,
