@@ -716,7 +716,7 @@ PrePlan plan_pre(int D, int P, int ot_max, int enc_size, int out_size, bool use_
     const int att = att_staged(D, P);
     int wr = enc_size > out_size ? enc_size : out_size;
     if (use_obs && att > wr) wr = att;
-    wr = (wr + 3) & ~3;
+    wr = ((wr + 3) & ~3) + 32;                            // + the tail mask of the graph (explorer_kernels.hip kTailMask)
     PrePlan p;
     p.wregion = wr;
     p.waves = (D == 32) ? 4 : 8;
@@ -905,7 +905,7 @@ int forward_impl(const gnnmp_explorer* h, const gnnmp_batch* b, int loop, int us
     PreParams pp[2];
     PrePlan plan[2];
     size_t res_lds[2] = {0, 0};                            // LDS bytes of the resident variant, 0 = not applicable
-    const size_t res_bytes = ((size_t)3 * (att_staged(D, P) + 6 * vec_floats(D)) + (size_t)3 * c.kv_stride) * sizeof(float) + 64;
+    const size_t res_bytes = ((size_t)3 * (att_staged(D, P) + 6 * vec_floats(D)) + (size_t)3 * c.kv_stride) * sizeof(float) + 64 + 128;   // + tile counter, tail mask
     const bool resident_ok = ((D == 32 && P == 0) || P == 1) && use_obs && res_bytes <= 163840 && h->resident;
     for (int edge = 0; edge < 2; ++edge) {
         PreParams& p = pp[edge];

@@ -26,6 +26,8 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
+template <int V> struct IntTag { static constexpr int value = V; };      // compile-time selector handed to a generic lambda
+
 constexpr int kTile = 32;             // rows per wave, features per tile
 constexpr int kATile = 1024;          // floats in one 32x32 A tile
 
@@ -185,31 +187,40 @@ __device__ __forceinline__ void mfma_tile_p(const float* a, const BOp<P>& x, f32
     }
 }
 
-// only K groups 0..nq-1 (8 obstacles each, 4 groups per tile) can be non-zero in x
+// only K groups 0..nq-1 (8 obstacles each, 4 groups per tile) can be non-zero in x; nq >= 1
 template <int P>
 __device__ __forceinline__ void mfma_tile_q_p(const float* a, const BOp<P>& x, f32x16& acc, int lane, int nq) {
-    if (nq >= 4) { mfma_tile_p<P>(a, x, acc, lane); return; }
     if constexpr (P == 0) {
-        for (int q = 0; q < nq; ++q) {
-            const f32x4 w = *reinterpret_cast<const f32x4*>(a + (q * 64 + lane) * 4);
-            f32x4 xb;
-            switch (q) {
-                case 0: xb = f32x4{x.v[0], x.v[1], x.v[2], x.v[3]}; break;
-                case 1: xb = f32x4{x.v[4], x.v[5], x.v[6], x.v[7]}; break;
-                default: xb = f32x4{x.v[8], x.v[9], x.v[10], x.v[11]}; break;
-            }
+        // one straight chain in the k order of mfma_tile_p with wave-uniform forward exits between its quarters: the B operands are
+        // x's own registers and the accumulator is updated in place.  (A quarter loop with a dynamic trip count picked its B operands
+        // through v_mov shuffles and, joined with the 16-MFMA form, made the compiler keep the accumulator in two register ranges:
+        // 16 v_mov_b64 per obstacle tile in kernels where every vector instruction costs MFMA issue time)
+        f32x4 w[4];                                             // the whole tile is in LDS: all four reads go out before the first MFMA
 #pragma unroll
-            for (int cidx = 0; cidx < 4; ++cidx)
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(w[cidx], xb[cidx], acc, 0, 0, 0);
+        for (int q = 0; q < 4; ++q) w[q] = *reinterpret_cast<const f32x4*>(a + (q * 64 + lane) * 4);
+        auto quarter = [&](const int q) __attribute__((always_inline)) {
+#pragma unroll
+            for (int c = 0; c < 4; ++c) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(w[q][c], x.v[q * 4 + c], acc, 0, 0, 0);
+        };
+        quarter(0);
+        if (nq > 1) {
+            quarter(1);
+            if (nq > 2) {
+                quarter(2);
+                if (nq > 3) quarter(3);
+            }
         }
-    } else if constexpr (P == 1) {
+        return;
+    }
+    if (nq >= 4) { mfma_tile_p<P>(a, x, acc, lane); return; }
+    if constexpr (P == 1) {
         const bf16x8 w0 = *reinterpret_cast<const bf16x8*>(a + lane * 4);
         acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w0, x.lo, acc, 0, 0, 0);            // groups 0, 1
         if (nq > 2) {
             const bf16x8 w1 = *reinterpret_cast<const bf16x8*>(a + (64 + lane) * 4);
             acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w1, x.hi, acc, 0, 0, 0);        // groups 2, 3
         }
-    } else {
+    } else if constexpr (P == 2) {
         constexpr int PW[6] = {2, 0, 1, 1, 0, 0}, PX[6] = {0, 2, 1, 0, 1, 0};
 #pragma unroll
         for (int t = 0; t < 6; ++t) {

@@ -998,11 +998,20 @@ __global__ __launch_bounds__(256) void obs_kernel(ObsParams p, NodeF64Params q, 
 
 // =====================================================================================================
 // attention Block on the map rows held in registers (model.py:164-181 + map_feed :212-216).
-// wl: LDS copy of AttBlob<D>; kvl: LDS K/V chunk region; kvg: this (graph, block)'s slab in global.
+// wl: LDS copy of AttBlob<D>; kvl: LDS K/V chunk region; kvg: this (graph, block)'s slab in global;
+// maskl: the graph's tail mask in LDS (write_tail_mask; read in the exact-fp32 mode only).
 // =====================================================================================================
+// The padding mask of a graph's last obstacle tile as the C operand its logit chain starts from: kTailMask floats in obstacle order,
+// 0 for the O % 32 valid obstacles, -inf behind them.  Lane half h reads registers 4q..4q+3 (obstacles phi(4q + c, h) = 8q + 4h + c) as
+// one 16-byte piece.  Written once per (workgroup, graph) by the first 32 threads; the caller's barrier publishes it.
+constexpr int kTailMask = 32;
+__device__ __forceinline__ void write_tail_mask(float* maskl, int O) {
+    if (threadIdx.x < kTailMask) maskl[threadIdx.x] = ((int)threadIdx.x < (O & 31)) ? 0.f : -INFINITY;
+}
+
 // MAYSKIP && skip (workgroup-uniform): m already went through the attention sub-block (node_f64_body), only map_feed runs
 template <int D, int P, bool MAYSKIP = false>
-__device__ __forceinline__ void attention_block(const float* wl, const float* wg, float* kvl, const float* kvg, int O,
+__device__ __forceinline__ void attention_block(const float* wl, const float* wg, float* kvl, const float* kvg, const float* maskl, int O,
                                                 int ot_max, int ot_chunk, f32x16 (&m)[D / 32], int lane, bool skip = false) {
     constexpr int NT = D / 32;
     constexpr int TF = Prec<P>::TF;
@@ -1044,6 +1053,61 @@ __device__ __forceinline__ void attention_block(const float* wl, const float* wg
             stage(kvl + chunk_floats, kvg + (size_t)(ot_max + c0) * NT * TF, (c1 - c0) * NT * TF);
             __syncthreads();
         }
+        if constexpr (P == 0) {
+            // Exact fp32: every vector instruction costs MFMA issue time (tools/microbench/mfma_chain.hip), so the one tile that can
+            // hold padding obstacles is peeled off the loop.  TAIL = false: a full tile, no mask, the 16-MFMA PV chain over one
+            // accumulator in place (the two PV forms behind one join cost a copy of the accumulator into a second register range and
+            // back, per tile).  TAIL = true: the last tile when O % 32 != 0.  Same order of operations in both: running maximum,
+            // exp2, tree_sum, conditional rescale, PV.
+            auto tile_step = [&](const int ot, auto tail) __attribute__((always_inline)) {
+                constexpr bool TAIL = decltype(tail)::value != 0;
+                const float* ko = kvl + (size_t)(ot - c0) * NT * TF;
+                const float* vo = kvl + chunk_floats + (size_t)(ot - c0) * NT * TF;
+                f32x16 s;
+                if constexpr (TAIL) {
+                    // the logit chain starts from 0 (valid obstacle) or -inf (padding) instead of the literal 0: a finite product
+                    // sum added to -inf is -inf, which is all the mask has to do
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        const f32x4 c = *reinterpret_cast<const f32x4*>(maskl + q * 8 + h * 4);
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) s[q * 4 + i] = c[i];
+                    }
+                } else {
+                    s = splat16(0.f);
+                }
+#pragma unroll
+                for (int t = 0; t < NT; ++t) mfma_tile_p<P>(ko + t * TF, qop[t], s, lane);
+                float tmax = s[0];
+#pragma unroll
+                for (int r = 1; r < 16; ++r) tmax = fmaxf(tmax, s[r]);
+                tmax = xmax(tmax);
+                const float nmx = fmaxf(mx, tmax);
+                const float off = -nmx * cs;
+                s = s * cs + off;                           // packed fmas
+#pragma unroll
+                for (int r = 0; r < 16; ++r) s[r] = __builtin_amdgcn_exp2f(s[r]);
+                const float ps = tree_sum(s);
+                const BOp<P> pop(s);
+                if (__builtin_amdgcn_ballot_w64(nmx != mx) != 0) {      // some row's maximum moved: rescale (alpha = 1 elsewhere)
+                    const float alpha = __builtin_amdgcn_exp2f((mx - nmx) * cs);
+                    psum *= alpha;
+#pragma unroll
+                    for (int t = 0; t < NT; ++t) acc[t] *= alpha;
+                }
+                psum += ps;
+#pragma unroll
+                for (int t = 0; t < NT; ++t) {
+                    if constexpr (TAIL) mfma_tile_q_p<P>(vo + t * TF, pop, acc[t], lane, (O - ot * 32 + 7) >> 3);
+                    else mfma_tile_p<P>(vo + t * TF, pop, acc[t], lane);
+                }
+                mx = nmx;
+            };
+            const int nfull = min(c1, O >> 5);
+            for (int ot = c0; ot < nfull; ++ot) tile_step(ot, IntTag<0>());
+            if (nfull < c1) tile_step(nfull, IntTag<1>());          // O % 32 != 0 and this is the final chunk: nfull == OT - 1
+        } else {
+        // bf16 / bf16x3: the loop as it was (the matrix pipe overlaps with the vector work there), every decision at run time
         for (int ot = c0; ot < c1; ++ot) {
             const float* ko = kvl + (size_t)(ot - c0) * NT * TF;
             const float* vo = kvl + chunk_floats + (size_t)(ot - c0) * NT * TF;
@@ -1105,6 +1169,7 @@ __device__ __forceinline__ void attention_block(const float* wl, const float* wg
             for (int t = 0; t < NT; ++t) mfma_tile_q_p<P>(vo + t * TF, pop, acc[t], lane, nq);
             mx = nmx;
         }
+        }
     }
     const float den = xsum(psum);                                // reciprocal: hardware estimate + one Newton step
     float inv = __builtin_amdgcn_rcpf(den);
@@ -1125,6 +1190,7 @@ __global__ __launch_bounds__(WAVES * 64) void pre_kernel(PreParams p) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float* wl = lds;
     float* kvl = lds + p.wregion;
+    float* maskl = kvl - kTailMask;                       // the last floats of the weight region: beyond every staged blob
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, h = lane >> 5, j = lane & 31;
     // XCD-aware order (see XcdWalk): XCD b % 8 works on a contiguous eighth of the workgroup tiles, so a
     // graph's K/V slabs and weights are staged from ONE XCD's L2
@@ -1185,6 +1251,7 @@ __global__ __launch_bounds__(WAVES * 64) void pre_kernel(PreParams p) {
         const int O = min(p.obs_ptr[g + 1] - p.obs_ptr[g], p.ot_max * 32);
         const int OT = (O + 31) / 32;
         const int chunk_floats = p.ot_chunk * NT * TF;
+        if constexpr (P == 0) write_tail_mask(maskl, O);  // published by the barriers below
         for (int b = 0; b < 3; ++b) {
             const float* kvg = p.kv + (size_t)(g * 3 + b) * p.kv_stride;
             __syncthreads();
@@ -1194,7 +1261,7 @@ __global__ __launch_bounds__(WAVES * 64) void pre_kernel(PreParams p) {
             stage(kvl, kvg, c1 * NT * TF);
             stage(kvl + chunk_floats, kvg + (size_t)p.ot_max * NT * TF, c1 * NT * TF);
             __syncthreads();
-            attention_block<D, P, !EDGE>(wl, attg, kvl, kvg, O, p.ot_max, p.ot_chunk, m, lane, !EDGE && b == 0 && p.m0 != nullptr);
+            attention_block<D, P, !EDGE>(wl, attg, kvl, kvg, maskl, O, p.ot_max, p.ot_chunk, m, lane, !EDGE && b == 0 && p.m0 != nullptr);
         }
     }
 
@@ -1262,7 +1329,8 @@ __device__ __forceinline__ void pre_resident_body(const PreParams& p, const int 
     float* wl = lds;                                           // [3][AB::size]: matrices AND the six vectors of a block
     float* kvl = lds + 3 * AB::size;                           // [3][kv_stride]
     int* ctr = reinterpret_cast<int*>(kvl + 3 * (size_t)p.kv_stride);
-    float* outl = reinterpret_cast<float*>(ctr) + 16;          // epilogue blob, when the launch reserved room (p.out_in_lds)
+    float* maskl = reinterpret_cast<float*>(ctr) + 16;         // [kTailMask], per graph
+    float* outl = maskl + kTailMask;                           // epilogue blob, when the launch reserved room (p.out_in_lds)
     const int lane = threadIdx.x & 63, h = lane >> 5, j = lane & 31;
     const int C = p.C;
     const int total = p.ptr_pad_total[p.G] / 32;               // padded 32-row tiles actually in use
@@ -1281,9 +1349,10 @@ __device__ __forceinline__ void pre_resident_body(const PreParams& p, const int 
         __syncthreads();                                       // previous graph's K/V no longer in use
         stage(kvl, p.kv + (size_t)g * 3 * p.kv_stride, 3 * p.kv_stride);
         if (threadIdx.x == 0) *ctr = t0;
+        const int O = min(p.obs_ptr[g + 1] - p.obs_ptr[g], p.ot_max * 32);
+        if constexpr (P == 0) write_tail_mask(maskl, O);
         __syncthreads();
         const int nbase_pad = p.node_ptr_pad[g], nbase = p.node_ptr[g];
-        const int O = min(p.obs_ptr[g + 1] - p.obs_ptr[g], p.ot_max * 32);
         while (true) {
             int tile = 0;
             if (lane == 0) tile = atomicAdd(ctr, 1);
@@ -1337,7 +1406,7 @@ __device__ __forceinline__ void pre_resident_body(const PreParams& p, const int 
             }
             for (int b = 0; b < 3; ++b)
                 attention_block<D, P, !EDGE>(wl + b * AB::size, wl + b * AB::size, kvl + (size_t)b * p.kv_stride, nullptr,
-                                   O, p.ot_max, p.ot_max, m, lane, !EDGE && b == 0 && p.m0 != nullptr);
+                                   maskl, O, p.ot_max, p.ot_max, m, lane, !EDGE && b == 0 && p.m0 != nullptr);
             if (p.om) store_row<NT>(p.om + (size_t)row * D, m, h);       // training path: frozen node_/edge_free_code
             if constexpr (EDGE) {
                 using L = OutEBlob<D, P>;
