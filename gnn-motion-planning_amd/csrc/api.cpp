@@ -279,6 +279,7 @@ struct gnnmp_explorer {
     int resident;         // use pre_resident_kernel when it fits (GNNMP_RESIDENT=0 disables)
     int resident_both;    // small batches: node and edge pre stages in one launch (GNNMP_PRE_BOTH=0 disables)
     int node_f64;         // node side block 0 in double precision (fp32-class modes; GNNMP_NODE_F64=0 disables, for attribution runs)
+    int f64_groups;       // 64-row groups per workgroup of that role: 0 = chosen per launch (GNNMP_F64_GROUPS forces 1, 4, 8, 12 or 16)
     float* w_raw_dev;     // the caller's weight blob as given (manifest order, torch row-major): the training path's view
     std::vector<Entry> man;
     std::vector<int64_t> man_off;
@@ -570,6 +571,9 @@ extern "C" int gnnmp_explorer_create(gnnmp_explorer** out, const gnnmp_explorer_
         h->resident_both = !(env2 && env2[0] == '0');
         const char* env3 = std::getenv("GNNMP_NODE_F64");
         h->node_f64 = !(env3 && env3[0] == '0');
+        const char* env4 = std::getenv("GNNMP_F64_GROUPS");
+        const int fg = env4 ? std::atoi(env4) : 0;
+        h->f64_groups = (fg == 1 || (fg >= 4 && fg <= 16 && fg % 4 == 0)) ? fg : 0;
     }
     if (e == hipSuccess) e = hipMalloc((void**)&h->w_dev, packed.size() * sizeof(float));
     if (e == hipSuccess) e = hipMemcpy(h->w_dev, packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice);
@@ -889,14 +893,31 @@ int forward_impl(const gnnmp_explorer* h, const gnnmp_batch* b, int loop, int us
         nq.v = b->v; nq.C = C; nq.node_ptr = node_ptr; nq.node_ptr_pad = q.node_ptr_pad; nq.ntile_graph = q.ntile_graph;
         nq.w = W + h->off.f64; nq.blob = F64Blob::make(D, C);
         nq.m0 = at<float>(ws, c.M0);
+        nq.n_rows = c.Npad;
+        const bool f64_role = P != GNNMP_BF16 && h->node_f64;
         nq.groups = c.Npad / 64 > 2 * h->n_cu ? 4 : 1;                          // kPad = 256 rows = 4 groups
+        if (nq.groups == 4 && f64_role) {
+            // More 256-row blocks than resident workgroups: a workgroup takes m blocks in a row when that costs no extra round --
+            // rounds(m) * m block times, the larger m on a tie: it builds the obstacle operands once per graph it meets instead of
+            // once per block.  Blocks in use from the caller's totals (exact for graphs of one size; the prefix arrays are on the
+            // device); a workgroup whose blocks belong to different graphs rebuilds where the graph changes, so any m is correct.
+            const int slots = obs_f64_slots(D, P, op, nq);
+            const long long per_graph = ((long long)b->total_nodes / c.G + kPad - 1) / kPad;
+            const long long blocks = per_graph * c.G;
+            long long best = 0;
+            for (int m = 1; m <= 4 && slots > 0; m *= 2) {
+                const long long wgs = (blocks + m - 1) / m, cost = (wgs + slots - 1) / slots * m;
+                if (m == 1 || cost <= best) { best = cost; nq.groups = 4 * m; }
+            }
+        }
+        if (h->f64_groups) nq.groups = h->f64_groups;
         {
             static const char* ord = std::getenv("GNNMP_F64_FIRST");
             // measured: cfg 2 (d = 32, 1024 double-precision workgroups = two rounds) 0.145 -> 0.139 ms with them first;
             // kuka7 fp32 (d = 64, 512 = one round) 0.153 -> 0.162 ms, so d = 64 keeps the obstacle workgroups in front
             nq.f64_first = ord ? (ord[0] != '0') : (nq.groups > 1 && D == 32);
         }
-        nq.n_wg = (P != GNNMP_BF16 && h->node_f64) ? c.Npad / (64 * nq.groups) : 0;
+        nq.n_wg = f64_role ? (c.Npad + 64 * nq.groups - 1) / (64 * nq.groups) : 0;
         use_m0 = nq.n_wg > 0;
         StageScope sc(prof, GNNMP_STAGE_OBS, st);
         HIP_TRY(launch_obs(D, P, op, nq, c.G, st));
@@ -1024,6 +1045,9 @@ extern "C" int gnnmp_explorer_debug_tap(const gnnmp_explorer* h, const gnnmp_bat
         case 3:
             HIP_TRY(launch_goal_tap(c.G, at<int>(ws, c.goal_node), at<int>(ws, c.node_ptr_pad), dst, st));
             return GNNMP_OK;
+        case 4:
+            if (h->dims.mlp_dtype == GNNMP_BF16 || !h->node_f64) return GNNMP_ERR_DIMS;      // the fp64 node role did not run
+            src = c.M0; break;
         default: return GNNMP_ERR_ARG;
     }
     HIP_TRY(launch_unpad_rows(c.G, b->total_nodes, D, b->node_ptr ? b->node_ptr : at<int>(ws, c.in_ptrs), at<int>(ws, c.node_ptr_pad),
@@ -2752,6 +2776,8 @@ bool geom_carve(const gnnmp_batch* b, int C, GeomCarve& g) {
 }
 
 }  // namespace
+
+extern "C" int gnnmp_prep_lds_row_capacity(int32_t nodes_per_slice) { return prep_lds_row_capacity(nodes_per_slice); }
 
 extern "C" int gnnmp_train_geom_workspace_bytes(const gnnmp_batch* shape, int32_t config_size, size_t* bytes) {
     if (!shape || !bytes) return GNNMP_ERR_NULL;

@@ -104,18 +104,27 @@ __device__ __forceinline__ int prep_id(int x, int Ng, int& bad) {
     return b ? 0 : x;
 }
 
+// 8-byte records of the one-launch form's row assembly that fit the dynamic LDS behind the counters and the scan
+__host__ __device__ constexpr int prep_row_capacity(int lds_ints, int cap) {
+    return lds_ints > 2 * cap + 1024 ? (lds_ints - 2 * cap - 1024) / 2 : 0;
+}
+
+template <int CAP>
 __device__ __forceinline__ void prep_graph_body(const PrepParams& q, int g, int part, int parts, int n0, int Np, int e0, int e1,
-                                                int* prep_lds) {
-    __shared__ int carry;                              // prep_lds: cnt[kPrepCap], rb[kPrepCap], scan[1024]
+                                                int* prep_lds, int rec_cap) {
+    // prep_lds: cnt[CAP], rb[CAP], scan[1024], rec[the rest] (8-byte records of the row assembly below).  The offsets are
+    // compile-time constants on purpose: sized by the slice, the address arithmetic costs the registers the 48 kept columns need
+    // (spills); the launcher picks CAP instead (slices of more than CAP nodes keep their counters in global memory)
+    __shared__ int carry;
     __shared__ int below_w[16];
     const int tid = threadIdx.x;
     const int c0 = prep_ep(q, g), Eg = prep_ep(q, g + 1) - c0;            // caller columns of this graph
     const int span = ((Np + parts - 1) / parts + 31) & ~31;
     const int lo = min(part * span, Np), hi = min(lo + span, Np), Nown = hi - lo;
-    const bool in_lds = Nown <= kPrepCap;
+    const bool in_lds = Nown <= CAP;
     int* cnt = in_lds ? prep_lds : q.deg + n0 + lo;
-    int* rb = in_lds ? prep_lds + kPrepCap : q.row_beg + n0 + lo;
-    int* scan = prep_lds + 2 * kPrepCap;
+    int* rb = in_lds ? prep_lds + CAP : q.row_beg + n0 + lo;
+    int* scan = prep_lds + 2 * CAP;
     const long long* srcs = q.edge_index + c0;
     const long long* dsts = q.edge_index + (size_t)q.E + c0;
     for (int i = tid; i < Nown; i += 1024) cnt[i] = 0;
@@ -171,7 +180,8 @@ __device__ __forceinline__ void prep_graph_body(const PrepParams& q, int g, int 
         carry = sum;
     }
     __syncthreads();
-    int carry_run = carry;                             // every thread carries the running offset itself
+    int carry_run = __builtin_amdgcn_readfirstlane(carry);      // every wave carries the running offset itself (a scalar)
+    const int slot0 = carry_run;                       // first slot of this slice's rows
     for (int base = 0; base < Nown; base += 1024) {    // exclusive scan -> absolute first slot of every node
         const int i = base + tid;
         const int d = (i < Nown) ? cnt[i] : 0;
@@ -182,14 +192,31 @@ __device__ __forceinline__ void prep_graph_body(const PrepParams& q, int g, int 
             rb[i] = r;
             if (in_lds) { q.row_beg[n0 + lo + i] = r; q.deg[n0 + lo + i] = d; }
         }
-        carry_run += chunk_total;
+        carry_run += __builtin_amdgcn_readfirstlane(chunk_total);
     }
     __syncthreads();                                   // rb is complete
+    // Scattered to their slots straight from the registers, every wave store is 64 separate 16-byte requests, and a workgroup's
+    // scatter is bound by its CU's request rate to L2.  Where the slice's records fit the LDS behind the counters they are
+    // assembled there first -- packed {local source | local target << 16, local column} at slot - slot0, the SAME slots from
+    // the same arrival ranks -- and written out in slot order: a wave store is then 1 KiB of consecutive addresses.
+    const int own = carry_run - slot0;                 // (uniform) records of this slice
+    const bool rows = q.lds_rows && in_lds && Ng <= 65536 && own <= rec_cap;             // ids below N_g fit 16 bits; read under in_regs only
     if (in_regs) {
+        int2* rec = reinterpret_cast<int2*>(scan + 1024);
 #pragma unroll
         for (int u = 0; u < U; ++u)
-            if (tv_r[u] >= 0)                                            // {source, target, caller column}
-                q.csr[rb[tv_r[u] - lo] + rk_r[u]] = make_int4(n0 + sv_r[u], n0 + tv_r[u], c0 + tid + u * 1024, 0);
+            if (tv_r[u] >= 0) {                                          // {source, target, caller column}
+                const int slot = rb[tv_r[u] - lo] + rk_r[u];
+                if (rows) rec[slot - slot0] = make_int2((int)((unsigned)sv_r[u] | ((unsigned)tv_r[u] << 16)), tid + u * 1024);
+                else q.csr[slot] = make_int4(n0 + sv_r[u], n0 + tv_r[u], c0 + tid + u * 1024, 0);
+            }
+        if (rows) {
+            __syncthreads();
+            for (int i = tid; i < own; i += 1024) {
+                const int2 r = rec[i];
+                q.csr[slot0 + i] = make_int4(n0 + (r.x & 0xffff), n0 + (int)((unsigned)r.x >> 16), c0 + r.y, 0);
+            }
+        }
     } else {
         for (int c = tid; c < Eg; c += U * 1024) {
             int sv[U], tv[U], rk[U];
@@ -352,22 +379,49 @@ __device__ __forceinline__ void prep_prefix(const PrepParams& q, int g, int part
 }
 
 // tiles / slots / nodes behind the last graph are unused (the padded totals are upper bounds)
-__device__ __forceinline__ void prep_trailing(const PrepParams& q, int n_end, int e_end, int Npad, int Epad) {
+// where the last graph ends, for every workgroup (G more loads spread over 1024 threads; n1, e1: where graph g ends): the unused
+// tail of the padded spaces is then marked by all workgroups together instead of by the last one behind its own graph (256 graphs
+// of 1000 nodes: 59 k node rows, 32 k slots -- 1.5 MB of stores from one CU)
+__device__ __forceinline__ void prep_end(const PrepParams& q, int g, int n1, int e1, int& n_end, int& e_end) {
+    __shared__ int tot[2][16];
     const int tid = threadIdx.x;
-    for (int i = n_end + tid; i < Npad; i += 1024) { q.deg[i] = 0; q.row_beg[i] = e_end; }
-    for (int t = n_end / 32 + tid; t < Npad / 32; t += 1024) q.ntile_graph[t] = -1;
-    for (int t = e_end / 32 + tid; t < Epad / 32; t += 1024) { q.etile_graph[t] = -1; q.tile_meta[t] = -1; }
-    for (int sl = e_end + tid; sl < Epad; sl += 1024) q.csr[sl] = make_int4(-1, -1, -1, -1);
+    int tn = 0, te = 0;
+    for (int t = g + 1 + tid; t < q.G; t += 1024) {
+        tn += round_up(prep_np(q, t + 1) - prep_np(q, t), kPad);
+        te += round_up(prep_ep(q, t + 1) - prep_ep(q, t), kPad);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) { tn += __shfl_down(tn, off); te += __shfl_down(te, off); }
+    if ((tid & 63) == 0) { tot[0][tid >> 6] = tn; tot[1][tid >> 6] = te; }
+    __syncthreads();
+    tn = n1; te = e1;
+#pragma unroll
+    for (int w = 0; w < 16; ++w) { tn += tot[0][w]; te += tot[1][w]; }
+    n_end = tn; e_end = te;
 }
 
-__global__ __launch_bounds__(1024) void prep_small_kernel(PrepParams q, int Npad, int Epad, int parts) {
-    extern __shared__ int prep_lds[];
+// share `wg` of `nwg` workgroups
+__device__ __forceinline__ void prep_trailing(const PrepParams& q, int n_end, int e_end, int Npad, int Epad, int wg = 0, int nwg = 1) {
+    const int tid = wg * 1024 + threadIdx.x, nt = nwg * 1024;
+    for (int i = n_end + tid; i < Npad; i += nt) { q.deg[i] = 0; q.row_beg[i] = e_end; }
+    for (int t = n_end / 32 + tid; t < Npad / 32; t += nt) q.ntile_graph[t] = -1;
+    for (int t = e_end / 32 + tid; t < Epad / 32; t += nt) { q.etile_graph[t] = -1; q.tile_meta[t] = -1; }
+    for (int sl = e_end + tid; sl < Epad; sl += nt) q.csr[sl] = make_int4(-1, -1, -1, -1);
+}
+
+template <int CAP>
+__global__ __launch_bounds__(1024) void prep_small_kernel(PrepParams q, int Npad, int Epad, int parts, int rec_cap) {
+    extern __shared__ __attribute__((aligned(16))) int prep_lds[];
     const int g = blockIdx.x / parts, part = blockIdx.x - g * parts;
-    int n0, n1, e0, e1;
+    int n0, n1, e0, e1, n_end, e_end;
     prep_prefix<false>(q, g, part, parts, n0, n1, e0, e1);
-    prep_graph_body(q, g, part, parts, n0, n1 - n0, e0, e1, prep_lds);
+    // uniform sums read back from LDS: kept in scalar registers (the body needs every vector register for its columns)
+    n0 = __builtin_amdgcn_readfirstlane(n0); n1 = __builtin_amdgcn_readfirstlane(n1);
+    e0 = __builtin_amdgcn_readfirstlane(e0); e1 = __builtin_amdgcn_readfirstlane(e1);
+    prep_graph_body<CAP>(q, g, part, parts, n0, n1 - n0, e0, e1, prep_lds, rec_cap);
     if (part == 0) goal_body(q.C, q.v, q.goal, prep_np(q, g), prep_np(q, g + 1) - prep_np(q, g), g, n0, q.goal_node);
-    if (g == q.G - 1 && part == parts - 1) prep_trailing(q, n1, e1, Npad, Epad);
+    prep_end(q, g, n1, e1, n_end, e_end);
+    prep_trailing(q, n_end, e_end, Npad, Epad, (int)blockIdx.x, (int)gridDim.x);
 }
 
 // -----------------------------------------------------------------------------------------------------
@@ -783,23 +837,32 @@ __device__ __forceinline__ void node_f64_body(const ObsParams& p, const NodeF64P
     float* kd = lds + ((L.size + 3) & ~3);
     float* vd = kd + OC * D;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, j16 = lane & 15, g = lane >> 4;
-    // a workgroup owns q.groups consecutive 64-row groups of ONE graph's padded node range (kPad is a multiple of 64 *
-    // groups): the obstacle operands are built once per workgroup
+    // a workgroup owns q.groups consecutive 64-row groups of the padded node space.  Up to four of them lie inside ONE 256-row block
+    // (kPad), hence inside one graph; a longer run may pass from one graph into the next, and the obstacle operands are rebuilt
+    // where it does (and only there: once per workgroup and graph)
     const int row00 = vblock * 64 * q.groups;
-    const int gr = q.ntile_graph[row00 >> 5];
-    if (gr < 0) return;
+    if (row00 >= q.n_rows || q.ntile_graph[row00 >> 5] < 0) return;
     stage(wl, q.w, L.size);
-    const int o0 = p.obs_ptr[gr], O = min(p.obs_ptr[gr + 1] - o0, p.ot_max * 32);
-    const int OT = (O + 31) / 32;
     const int C = q.C;
-    const int nbase_pad = q.node_ptr_pad[gr], nbase = q.node_ptr[gr], ng = q.node_ptr[gr + 1] - nbase;
-    const bool single_chunk = O <= OC;
     const double isd = 1.0 / sqrt((double)D);
+    int gr = -1, o0 = 0, O = 0, OT = 0, nbase_pad = 0, nbase = 0, ng = 0;
+    bool single_chunk = true, used = false;                // used: kd / vd hold operands that some wave may still be reading
     for (int grp = 0; grp < q.groups; ++grp) {
     const int row0 = row00 + grp * 64;
-    if (row0 - nbase_pad >= ng) {                          // (uniform) nothing but padding rows from here on: finite rows, no work
-        for (int i = threadIdx.x; i < (q.groups - grp) * 64 * D; i += 256) q.m0[(size_t)row0 * D + i] = 0.f;
-        break;
+    const int gnew = row0 < q.n_rows ? q.ntile_graph[row0 >> 5] : -1;
+    if (gnew < 0) break;                                   // (uniform) behind the last graph
+    const bool fresh = gnew != gr;
+    if (fresh) {
+        gr = gnew;
+        o0 = p.obs_ptr[gr]; O = min(p.obs_ptr[gr + 1] - o0, p.ot_max * 32);
+        OT = (O + 31) / 32;
+        nbase_pad = q.node_ptr_pad[gr]; nbase = q.node_ptr[gr]; ng = q.node_ptr[gr + 1] - nbase;
+        single_chunk = O <= OC;
+    }
+    if (row0 - nbase_pad >= ng) {                          // (uniform) nothing but padding rows in this group: finite rows, no work
+        for (int i = threadIdx.x; i < 64 * D; i += 256) q.m0[(size_t)row0 * D + i] = 0.f;
+        if (fresh) gr = -1;                                // the operands in LDS are not this graph's
+        continue;
     }
     const int row = row0 + wave * 16 + j16, local = row - nbase_pad;
     const float* vr = q.v + (size_t)(nbase + (local < ng ? local : 0)) * C;
@@ -809,8 +872,9 @@ __device__ __forceinline__ void node_f64_body(const ObsParams& p, const NodeF64P
     float mxs = 0.f, l0s = 0.f;
     double den = 0.0;
     for (int oc0 = 0; oc0 == 0 || oc0 < O; oc0 += OC) {
-        if (oc0 > 0 || (grp > 0 && !single_chunk)) __syncthreads();    // everybody is done with the previous chunk's operands
-        if (grp == 0 || !single_chunk)
+        const bool build = fresh || !single_chunk;         // (uniform) a single chunk stays in LDS for all groups of the graph
+        if (build && used) __syncthreads();                // everybody is done with the previous chunk's operands
+        if (build)
         {   // obstacle operands of this chunk: wave w owns the 32-obstacle tiles oc0/32 + w, ... (obs_body's arithmetic for b = 0)
             const ObsBlob Lo = p.blob;
             const int h = lane >> 5, j = lane & 31, S = p.S;
@@ -845,7 +909,8 @@ __device__ __forceinline__ void node_f64_body(const ObsParams& p, const NodeF64P
                     }
             }
         }
-        if (grp == 0 || !single_chunk) __syncthreads();    // operands (and, the first time, the staged weights) are in LDS
+        if (build) __syncthreads();                        // operands (and, the first time, the staged weights) are in LDS
+        used = true;
         if (oc0 == 0) {
             // node_free_code = W2 relu(W1 v + b1) + b2
             f64x4 hdn[NB];
@@ -3025,26 +3090,56 @@ int prep_parts(int G, int E) {
 }
 
 // `hist`: 2 * prep_parts * Npad ints of workspace when prep_parts > 1 (unused otherwise)
-hipError_t launch_prep(const PrepParams& q, int Npad, int Epad, int* hist, hipStream_t st) {
+// one-launch form: all the LDS a workgroup can have (its 128 registers per lane leave one 1024-thread workgroup per CU anyway);
+// what the counters and the scan leave of it holds the records of the row assembly (prep_graph_body)
+constexpr int kPrepSmallLdsInts = (160 * 1024 - 1024) / (int)sizeof(int);
+static_assert(kPrepSmallLdsInts >= 2 * kPrepCap + 1024, "counters of kPrepCap own nodes + scan");
+// LDS counters of a slice: 2048 nodes where the launch's slices have at most 1536 padded nodes on average, counted from the
+// launch's upper bound Npad (a slice of more than 2048 then keeps its counters in global memory) -- that leaves room for the
+// records of any slice whose columns stay in registers (16 k) -- else kPrepCap, and the row assembly takes slices of up to
+// 11.6 k records
+constexpr int kPrepCapSmall = 2048;
+static int prep_counter_cap(int nodes_per_slice) { return nodes_per_slice <= kPrepCapSmall * 3 / 4 ? kPrepCapSmall : kPrepCap; }
+
+int prep_lds_row_capacity(int nodes_per_slice) { return prep_row_capacity(kPrepSmallLdsInts, prep_counter_cap(nodes_per_slice)); }
+
+hipError_t launch_prep(const PrepParams& q_in, int Npad, int Epad, int* hist, hipStream_t st) {
     const size_t glds = (size_t)(2 * kPrepCap + 1024) * sizeof(int);
+    PrepParams q = q_in;
+    {   // GNNMP_PREP_LDS_ROWS=0: records go from the registers to their slots (A/B runs and the tests; read per call)
+        const char* env = getenv("GNNMP_PREP_LDS_ROWS");
+        q.lds_rows = !(env && env[0] == '0');
+    }
     const int parts = prep_parts(q.G, q.E);
     if (parts == 1) {
-        const hipError_t attr = set_lds(prep_small_kernel, glds);
-        if (attr != hipSuccess) return attr;
+        const size_t slds = (size_t)kPrepSmallLdsInts * sizeof(int);
         // Few graphs (the reference's call is ONE): a graph's target nodes are cut into slices, one workgroup each.  A
         // workgroup's scatter of the int4 records is bound by its CU's request rate to L2 (one 16-byte store per clock: 7 of the
         // 14 us a single 1000-node graph's CSR build took); every slice's workgroup reads all columns (L2 hits) and ranks /
         // scatters its own.  One slice per 128 target nodes at most, eight at most, and about two workgroups per CU in all
         // (256 graphs of 1000 nodes: 0.068 -> 0.057 ms with two slices, 0.081 with four).
+        // With the rows assembled in LDS the scatter no longer bounds a workgroup, and what every slice repeats -- reading all
+        // columns -- does: one workgroup per CU in all (the kernel's registers leave one resident), a single round (the same
+        // 256 graphs: 0.062 ms with two slices, 0.045 with one, 0.104 with four).
         static const int slices_env = getenv("GNNMP_PREP_SLICES") ? atoi(getenv("GNNMP_PREP_SLICES")) : 0;    // experiments
-        int slices = q.G > 0 ? 512 / q.G : 1;
+        int slices = q.G > 0 ? (q.lds_rows ? 256 : 512) / q.G : 1;
         const int by_nodes = q.G > 0 ? (Npad / q.G) / 128 : 1;
         if (slices > by_nodes) slices = by_nodes;
         if (slices > 8) slices = 8;
         if (slices_env > 0) slices = slices_env;
         if (slices < 1) slices = 1;
         if (slices > kGstatStride - 1) slices = kGstatStride - 1;
-        hipLaunchKernelGGL(prep_small_kernel, dim3(q.G * slices), dim3(1024), glds, st, q, Npad, Epad, slices);
+        const int cap = prep_counter_cap(q.G > 0 ? Npad / q.G / slices : Npad);
+        const int rec_cap = prep_row_capacity(kPrepSmallLdsInts, cap);
+        if (cap == kPrepCapSmall) {
+            const hipError_t attr = set_lds(prep_small_kernel<kPrepCapSmall>, slds);
+            if (attr != hipSuccess) return attr;
+            hipLaunchKernelGGL(prep_small_kernel<kPrepCapSmall>, dim3(q.G * slices), dim3(1024), slds, st, q, Npad, Epad, slices, rec_cap);
+        } else {
+            const hipError_t attr = set_lds(prep_small_kernel<kPrepCap>, slds);
+            if (attr != hipSuccess) return attr;
+            hipLaunchKernelGGL(prep_small_kernel<kPrepCap>, dim3(q.G * slices), dim3(1024), slds, st, q, Npad, Epad, slices, rec_cap);
+        }
         LAUNCH_CHECK();
         return hipSuccess;
     }
@@ -3061,12 +3156,18 @@ hipError_t launch_prep(const PrepParams& q, int Npad, int Epad, int* hist, hipSt
 }
 
 
+// dynamic LDS of the obstacle launch: the larger of its two roles'
+template <int D, int P>
+static size_t obs_lds_bytes(const ObsParams& p, const NodeF64Params& q, bool f64_role) {
+    size_t lds = f64_role ? (size_t)(((q.blob.size + 3) & ~3) + 2 * f64_obs_chunk(D) * D) * sizeof(float) : 0;
+    const size_t obs_lds = (D == 32 && P != 2) ? (size_t)((p.blob.size + 3) & ~3) * sizeof(float) : 0;     // obstacle role: its blob
+    return obs_lds > lds ? obs_lds : lds;
+}
+
 template <int D, int P>
 static hipError_t launch_obs_t(const ObsParams& p, const NodeF64Params& q, int G, hipStream_t st) {
     const int f64_blocks = P == 1 ? 0 : q.n_wg;
-    size_t lds = f64_blocks ? (size_t)(((q.blob.size + 3) & ~3) + 2 * f64_obs_chunk(D) * D) * sizeof(float) : 0;
-    const size_t obs_lds = (D == 32 && P != 2) ? (size_t)((p.blob.size + 3) & ~3) * sizeof(float) : 0;     // obstacle role: its blob
-    if (obs_lds > lds) lds = obs_lds;
+    const size_t lds = obs_lds_bytes<D, P>(p, q, f64_blocks > 0);
     if (lds) {
         const hipError_t e = set_lds(obs_kernel<D, P>, lds);
         if (e != hipSuccess) return e;
@@ -3163,6 +3264,20 @@ static Residency resident_workgroups(const void* kernel, size_t lds_bytes) {
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&r.per_cu, kernel, 256, lds_bytes) != hipSuccess || r.per_cu < 1) r.per_cu = 4;
     if (getenv("GNNMP_DEBUG_GRID")) fprintf(stderr, "[gnnmp] resident workgroups per CU: %d (lds %zu)\n", r.per_cu, lds_bytes);
     return cache[{kernel, lds_bytes}] = r;
+}
+
+// workgroups of the obstacle launch (with its double-precision node role) that the device keeps resident at once
+template <int D, int P>
+static int obs_f64_slots_t(const ObsParams& p, const NodeF64Params& q) {
+    const Residency r = resident_workgroups(reinterpret_cast<const void*>(obs_kernel<D, P>), obs_lds_bytes<D, P>(p, q, true));
+    return r.per_cu * r.cus;
+}
+int obs_f64_slots(int D, int P, const ObsParams& p, const NodeF64Params& q) {
+    if (D == 32 && P == 0) return obs_f64_slots_t<32, 0>(p, q);
+    if (D == 32 && P == 2) return obs_f64_slots_t<32, 2>(p, q);
+    if (D == 64 && P == 0) return obs_f64_slots_t<64, 0>(p, q);
+    if (D == 64 && P == 2) return obs_f64_slots_t<64, 2>(p, q);
+    return 0;
 }
 
 // max_per_cu: measured sweet spot of the kernel -- more resident waves than that only add contention in the memory

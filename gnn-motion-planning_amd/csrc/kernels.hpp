@@ -28,6 +28,7 @@ struct PrepParams {
     const int* obs_ptr;                          // caller prefix array or nullptr (single graph: single_o)
     int obs_cap;                                 // 32 * ot_max, or INT_MAX when the forward ignores obstacles
     int* gstat;
+    int lds_rows;                                // one-launch form: assemble a slice's CSR rows in LDS and write them out in slot order
 };
 constexpr int kGstatStride = 17;                 // 1 + the largest `parts` of the prep stage
 
@@ -50,9 +51,11 @@ struct NodeF64Params {
     const float* w;          // F64Blob
     F64Blob blob;
     float* m0;               // out [Npad, d]: node_free_code after the attention sub-block of block 0 (input of its map_feed)
+    int n_rows;              // Npad: rows of the padded node space (the last workgroup's run may end behind it)
     int n_wg;                // workgroups of this role (64 * groups padded node rows each); 0 = role not used
     int f64_first;           // dispatch order inside the obstacle launch: 1 = these workgroups before the obstacle ones
-    int groups;              // 64-row groups per workgroup: 1 (few graphs: shortest chains) or 4 (obstacle operands built once per 256 rows)
+    int groups;              // 64-row groups per workgroup: 1 (few graphs: shortest chains), 4 (obstacle operands built once per 256
+                             // rows) or a multiple of 4 (several 256-row blocks: the operands are rebuilt only where the graph changes)
 };
 
 struct PreParams {
@@ -406,8 +409,10 @@ hipError_t t_sm_path_update_bwd_seg(const SmSeg& g, int C, const float* d_next, 
 hipError_t t_sm_coords_bwd_seg(const SmSeg& g, int C, const float* dXin, float* d_prev, hipStream_t st);
 
 int prep_parts(int G, int E);
+int prep_lds_row_capacity(int nodes_per_slice);   // records per workgroup (slice of a graph) that the one-launch form assembles in LDS
 hipError_t launch_prep(const PrepParams& q, int Npad, int Epad, int* hist, hipStream_t st);
 hipError_t launch_obs(int D, int P, const ObsParams& p, const NodeF64Params& q, int G, hipStream_t st);
+int obs_f64_slots(int D, int P, const ObsParams& p, const NodeF64Params& q);    // resident workgroups of that launch, device-wide (0: no fp64 role)
 hipError_t launch_pre(int D, int P, bool edge, int waves, const PreParams& p, int n_tiles32, size_t lds_bytes, hipStream_t st);
 hipError_t launch_pre_resident_both(int D, int P, const PreParams& pn, const PreParams& pe, size_t lds_bytes, int node_blocks,
                                     int edge_blocks, hipStream_t st);

@@ -198,8 +198,10 @@ int gnnmp_explorer_profile_read(gnnmp_explorer* h, double* ms_sum /* [GNNMP_N_ST
 /* Test hook: after a forward, copy an intermediate out of `workspace` into `dst` (device, fp32,
  * row-major, caller node/edge order).  which: 0 = loop-invariant part of the encoder output [total_nodes, d]
  * (model.py:141 without the h_i term), 1 = final h_i [total_nodes, d] (model.py:142), 2 = decode [total_nodes, d]
- * (model.py:143), 3 = goal node per graph as float [G].  Returns GNNMP_ERR_ARG if unknown; tap 2 is kept in bf16 in the
- * GNNMP_BF16 mode (its only reader is an MFMA operand) and returns GNNMP_ERR_DIMS there. */
+ * (model.py:143), 3 = goal node per graph as float [G], 4 = node_free_code after the attention sub-block of node block 0 as the
+ * double-precision node role left it [total_nodes, d] (forwards with obstacles).  Returns GNNMP_ERR_ARG if unknown; tap 2 is kept in
+ * bf16 in the GNNMP_BF16 mode (its only reader is an MFMA operand) and returns GNNMP_ERR_DIMS there, as does tap 4 where that role
+ * is off (GNNMP_BF16, GNNMP_NODE_F64=0). */
 int gnnmp_explorer_debug_tap(const gnnmp_explorer* h, const gnnmp_batch* batch, int which, float* dst,
                              void* workspace, size_t workspace_bytes, void* hip_stream);
 
@@ -816,6 +818,11 @@ typedef struct {
  * node_ptr / edge_ptr; obs_ptr may be NULL, obstacles play no part), enqueued on hip_stream; *geom_out is filled on the host at once.  workspace:
  * 256-byte aligned, >= gnnmp_train_geom_workspace_bytes. */
 int gnnmp_train_geom_workspace_bytes(const gnnmp_batch* shape, int32_t config_size, size_t* bytes);
+/* Test hook: the prep stage's one-launch form assembles the CSR rows of a workgroup's slice of a graph's target nodes in LDS and
+ * writes them out in slot order when the slice has at most this many records and the graph at most 65536 nodes
+ * (GNNMP_PREP_LDS_ROWS=0: never); other slices are scattered record by record.  Both give the same slots.  nodes_per_slice:
+ * padded nodes of the batch / (graphs x slices per graph), which picks the LDS layout of the launch. */
+int gnnmp_prep_lds_row_capacity(int32_t nodes_per_slice);
 int gnnmp_train_geom_build(const gnnmp_batch* batch, int32_t config_size, void* workspace, size_t workspace_bytes,
                            gnnmp_train_geom* geom_out, void* hip_stream);
 int gnnmp_train_op(int op, const int64_t* dims, int n_dims, void* const* bufs, int n_bufs,
