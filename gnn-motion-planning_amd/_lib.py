@@ -95,6 +95,12 @@ class OracleSmoothBatch(ctypes.Structure):
                 ('action', ctypes.c_void_p), ('node_idx', ctypes.c_void_p), ('u', ctypes.c_void_p)]
 
 
+class FrontierBatch(ctypes.Structure):
+    _fields_ = [('n_graphs', ctypes.c_int32), ('total_nodes', ctypes.c_int32), ('total_edges', ctypes.c_int32),
+                ('edge_index', ctypes.c_void_p), ('scores', ctypes.c_void_p), ('node_ptr', ctypes.c_void_p),
+                ('edge_ptr', ctypes.c_void_p), ('n_free', ctypes.c_void_p)]
+
+
 class TrainGeom(ctypes.Structure):
     """gnnmp_train_geom: filled by gnnmp_train_geom_build, handed back to gnnmp_train_op (test hooks only)."""
     _fields_ = [('n_graphs', ctypes.c_int32), ('config_size', ctypes.c_int32), ('n_pad', ctypes.c_int32), ('e_pad', ctypes.c_int32),
@@ -202,6 +208,9 @@ def lib():
     L.gnnmp_episode_explore.argtypes = [ctypes.POINTER(EpisodeGraphs), vp, vp, vp, vp, vp, ctypes.c_int32, vp, vp, vp, sz, vp]
     L.gnnmp_episode_frontier.argtypes = [ctypes.POINTER(EpisodeGraphs), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz,
                                          vp]
+    L.gnnmp_frontier_limits.argtypes = [c_int32_p, c_int32_p]
+    L.gnnmp_frontier_workspace_bytes.argtypes = [ctypes.POINTER(FrontierBatch), ctypes.POINTER(sz)]
+    L.gnnmp_frontier_rank.argtypes = [ctypes.POINTER(FrontierBatch), vp, vp, vp, vp, vp, vp, sz, vp]
     L.gnnmp_oracle_smooth_limits.argtypes = [c_int32_p, c_int32_p]
     L.gnnmp_oracle_smooth.argtypes = [ctypes.POINTER(OracleSmoothBatch), vp, vp, vp, vp, vp, vp]
     L.gnnmp_stick_oracle_smooth.argtypes = [ctypes.POINTER(OracleSmoothBatch), vp, vp, vp, vp, vp, vp]

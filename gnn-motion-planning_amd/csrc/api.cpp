@@ -2619,6 +2619,68 @@ extern "C" int gnnmp_episode_frontier(const gnnmp_episode_graphs* g, const float
 }
 
 // =============================================================================================
+// ranked frontier rows for the host-checked planner (frontier_kernels.hip)
+// =============================================================================================
+namespace {
+struct FrCarve { size_t zero_beg, cnt, deg, long_cnt, zero_end, long_list, st_b, st_e, st_v, total; };
+bool fr_carve(const gnnmp_frontier_batch* b, FrCarve& c) {
+    if (b->n_graphs < 1 || b->total_nodes < 0 || b->total_edges < 0) return false;
+    size_t o = 0;
+    auto take = [&](size_t bytes) { const size_t r = o; o += (bytes + 255) & ~(size_t)255; return r; };
+    const size_t n = (size_t)(b->total_nodes > 0 ? b->total_nodes : 1), e = (size_t)(b->total_edges > 0 ? b->total_edges : 1);
+    c.zero_beg = o;
+    c.cnt = take(sizeof(int) * n);
+    c.deg = take(sizeof(int) * n);
+    c.long_cnt = take(sizeof(int));
+    c.zero_end = o;
+    c.long_list = take(sizeof(int) * n);
+    c.st_b = take(sizeof(int) * e);
+    c.st_e = take(sizeof(int) * e);
+    c.st_v = take(sizeof(float) * e);
+    c.total = o;
+    return true;
+}
+}  // namespace
+
+extern "C" int gnnmp_frontier_limits(int32_t* wave_row_cells, int32_t* block_tile_cells) {
+    if (!wave_row_cells || !block_tile_cells) return GNNMP_ERR_NULL;
+    *wave_row_cells = kFrWaveCells;
+    *block_tile_cells = kFrTileCells;
+    return GNNMP_OK;
+}
+
+extern "C" int gnnmp_frontier_workspace_bytes(const gnnmp_frontier_batch* b, size_t* bytes) {
+    if (!b || !bytes) return GNNMP_ERR_NULL;
+    FrCarve c;
+    if (!fr_carve(b, c)) return GNNMP_ERR_ARG;
+    *bytes = c.total;
+    return GNNMP_OK;
+}
+
+extern "C" int gnnmp_frontier_rank(const gnnmp_frontier_batch* b, int32_t* row_beg, int32_t* row_len, int32_t* cols, float* vals,
+                                   int32_t* status, void* ws, size_t ws_bytes, void* hip_stream) {
+    if (!b || !row_beg || !row_len || !cols || !vals || !status || !ws) return GNNMP_ERR_NULL;
+    FrCarve c;
+    if (!fr_carve(b, c)) return GNNMP_ERR_ARG;
+    if (!b->n_free) return GNNMP_ERR_NULL;
+    if (b->n_graphs > 1 && (!b->node_ptr || !b->edge_ptr)) return GNNMP_ERR_NULL;      // one graph may leave them out
+    if (b->total_edges > 0 && (!b->edge_index || !b->scores)) return GNNMP_ERR_NULL;
+    if (ws_bytes < c.total || (reinterpret_cast<uintptr_t>(ws) & 255)) return GNNMP_ERR_WORKSPACE;
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    HIP_TRY(hipMemsetAsync(at<char>(ws, c.zero_beg), 0, c.zero_end - c.zero_beg, st));
+    FrontierParams p;
+    p.G = b->n_graphs; p.total_nodes = b->total_nodes; p.total_edges = b->total_edges;
+    p.edge_index = reinterpret_cast<const long long*>(b->edge_index); p.scores = b->scores;
+    p.node_ptr = b->node_ptr; p.edge_ptr = b->edge_ptr; p.n_free = b->n_free;
+    p.row_beg = row_beg; p.row_len = row_len; p.cols = cols; p.vals = vals; p.status = status;
+    p.cnt = at<int>(ws, c.cnt); p.deg = at<int>(ws, c.deg); p.long_cnt = at<int>(ws, c.long_cnt);
+    p.long_list = at<int>(ws, c.long_list);
+    p.st_b = at<int>(ws, c.st_b); p.st_e = at<int>(ws, c.st_e); p.st_v = at<float>(ws, c.st_v);
+    HIP_TRY(launch_frontier_rank(p, st));
+    return GNNMP_OK;
+}
+
+// =============================================================================================
 // the smoother's training targets (smoother.py:67-151, oracle_smooth_kernels.hip)
 // =============================================================================================
 extern "C" int gnnmp_oracle_smooth_limits(int32_t* max_waypoints, int32_t* max_width) {

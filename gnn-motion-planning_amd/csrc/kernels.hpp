@@ -314,6 +314,24 @@ struct OracleSmoothParams {
 };
 hipError_t launch_oracle_smooth(const OracleSmoothParams& p, hipStream_t st);
 
+// ---- ranked frontier rows for the host-checked planner (frontier_kernels.hip)
+constexpr int kFrWaveCells = 256;             // rows up to this many cells: one wave, the row in LDS
+constexpr int kFrTileCells = 2048;            // longer rows: a workgroup streams the row through LDS tiles of this many cells
+struct FrontierParams {
+    int G, total_nodes, total_edges;
+    const long long* edge_index;          // [2, sumE] graph-local (row 0 = source b, row 1 = target a)
+    const float* scores;                  // [sumE]
+    const int *node_ptr, *edge_ptr;       // [G + 1] or nullptr (G == 1)
+    const int* n_free;                    // [G]
+    int *row_beg, *row_len, *cols;        // out [sumN], [sumN], [sumE]
+    float* vals;                          // out [sumE]
+    int* status;                          // out [G]
+    int *cnt, *deg, *long_cnt, *long_list;        // ws: [sumN] x 2 and one int, zero on entry; [sumN]
+    int *st_b, *st_e;                     // ws [sumE]: staged cells grouped by row (source, column)
+    float* st_v;                          // ws [sumE]: staged score, 0 = dead
+};
+hipError_t launch_frontier_rank(const FrontierParams& p, hipStream_t st);
+
 // ---- training path (train_kernels.hip)
 struct TrainGeom {
     int G, C, Npad, Epad;

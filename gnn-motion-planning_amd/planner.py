@@ -151,6 +151,57 @@ def greedy_expand_sparse(scores, edge_index, labels, v, env, state):
     return None
 
 
+def greedy_expand_ranked(ranked, n, v, env, state):
+    """Same decisions as ``greedy_expand_sparse`` on rows that are already ranked (``frontier.rank_rows``: per node row the live
+    cells by score descending, then source ascending; the device did the masking of self loops, zeros and collided ends and the
+    sort).  ``n``: number of nodes.  The heap holds ONE entry per explored row -- its best cell not yet popped,
+    ``(-score, position of a in the explored list, b, a, cursor)`` -- and popping an entry pushes the row's next cell, so the pop
+    order is that of a heap over all live cells (ties like the dense row-major argmax) while only the cells that are tried are
+    ever touched.  What the walk itself zeroes is tracked on the side: a popped cell is skipped if ``b`` has been explored or
+    ``(a, b)`` was killed -- by the reference's legacy-index mask of the explored-edge history (finding 0.6: the pairs of
+    ``np.array(explored_edges).reshape(2, -1)``, as they stand, no mirrors) or by a blocked edge (both directions).  Stops when the
+    heap is empty, i.e. when no live cell remains (not the reference's float-sum test; see ``greedy_expand_sparse``)."""
+    import heapq
+    row_beg, row_len, cols, vals = ranked.host()
+    explored, explored_edges = state['explored'], state['explored_edges']
+    idx = np.array(explored_edges).reshape(2, -1)        # the reference's quirk (finding 0.6)
+    killed = set(zip(idx[0].tolist(), idx[1].tolist()))
+    is_explored = np.zeros(n, dtype=bool)
+    is_explored[explored] = True
+    heap = []
+
+    def push(pos, a, cursor):
+        if cursor < row_len[a]:
+            i = int(row_beg[a]) + cursor
+            heapq.heappush(heap, (-float(vals[i]), pos, int(cols[i]), a, cursor))
+
+    for pos, a in enumerate(explored):
+        push(pos, a, 0)
+    while heap:
+        _, pos, end_b, end_a, cursor = heapq.heappop(heap)
+        push(pos, end_a, cursor + 1)
+        if is_explored[end_b] or (end_a, end_b) in killed:
+            continue
+        explored_edges.extend([[end_a, end_b], [end_b, end_a]])
+        if env._edge_fp(v[end_a], v[end_b]):
+            explored.append(end_b)
+            is_explored[end_b] = True
+            state['costs'][end_b] = state['costs'][end_a] + np.linalg.norm(v[end_a] - v[end_b])
+            state['prev'][end_b] = end_a
+            if env.in_goal_region(v[end_b]):
+                path, node = [end_b], end_b
+                while node != 0:
+                    node = state['prev'][node]
+                    path.append(node)
+                path.reverse()
+                return path
+            push(len(explored) - 1, end_b, 0)
+        else:
+            killed.add((end_a, end_b))
+            killed.add((end_b, end_a))
+    return None
+
+
 def _steer_round(path, target, env):
     """One sweep over the interior waypoints, left to right: each moves at most env.RRT_EPS towards its target and the move
     is kept only if the edges to both neighbours stay free -- the left neighbour already at its new place, the right one
@@ -221,14 +272,25 @@ def model_smooth(model, free, collided, old_path, env, device, iters=5, trace=No
 
 @torch.no_grad()
 def explore(env, model, model_s, smooth=True, batch=500, t_max=1000, k=30, smoother='model', loop=5, device='cuda',
-            trace=None, sparse=False, gpu_graph=False, reference_kwargs=None):
+            trace=None, sparse=False, gpu_graph=False, reference_kwargs=None, frontier='heap'):
     """Counterpart of ``explore`` (eval_gnn.py:168-276).  Returns the same result dict.
     ``reference_kwargs=True`` hands the model every keyword the reference does (``free``, ``collided``, ``labels``: built, copied to
     the device and then ignored by the forward, model.py:115); ``False`` passes only what the forward reads -- same output.  Default
     (None): False for this package's ``EncoderProcessDecoder``, True for any other model (one with the reference's signature needs them).
     ``sparse=True`` asks the model for per-edge scores (``edge_scores``) and runs the heap-based
     frontier instead of pulling the dense N x N matrix to the host; decisions are identical.
-    ``gpu_graph=True`` builds the kNN graph on the device (graph_kernels.hip; same edge_index)."""
+    ``gpu_graph=True`` builds the kNN graph on the device (graph_kernels.hip; same edge_index).
+    ``frontier='ranked'`` (default ``'heap'``: the loops above, chosen by ``sparse``) also asks for per-edge scores and leaves
+    them on the device: ``frontier.rank_rows`` sorts every node row's live cells behind the policy head, ONE copy brings the
+    ranked rows to pinned host memory and ``greedy_expand_ranked`` walks them -- same decisions as ``sparse=True`` without its
+    Python pass over all E scores after every forward.  With ``gpu_graph=True`` the edge_index is copied to the host only for
+    a ``trace``."""
+    if frontier not in ('heap', 'ranked'):
+        raise ValueError("explore: frontier must be 'heap' or 'ranked', got %r" % (frontier,))
+    ranked = None
+    if frontier == 'ranked':
+        from .frontier import RankedRows, rank_rows
+        ranked = RankedRows()                            # device block, pinned buffer, workspace: once per call, reused by its forwards
     if reference_kwargs is None:
         from .explorer import EncoderProcessDecoder
         reference_kwargs = not isinstance(model, EncoderProcessDecoder)
@@ -255,12 +317,25 @@ def explore(env, model, model_s, smooth=True, batch=500, t_max=1000, k=30, smoot
         if reference_kwargs:
             kw['labels'] = data['labels'].to(device)
         t3 = time.time()
-        ei = data['edge_index'].cpu().numpy()
+        ei = data['edge_index'].cpu().numpy() if ranked is None or trace is not None else None
         v = data['v'].numpy()
         split['obs_data'] += t2 - t1
         split['h2d'] += t3 - t2
         split['calls'] += 1
-        if sparse:
+        if ranked is not None:
+            t4 = time.time()
+            sc = model.edge_scores(**kw)
+            rank_rows(sc, kw['edge_index'], len(free), n_nodes=v.shape[0], out=ranked)
+            t5 = time.time()
+            ranked.host()                                            # rows of E cells, sorted: the one copy and the one wait
+            forward += time.time() - t1
+            split['module_call'] += t5 - t4
+            split['d2h_wait'] += time.time() - t5
+            if trace is not None:
+                trace.setdefault('forwards', []).append({'v': v.copy(), 'edge_index': ei.copy(),
+                                                         'scores': sc.detach().cpu().numpy().copy()})
+            found = greedy_expand_ranked(ranked, v.shape[0], v, env, state)
+        elif sparse:
             t4 = time.time()
             sc = model.edge_scores(**kw)
             t5 = time.time()

@@ -28,6 +28,8 @@
  *       proposed_path_smootherv2 (steering of the smoothing stage)  smoother.py:194-216
  *   gnnmp_maze_explore_workspace_bytes / gnnmp_maze_explore / gnnmp_maze_explore_ex
  *       explore()'s greedy loop + MazeEnv._edge_fp            eval_gnn.py:198-233, environment/maze_env.py:270-326
+ *   gnnmp_frontier_workspace_bytes / gnnmp_frontier_rank / gnnmp_frontier_limits
+ *       explore()'s masking and the order its argmax visits a row's cells in, for a host loop that checks edges itself   eval_gnn.py:198-204
  *
  * Conventions
  *   - plain C types only; every pointer in a batch / forward call is a DEVICE pointer unless the
@@ -650,6 +652,43 @@ int gnnmp_episode_frontier(const gnnmp_episode_graphs* graphs, const float* scor
                            const double* dist, const int32_t* prev, const int32_t* step, const int32_t* status,
                            int32_t* frontier, int32_t* frontier_len, int32_t* label, void* workspace,
                            size_t workspace_bytes, void* hip_stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Ranked frontier rows for planners whose collision checks stay on the host (eval_gnn.py:198-233 without the checks):
+ * for every node row a of every graph, the live cells P[a, b] sorted by score descending, ties by source id b ascending.
+ * The host loop then walks the rows of the explored nodes and touches only the cells it tries.
+ *
+ * A batch in the gnnmp_batch convention: column e of edge_index (row stride total_edges; row 0 = source b, row 1 = target
+ * a, graph-local ids) is the dense cell P[a, b] with score scores[e]; graph g owns node rows [node_ptr[g], node_ptr[g+1])
+ * and columns [edge_ptr[g], edge_ptr[g+1]).  With n_graphs == 1 either prefix array may be NULL (the whole batch is the
+ * graph).  The free samples are a prefix of a graph's nodes: node id >= n_free[g] means collided.
+ *
+ * A cell (a, b) is live iff a != b, its score != 0 (+0 and -0 are zero) and a, b < n_free[g].  If several columns name the
+ * same (a, b) the column with the highest index decides (index_put); if that value is 0 the cell is dead.  Scores are
+ * finite and compared as floats; a NaN cannot hang or fault anything, but the order of its row's cells is unspecified.
+ *
+ * Outputs (device): graph g's cells live in [edge_ptr[g], edge_ptr[g+1]) of cols (int32 source ids) and vals; row a of
+ * graph g starts at row_beg[node_ptr[g] + a] (an absolute index into cols / vals: the by-target CSR position) and its first
+ * row_len[node_ptr[g] + a] slots are the ranked live cells; the rest of the row's in-degree range is unspecified.  The
+ * live prefixes are bit-identical from run to run.  status [n_graphs]: GNNMP_OK, or GNNMP_ERR_INDEX for a graph with a node
+ * id outside [0, N_g) (such a column is dropped, never used as an address) or with a prefix-array range outside the batch
+ * (nothing of that graph is read); the other graphs of the launch are unaffected.
+ * Everything is enqueued on hip_stream: no allocation, no synchronisation.  Rows of any length up to the graph's edge count.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct {
+    int32_t n_graphs, total_nodes, total_edges;
+    const int64_t* edge_index;   /* [2, total_edges]                                          */
+    const float* scores;         /* [total_edges]                                             */
+    const int32_t *node_ptr, *edge_ptr;   /* [G+1]; NULL allowed for one graph                */
+    const int32_t* n_free;       /* [G]                                                       */
+} gnnmp_frontier_batch;
+
+int gnnmp_frontier_workspace_bytes(const gnnmp_frontier_batch* shape, size_t* bytes);
+int gnnmp_frontier_rank(const gnnmp_frontier_batch* batch, int32_t* row_beg, int32_t* row_len, int32_t* cols, float* vals,
+                        int32_t* status, void* workspace, size_t workspace_bytes, void* hip_stream);
+/* The row lengths at which the implementation changes path: rows of up to wave_row_cells cells are ranked by one wave,
+ * longer ones by a workgroup that streams the row through tiles of block_tile_cells cells. */
+int gnnmp_frontier_limits(int32_t* wave_row_cells, int32_t* block_tile_cells);
 
 /* ------------------------------------------------------------------------------------------
  * The smoother's training targets (train_smoother.py:98): joint_smoother_ratio / joint_smoother (smoother.py:67-151) for

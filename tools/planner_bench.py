@@ -28,6 +28,9 @@ def main():
     ap.add_argument('--problems', type=int, default=48)
     ap.add_argument('--sparse', action='store_true', help='sparse frontier on per-edge scores instead of the dense N x N matrix')
     ap.add_argument('--gpu-graph', action='store_true', help='build the kNN graph on the device')
+    ap.add_argument('--frontier', choices=('heap', 'ranked'), default='heap',
+                    help="'ranked': rows ranked on the device (gnnmp_frontier_rank), one copy, the host walks them; 'heap' (default): "
+                         'the host frontier picked by --sparse')
     ap.add_argument('--device-explore', action='store_true',
                     help='explore stage of ALL problems in one device pass (graphs, forward, greedy loop, collision checks)')
     ap.add_argument('--device-smooth', action='store_true',
@@ -96,13 +99,14 @@ def main():
     np.random.seed(1234)
     torch.manual_seed(1234)
     env.init_new_problem(0)
-    planner.explore(env, m, ms, True, batch=a.batch, t_max=500, k=a.k, device=dev, sparse=a.sparse, gpu_graph=a.gpu_graph)     # warm-up
+    planner.explore(env, m, ms, True, batch=a.batch, t_max=500, k=a.k, device=dev, sparse=a.sparse, gpu_graph=a.gpu_graph,
+                    frontier=a.frontier)     # warm-up
     tot = dict(success=0, forward=0.0, total=0.0, explore=0.0, c_explore=0, c_smooth=0)
     t0 = time.perf_counter()
     for i in range(a.problems):
         env.init_new_problem(i % maps.shape[0])
         r = planner.explore(env, m, ms, True, batch=a.batch, t_max=500, k=a.k, device=dev, sparse=a.sparse,
-                            gpu_graph=a.gpu_graph)
+                            gpu_graph=a.gpu_graph, frontier=a.frontier)
         tot['success'] += int(r['success']); tot['forward'] += r['forward']; tot['total'] += r['total']
         tot['explore'] += r['total_explore']; tot['c_explore'] += r['c_explore']; tot['c_smooth'] += r['c_smooth']
     wall = time.perf_counter() - t0
@@ -112,7 +116,8 @@ def main():
                       'host_s_per_problem': round((tot['total'] - tot['forward']) / n, 4),
                       'collision_checks_explore': round(tot['c_explore'] / n, 2),
                       'collision_checks_total': round((tot['c_explore'] + tot['c_smooth']) / n, 2),
-                      'host_cores_used': 1, 'graph_build': 'device' if a.gpu_graph else 'host', 'frontier': 'sparse heap' if a.sparse else 'dense N x N (reference form)',
+                      'host_cores_used': 1, 'graph_build': 'device' if a.gpu_graph else 'host', 'frontier': 'ranked rows (device sort, host walk)' if a.frontier == 'ranked' else
+                      'sparse heap' if a.sparse else 'dense N x N (reference form)',
                       'config': 'maze2 hard, batch=%d, k=%d, smoothing on' % (a.batch, a.k)}))
 
 
