@@ -13,6 +13,7 @@ from .smoother import ModelSmoother, SmoothBatch  # noqa: F401
 from . import episodes  # noqa: F401,E402  (training supervision: gnnmp_episode_* entry points)
 from . import oracle_smooth  # noqa: F401,E402  (the smoother's training targets: gnnmp_oracle_smooth)
 from . import frontier  # noqa: F401,E402  (ranked frontier rows for the host-checked planner: gnnmp_frontier_rank)
+from . import rng  # noqa: F401,E402  (numpy's MT19937 per problem on the device: gnnmp_mt19937_*)
 
 __all__ = ['graph_build', 'hostenv', 'synth', 'GraphBatch', 'EncoderProcessDecoder', 'ModelSmoother', 'SmoothBatch', 'episodes',
-           'oracle_smooth', 'frontier']
+           'oracle_smooth', 'frontier', 'rng']

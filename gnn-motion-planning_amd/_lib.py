@@ -82,6 +82,11 @@ class MazeStreamsBatch(ctypes.Structure):
                 ('goal_states', ctypes.c_void_p), ('active', ctypes.c_void_p)]
 
 
+class MtUniformBatch(ctypes.Structure):
+    _fields_ = [('n_streams', ctypes.c_int32), ('dim', ctypes.c_int32), ('out_rows', ctypes.c_int64), ('counts', ctypes.c_void_p),
+                ('out_ptr', ctypes.c_void_p), ('active', ctypes.c_void_p), ('low', ctypes.c_double * 3), ('range', ctypes.c_double * 3)]
+
+
 class EpisodeGraphs(ctypes.Structure):
     _fields_ = [('n_problems', ctypes.c_int32), ('total_nodes', ctypes.c_int32), ('total_edges', ctypes.c_int32),
                 ('node_ptr', ctypes.c_void_p), ('edge_ptr', ctypes.c_void_p), ('edge_index', ctypes.c_void_p)]
@@ -196,6 +201,8 @@ def lib():
     L.gnnmp_maze_sample.argtypes = [ctypes.POINTER(MazeSampleBatch), vp, vp, vp, vp, vp, vp]
     L.gnnmp_stick_sample.argtypes = [ctypes.POINTER(MazeSampleBatch), vp, vp, vp, vp, vp, vp, vp]
     L.gnnmp_maze_sample_streams.argtypes = [ctypes.POINTER(MazeStreamsBatch), ctypes.c_int32, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.gnnmp_mt19937_seed.argtypes = [ctypes.c_int32, vp, vp, vp]
+    L.gnnmp_mt19937_uniform.argtypes = [ctypes.POINTER(MtUniformBatch), vp, vp, ctypes.c_int32, vp, vp]
     L.gnnmp_maze_rounds_gather.argtypes = [ctypes.POINTER(MazeRoundsState), ctypes.c_int32, vp, ctypes.c_int32, ctypes.c_int64, vp, vp, vp, vp,
                                            ctypes.POINTER(MazeResume), vp]
     L.gnnmp_maze_rounds_carry.argtypes = [ctypes.POINTER(MazeRoundsState), ctypes.c_int32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,

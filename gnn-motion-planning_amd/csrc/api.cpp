@@ -1582,6 +1582,43 @@ extern "C" int gnnmp_maze_sample_streams(const gnnmp_maze_streams_batch* b, int3
 }
 
 namespace {
+// finite by the exponent bits: the library is built with -fno-honor-nans, which lets the compiler fold std::isfinite(NaN)
+bool finite_bits(double x) {
+    uint64_t u;
+    std::memcpy(&u, &x, sizeof u);
+    return ((u >> 52) & 0x7ff) != 0x7ff;
+}
+}  // namespace
+
+extern "C" int gnnmp_mt19937_seed(int32_t n_streams, const uint32_t* seeds, uint32_t* state, void* hip_stream) {
+    if (!seeds || !state) return GNNMP_ERR_NULL;
+    if (n_streams < 1) return GNNMP_ERR_ARG;
+    HIP_TRY(launch_mt_seed(n_streams, seeds, state, static_cast<hipStream_t>(hip_stream)));
+    return GNNMP_OK;
+}
+
+extern "C" int gnnmp_mt19937_uniform(const gnnmp_mt_uniform_batch* b, uint32_t* state, double* out, int32_t commit,
+                                     int32_t* status_out, void* hip_stream) {
+    if (!b || !state || !status_out || !b->counts) return GNNMP_ERR_NULL;
+    if (b->dim < 1 || b->dim > 3) return GNNMP_ERR_DIMS;
+    if (out && !b->out_ptr) return GNNMP_ERR_NULL;
+    if (b->n_streams < 1 || b->out_rows < 0 || (!out && !commit)) return GNNMP_ERR_ARG;
+    double low[3] = {0.0, 0.0, 0.0}, range[3] = {0.0, 0.0, 0.0};
+    for (int c = 0; c < b->dim; ++c) {
+        if (!(finite_bits(b->low[c]) && finite_bits(b->range[c]))) return GNNMP_ERR_ARG;
+        low[c] = b->low[c];
+        range[c] = b->range[c];
+    }
+    MtUniformParams p;
+    p.low0 = low[0]; p.low1 = low[1]; p.low2 = low[2]; p.range0 = range[0]; p.range1 = range[1]; p.range2 = range[2];
+    p.n = b->n_streams; p.dim = b->dim; p.commit = commit ? 1 : 0; p.out_rows = b->out_rows;
+    p.counts = b->counts; p.out_ptr = reinterpret_cast<const long long*>(b->out_ptr); p.active = b->active;
+    p.state = state; p.out = out; p.status = status_out;
+    HIP_TRY(launch_mt_uniform(p, static_cast<hipStream_t>(hip_stream)));
+    return GNNMP_OK;
+}
+
+namespace {
 int rounds_state_check(const gnnmp_maze_rounds_state* s, bool trees) {
     if (!s) return GNNMP_ERR_NULL;
     if (!s->free_pool || !s->coll_pool || !s->n_free || !s->n_coll) return GNNMP_ERR_NULL;

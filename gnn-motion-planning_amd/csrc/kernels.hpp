@@ -226,6 +226,23 @@ struct MazeStreamsParams {
 };
 hipError_t launch_maze_sample_streams(const MazeStreamsParams& p, hipStream_t st);
 
+// numpy's RandomState (MT19937) per problem on the device (rng_kernels.hip): the streams planner's draws.  A stream's state is
+// uint32 key[624] + int32 pos = 625 words, get_state()'s layout.
+struct MtUniformParams {
+    int n, dim, commit;                   // streams, columns per row (1..3), store the advanced state
+    long long out_rows;                   // rows `out` holds
+    const int* counts;                    // [n] rows per stream
+    const long long* out_ptr;             // [n + 1] row offset of stream b's block in out (read only when out is given)
+    const unsigned char* active;          // [n] or nullptr (= all): 0 = the stream is skipped entirely
+    unsigned* state;                      // [n, 625] in / out
+    double* out;                          // [out_rows, dim] or nullptr: skip the rows instead of writing them
+    int* status;                          // out [n]: 0 done, 2 negative count / block outside out / pos outside [0, 624] (untouched)
+    double low0, low1, low2, range0, range1, range2;     // element (r, c) = low[c] + range[c] * d (scalars: an array in a
+                                          // by-value kernel argument that is indexed at run time is copied to scratch)
+};
+hipError_t launch_mt_seed(int n, const unsigned* seeds, unsigned* state, hipStream_t st);
+hipError_t launch_mt_uniform(const MtUniformParams& p, hipStream_t st);
+
 struct MazeGatherParams {
     int A, B, dim, cap, pair_cap;         // problems of the round (the [A] / [A + 1] outputs), slots of the store
     long long v_rows;                     // rows v can hold

@@ -740,8 +740,9 @@ __global__ __launch_bounds__(64) void maze_steer_kernel(MazeSteerParams p) {
 // MazeEnv.sample_n_points, maze_env.py): draw a uniform point of [-1, 1)^2 from the GLOBAL numpy generator, keep it if its grid
 // cell is free, until n free points exist; the rejected draws of the same loop become the problem's collided samples (the first n
 // of them), and the NEXT problem continues in the same random stream -- so where problem b + 1 starts depends on how many
-// draws problem b needed.  The draws themselves stay with the host (numpy's Mersenne twister: cheap, and it keeps the recorded
-// known answers); what moves here is everything after them: the classification of every draw (float64 arithmetic of
+// draws problem b needed.  For this one GLOBAL stream the draws themselves stay with the host (numpy's Mersenne twister: cheap,
+// it keeps the recorded known answers, and a global stream cannot be run ahead without knowing how much each problem consumes;
+// the per-problem streams of maze_sample_streams_kernel below can be drawn on the device, rng_kernels.hip); what moves here is everything after them: the classification of every draw (float64 arithmetic of
 // ((x + 1.0) * w / 2.0).astype(int), clipped at w - 1, one map lookup), the position of the n-th free draw, the compaction into
 // the float32 node rows [start, goal, free ..., rejected ...] the graph builder and the explorer read, the per-problem counts.
 // ONE workgroup walks the problems in stream order (the dependency is serial), 1024 draws per step: a block scan of the free

@@ -1244,7 +1244,7 @@ def maze_rounds_explore(store, g, ei, edge_ptr, scores, maps, goal64, between=No
 
 @torch.no_grad()
 def plan_maze_rounds_batch(problems, model, device, seeds, batch=500, t_max=500, k=30, loop=5, model_s=None, smooth_iters=5,
-                           timings=None):
+                           timings=None, draws='host'):
     """The general loop of ``explore`` (eval_gnn.py:191-247) for many maze problems at once (point robot or stick robot, by the
     width of ``init_state``), every problem on its OWN sample stream: the draws of problem i are
     ``np.random.RandomState(seeds[i]).uniform(-LIMITS, LIMITS, (m, dim))`` -- the values ``np.random.seed(seeds[i])`` followed by
@@ -1258,6 +1258,13 @@ def plan_maze_rounds_batch(problems, model, device, seeds, batch=500, t_max=500,
     host reads two small arrays: the sampler's status / used / collided counts (they size the next block and the node rows) and
     the success flags; the graph build reads its edge count as before.  Trees, pairs and parents never visit Python.
     With ``model_s`` the solved problems go through the smoothing stage on the device afterwards.
+
+    ``draws``: ``'host'`` -- B ``RandomState`` objects draw every block in a Python loop and the blocks are copied over;
+    ``'device'`` -- the same generators run on the device (:class:`gnnmp.rng.MTStreams`, numpy's MT19937 bit for bit): a
+    sampling attempt fills ``want`` rows per pending problem from the problem's uncommitted state, the sampler runs on them
+    unchanged, and the streams that finished are advanced by the rows they consumed; a problem whose block ended first is
+    filled again from the same state with twice the rows.  Only the block offsets go to the device, and the generators'
+    status words come back in the read the sampler's counts already need.  Identical results for every problem.
 
     Returns one dict per problem with the fields of :func:`explore_maze_batch` plus ``rounds``; ``c_explore`` = sampling checks
     + explore checks over all rounds, ``explored_edges`` the full pair list."""
@@ -1278,6 +1285,8 @@ def plan_maze_rounds_batch(problems, model, device, seeds, batch=500, t_max=500,
         raise ValueError('plan_maze_rounds_batch: one seed per problem')
     if n < 1 or n > t_max:
         raise ValueError('plan_maze_rounds_batch: 1 <= batch <= t_max')
+    if draws not in ('host', 'device'):
+        raise ValueError("plan_maze_rounds_batch: draws is 'host' or 'device'")
     tm = time.perf_counter()
     dev = torch.device(device)
     dim = _problems_dim(problems)
@@ -1299,8 +1308,12 @@ def plan_maze_rounds_batch(problems, model, device, seeds, batch=500, t_max=500,
     optr_all = np.zeros(B + 1, dtype=np.int64)
     optr_all[1:] = np.cumsum(ocount)
     obs_all = torch.from_numpy(np.ascontiguousarray(np.concatenate(obs), dtype=np.float32)).to(dev)
-    gens = [np.random.RandomState(int(s) & 0xffffffff) for s in seeds]
-    bufs = [np.zeros((0, dim))] * B                                      # drawn, not yet consumed
+    if draws == 'device':
+        from .rng import MTStreams
+        streams = MTStreams(seeds, dev)
+    else:
+        gens = [np.random.RandomState(int(s) & 0xffffffff) for s in seeds]
+        bufs = [np.zeros((0, dim))] * B                                  # drawn, not yet consumed
     samp_checks = torch.zeros(B, dtype=torch.int64, device=dev)
     n_coll_h = np.zeros(B, dtype=np.int64)
     rounds = np.zeros(B, dtype=np.int64)
@@ -1314,6 +1327,31 @@ def plan_maze_rounds_batch(problems, model, device, seeds, batch=500, t_max=500,
             act_mask[act] = 1
             act_mask_d = torch.from_numpy(act_mask).to(dev)
             drawn = consumed = 0
+            while pending.size and draws == 'device':
+                counts = np.zeros(B, dtype=np.int64)
+                counts[pending] = want
+                att_ptr = np.zeros(B + 1, dtype=np.int64)
+                att_ptr[1:] = np.cumsum(counts)
+                mask = np.zeros(B, dtype=np.uint8)
+                mask[pending] = 1
+                mask_d = torch.from_numpy(mask).to(dev)
+                att, gstat = streams.uniform(counts, -limits, limits, out_ptr=att_ptr, active=mask_d)      # not committed
+                used, checks, status = maze_sample_streams(store, att, att_ptr, maps, init64, goal64, n, active=mask_d)
+                samp_checks += checks * mask_d
+                streams.advance(used, dim, active=mask_d)                # used is 0 for whoever ran out: those stay put
+                status_h, used_h, ncoll, gstat_h = torch.stack((status, used, store.n_coll, gstat)).cpu().numpy()
+                if gstat_h[pending].any():
+                    raise RuntimeError('gnnmp_mt19937_uniform: status %s for problem(s) %s'
+                                       % (gstat_h[pending][gstat_h[pending] != 0].tolist(), pending[gstat_h[pending] != 0].tolist()))
+                if (status_h[pending] > 1).any():
+                    raise RuntimeError('gnnmp_maze_sample_streams: no room in the pools of problem(s) %s'
+                                       % pending[status_h[pending] > 1].tolist())
+                fin = pending[status_h[pending] == 0]
+                n_coll_h[fin] = ncoll[fin]
+                drawn += n * int(fin.size)
+                consumed += int(used_h[fin].sum())
+                pending = pending[status_h[pending] == 1]
+                want *= 2
             while pending.size:
                 counts = np.zeros(B, dtype=np.int64)
                 for i in pending:
@@ -1418,7 +1456,7 @@ def stream_seeds(seed, indexes):
 
 
 def eval_gnn_device_streams(env, indexes, model, model_s=None, seed=1234, seeds=None, batch=500, t_max=500, k=30, device='cuda',
-                            loop=5, chunk=256, rows_out=None, details_out=None, timings=None):
+                            loop=5, chunk=256, rows_out=None, details_out=None, timings=None, draws='host'):
     """:func:`eval_gnn_device_rounds` with one sample stream PER PROBLEM (:func:`plan_maze_rounds_batch`, ``chunk`` problems per
     batch): same return dict, ``rows_out`` / ``details_out`` filled the same way.  Problem ``indexes[i]`` draws from
     ``np.random.RandomState(seeds[i])``; default ``seeds[i] = (seed + 0x9E3779B1 * (indexes[i] + 1)) mod 2**32``
@@ -1427,7 +1465,8 @@ def eval_gnn_device_streams(env, indexes, model, model_s=None, seed=1234, seeds=
     which walk one global stream problem after problem -- other samples of the same distribution -- and in exchange they do not
     depend on the order of ``indexes``, on ``chunk`` or on how the problems are sharded over ranks: no rank has to wind a
     generator past other ranks' problems.  The global numpy generator is left alone.  ``chunk`` bounds the device memory of
-    the per-problem store (:class:`MazeRoundsStore`: about 0.5 MB per problem at the default settings)."""
+    the per-problem store (:class:`MazeRoundsStore`: about 0.5 MB per problem at the default settings).  ``draws``: where the
+    generators run, ``'host'`` or ``'device'`` (:func:`plan_maze_rounds_batch`); the results are the same."""
     model.eval()                       # eval_gnn.py:109-110
     if model_s is not None:
         model_s.eval()
@@ -1439,7 +1478,7 @@ def eval_gnn_device_streams(env, indexes, model, model_s=None, seed=1234, seeds=
         part = indexes[c0:c0 + max(int(chunk), 1)]
         pr = [dict(map=env.maps[i], init_state=env.init_states[i], goal_state=env.goal_states[i]) for i in part]
         res = plan_maze_rounds_batch(pr, model, device, seeds[c0:c0 + len(part)], batch=batch, t_max=t_max, k=k, loop=loop,
-                                     model_s=model_s, timings=timings)
+                                     model_s=model_s, timings=timings, draws=draws)
         for r in res:
             p = r['path'] if r['success'] else np.zeros((0, dim), dtype=np.float32)
             sp, cs = (r.get('smooth_path', p), r.get('c_smooth', 0)) if r['success'] else (p, 0)

@@ -24,6 +24,8 @@
  *       the same for MazeEnv(dim=3): _stick_in_free_space per draw     environment/maze_env.py:279-314
  *   gnnmp_maze_sample_streams / gnnmp_maze_rounds_gather / gnnmp_maze_rounds_carry
  *       explore()'s resample rounds for a batch, one sample stream per problem     eval_gnn.py:191-247
+ *   gnnmp_mt19937_seed / gnnmp_mt19937_uniform
+ *       np.random.seed(s_b) + uniform_sample's draws, one numpy generator per problem    eval_gnn.py:180, 241-245, environment/maze_env.py
  *   gnnmp_maze_steer / gnnmp_stick_steer
  *       proposed_path_smootherv2 (steering of the smoothing stage)  smoother.py:194-216
  *   gnnmp_maze_explore_workspace_bytes / gnnmp_maze_explore / gnnmp_maze_explore_ex
@@ -604,6 +606,50 @@ int gnnmp_maze_rounds_carry(const gnnmp_maze_rounds_state* state, int32_t n_acti
                             const int32_t* n_explored, const int32_t* explored, const int32_t* prev, const int32_t* n_pairs,
                             const int32_t* explored_edges, const int32_t* path_len, const int32_t* path, const int64_t* checks,
                             int32_t* status_out, void* hip_stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The per-problem sample streams themselves, drawn on the device: numpy's legacy generator (np.random.RandomState = MT19937),
+ * bit for bit.  Problem b of the streams planner draws what np.random.seed(s_b) followed by the reference's one-by-one
+ * uniform_sample calls gives (eval_gnn.py:180, 241-245 through environment/maze_env.py uniform_sample =
+ * np.random.uniform(-LIMITS, LIMITS)); with one generator per problem those are B independent recurrences, so they can be
+ * produced where gnnmp_maze_sample_streams reads them.
+ * A stream's state is 625 words: uint32 key[624] followed by int32 pos -- RandomState.get_state()[1:3], so a state can be
+ * compared with numpy's or taken from it (any pos in [0, 624], odd ones included).  The twist is numpy's LAZY one: a block
+ * of 624 words is regenerated when a word is needed and pos == 624, so a stream that consumed exactly to the end of a block
+ * keeps pos = 624 and the old key.
+ * ---------------------------------------------------------------------------------------- */
+/* np.random.RandomState(seeds[i]) for i < n_streams: init_genrand (key[0] = seed, key[j] = 1812433253 * (key[j-1] ^
+ * (key[j-1] >> 30)) + j, pos = 624) into state [n_streams, 625].  One launch.  GNNMP_ERR_NULL / GNNMP_ERR_ARG (n_streams < 1). */
+int gnnmp_mt19937_seed(int32_t n_streams, const uint32_t* seeds, uint32_t* state, void* hip_stream);
+
+/* RandomState.uniform(low, high, (counts[b], dim)) of every stream: each double takes two consecutive tempered words a, b --
+ * d = ((a >> 5) * 67108864.0 + (b >> 6)) / 9007199254740992.0 -- and element (r, c), in C order, is low[c] + range[c] * d with
+ * range = high - low taken by the caller in double (numpy's uniform with array bounds); two rounded operations, never fused.
+ * Three modes:
+ *   out, commit = 0    fill: counts[b] rows at row out_ptr[b] of out [out_rows, dim]; the stored state is left alone, so the
+ *                      same state can be filled from again (with a longer count);
+ *   out, commit = 1    fill and store the advanced state;
+ *   out NULL, commit   advance: skip counts[b] rows (counts is int32 so that gnnmp_maze_sample_streams' used_out can be
+ *                      passed as it is; out_ptr is not read).
+ * status_out [n_streams]: 0 = done; 2 = a negative count, a block [out_ptr[b], out_ptr[b] + counts[b]) outside
+ * [0, out_rows], or a pos outside [0, 624]: neither the stream's state nor out is touched and the other streams complete.
+ * active [n_streams] (uint8) or NULL = all: a stream with 0 is skipped entirely (its status word included).  out_ptr is
+ * int64 [n_streams + 1] like gnnmp_maze_streams_batch's att_ptr, which can be passed here.  One workgroup per stream, one
+ * launch on hip_stream; no allocation, no synchronisation, no atomics, deterministic.
+ * Returns, before any launch: GNNMP_ERR_NULL (batch, counts, state, status_out, or out given without out_ptr),
+ * GNNMP_ERR_DIMS (dim outside 1..3), GNNMP_ERR_ARG (n_streams < 1, out_rows < 0, a bound of a used column not finite, or
+ * neither out nor commit). */
+typedef double gnnmp_mt_bounds[3];
+typedef struct {
+    int32_t n_streams, dim;
+    int64_t out_rows;
+    const int32_t* counts;       /* [n_streams]                                                */
+    const int64_t* out_ptr;      /* [n_streams + 1], or NULL when out is NULL                  */
+    const uint8_t* active;       /* [n_streams] or NULL                                        */
+    gnnmp_mt_bounds low, range;  /* by value; entries behind dim are ignored                   */
+} gnnmp_mt_uniform_batch;
+int gnnmp_mt19937_uniform(const gnnmp_mt_uniform_batch* batch, uint32_t* state, double* out_or_null, int32_t commit,
+                          int32_t* status_out, void* hip_stream);
 
 /* ------------------------------------------------------------------------------------------
  * Supervision of the explorer's training step (train_explorer.py:124-176): edge labels, shortest paths to the goal,
