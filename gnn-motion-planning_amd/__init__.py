@@ -14,6 +14,8 @@ from . import episodes  # noqa: F401,E402  (training supervision: gnnmp_episode_
 from . import oracle_smooth  # noqa: F401,E402  (the smoother's training targets: gnnmp_oracle_smooth)
 from . import frontier  # noqa: F401,E402  (ranked frontier rows for the host-checked planner: gnnmp_frontier_rank)
 from . import rng  # noqa: F401,E402  (numpy's MT19937 per problem on the device: gnnmp_mt19937_*)
+from . import lazysp  # noqa: F401,E402  (the LazySP baseline on maze problems: gnnmp_lazysp_*)
+from .lazysp import eval_lazysp_device, plan_host as lazysp_plan_host, plan_maze_batch as plan_lazysp_maze_batch  # noqa: F401,E402
 
 __all__ = ['graph_build', 'hostenv', 'synth', 'GraphBatch', 'EncoderProcessDecoder', 'ModelSmoother', 'SmoothBatch', 'episodes',
-           'oracle_smooth', 'frontier', 'rng']
+           'oracle_smooth', 'frontier', 'rng', 'lazysp', 'eval_lazysp_device', 'lazysp_plan_host', 'plan_lazysp_maze_batch']

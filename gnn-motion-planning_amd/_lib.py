@@ -6,7 +6,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('GNNMP_LIB') or os.path.join(_HERE, 'libgnnmp.so')      # GNNMP_LIB: an experiment build (tools/diag/build_variant.sh)
 
-ABI_VERSION = 4                        # include/gnnmp.h gnnmp_abi_version(): what this binding was written against
+ABI_VERSION = 5                        # include/gnnmp.h gnnmp_abi_version(): what this binding was written against
 
 c_float_p = ctypes.POINTER(ctypes.c_float)
 c_int32_p = ctypes.POINTER(ctypes.c_int32)
@@ -80,6 +80,13 @@ class MazeStreamsBatch(ctypes.Structure):
                 ('n_attempts', ctypes.c_int64), ('attempts', ctypes.c_void_p), ('att_ptr', ctypes.c_void_p),
                 ('att_ptr_host', ctypes.c_void_p), ('maps', ctypes.c_void_p), ('init_states', ctypes.c_void_p),
                 ('goal_states', ctypes.c_void_p), ('active', ctypes.c_void_p)]
+
+
+class LazySPState(ctypes.Structure):
+    _fields_ = [('n_problems', ctypes.c_int32), ('cap', ctypes.c_int32), ('pair_cap', ctypes.c_int32),
+                ('pool', ctypes.c_void_p), ('n_nodes', ctypes.c_void_p), ('pairs', ctypes.c_void_p), ('pair_state', ctypes.c_void_p),
+                ('n_pairs', ctypes.c_void_p), ('checks', ctypes.c_void_p), ('dijkstra_runs', ctypes.c_void_p),
+                ('path_len', ctypes.c_void_p), ('path', ctypes.c_void_p), ('solved', ctypes.c_void_p), ('status', ctypes.c_void_p)]
 
 
 class MtUniformBatch(ctypes.Structure):
@@ -207,6 +214,14 @@ def lib():
                                            ctypes.POINTER(MazeResume), vp]
     L.gnnmp_maze_rounds_carry.argtypes = [ctypes.POINTER(MazeRoundsState), ctypes.c_int32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
                                           vp, vp, vp, vp]
+    L.gnnmp_lazysp_pair_cap.argtypes = [ctypes.c_int32, ctypes.c_int32, i32p, c_int64_p]
+    L.gnnmp_lazysp_sample.argtypes = [ctypes.POINTER(MazeStreamsBatch), ctypes.c_int32, ctypes.POINTER(LazySPState), vp, vp, vp, vp]
+    L.gnnmp_lazysp_gather.argtypes = [ctypes.POINTER(LazySPState), ctypes.c_int32, ctypes.c_int32, vp, vp, ctypes.c_int64, vp, vp, vp,
+                                      vp, vp]
+    L.gnnmp_lazysp_workspace_bytes.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, ctypes.POINTER(sz)]
+    L.gnnmp_lazysp_lds_nodes.argtypes = []
+    L.gnnmp_lazysp_round.argtypes = [ctypes.POINTER(LazySPState), ctypes.c_int32, ctypes.c_int32, vp, vp, ctypes.c_int64, vp, vp,
+                                     ctypes.c_int32, vp, sz, vp]
     L.gnnmp_maze_steer.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, vp, vp, vp, vp, vp, vp, vp, vp]
     L.gnnmp_stick_steer.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.gnnmp_episode_label_maze.argtypes = [ctypes.POINTER(EpisodeGraphs), ctypes.c_int32, ctypes.c_int32, vp, vp, vp, vp, vp]

@@ -248,7 +248,7 @@ extern "C" const char* gnnmp_status_string(int s) {
 }
 extern "C" const char* gnnmp_last_hip_error(void) { return g_hip_error.c_str(); }
 // 2: stage list of gnnmp_explorer_profile_read (fused message passing); 3: device-side status words (gnnmp_*_status*)
-extern "C" int gnnmp_abi_version(void) { return 4; }
+extern "C" int gnnmp_abi_version(void) { return 5; }
 
 // ---------------------------------------------------------------------------------------------
 // explorer handle
@@ -1671,6 +1671,122 @@ extern "C" int gnnmp_maze_rounds_carry(const gnnmp_maze_rounds_state* s, int32_t
     p.tree_path_len = s->tree_path_len; p.tree_path = s->tree_path; p.tree_checks = reinterpret_cast<long long*>(s->tree_checks);
     p.status = status_out;
     HIP_TRY(launch_maze_rounds_carry(p, static_cast<hipStream_t>(hip_stream)));
+    return GNNMP_OK;
+}
+
+// =============================================================================================
+// the LazySP baseline on maze problems (lazysp_kernels.hip; algorithm/lazy_sp.py:147-196)
+// =============================================================================================
+namespace {
+int lazysp_state_check(const gnnmp_lazysp_state* s, bool lists) {
+    if (!s) return GNNMP_ERR_NULL;
+    if (!s->pool || !s->n_nodes) return GNNMP_ERR_NULL;
+    if (lists && (!s->pairs || !s->pair_state || !s->n_pairs || !s->checks || !s->dijkstra_runs || !s->path_len || !s->path ||
+                  !s->solved || !s->status))
+        return GNNMP_ERR_NULL;
+    if (s->n_problems < 1 || s->cap < 1 || s->pair_cap < 1 || (long long)s->n_problems * s->pair_cap > (1ll << 30)) return GNNMP_ERR_ARG;
+    return GNNMP_OK;
+}
+size_t lsp_align(size_t x) { return (x + 255) & ~(size_t)255; }
+struct LspCarve { size_t cost, flag, dist, prev, rb, total; };
+LspCarve lsp_carve(int n_active, int cap, long long total_edges) {
+    LspCarve c;
+    const size_t nodes = (size_t)n_active * ((size_t)cap + 3);
+    size_t off = 0;
+    c.cost = off; off = lsp_align(off + sizeof(double) * (size_t)total_edges);
+    c.flag = off; off = lsp_align(off + (size_t)total_edges);
+    c.dist = off; off = lsp_align(off + sizeof(unsigned long long) * nodes);
+    c.prev = off; off = lsp_align(off + sizeof(int) * nodes);
+    c.rb = off;   off = lsp_align(off + sizeof(int) * nodes);
+    c.total = off;
+    return c;
+}
+}  // namespace
+
+extern "C" int gnnmp_lazysp_pair_cap(int32_t batch, int32_t n_rounds, const int32_t* k1_by_round, int64_t* pair_cap) {
+    if (!k1_by_round || !pair_cap) return GNNMP_ERR_NULL;
+    if (batch < 1 || n_rounds < 1) return GNNMP_ERR_ARG;
+    long long cap = 0;
+    for (int r = 1; r <= n_rounds; ++r) {
+        const long long n = 2 + (long long)r * batch, k1 = k1_by_round[r - 1];
+        if (k1 < 1) return GNNMP_ERR_ARG;
+        const long long by_k = (k1 < n ? k1 : n) * n, all = n * (n - 1) / 2;
+        cap += by_k < all ? by_k : all;
+        if (cap > (1ll << 30)) return GNNMP_ERR_ARG;
+    }
+    *pair_cap = cap < 1 ? 1 : cap;
+    return GNNMP_OK;
+}
+
+extern "C" int gnnmp_lazysp_sample(const gnnmp_maze_streams_batch* b, int32_t dim, const gnnmp_lazysp_state* s, int32_t* used_out,
+                                   int64_t* checks_out, int32_t* status_out, void* hip_stream) {
+    if (dim != 2 && dim != 3) return GNNMP_ERR_DIMS;
+    if (!b || !used_out || !checks_out || !status_out) return GNNMP_ERR_NULL;
+    if (!b->attempts || !b->att_ptr || !b->maps || !b->init_states || !b->goal_states) return GNNMP_ERR_NULL;
+    if (const int rc = lazysp_state_check(s, false)) return rc;
+    if (!s->checks) return GNNMP_ERR_NULL;
+    if (b->n_problems < 1 || b->n_problems != s->n_problems || b->width < 1 || b->n_free < 1 || s->cap < b->n_free || b->n_attempts < 0)
+        return GNNMP_ERR_ARG;
+    if (b->att_ptr_host) {
+        if (b->att_ptr_host[0] < 0 || b->att_ptr_host[b->n_problems] > b->n_attempts) return GNNMP_ERR_ARG;
+        for (int i = 0; i < b->n_problems; ++i)
+            if (b->att_ptr_host[i + 1] < b->att_ptr_host[i]) return GNNMP_ERR_ARG;
+    }
+    LspSampleParams p;
+    p.B = b->n_problems; p.w = b->width; p.n = b->n_free; p.cap = s->cap; p.dim = dim;
+    p.attempts = b->attempts; p.M = b->n_attempts; p.att_ptr = reinterpret_cast<const long long*>(b->att_ptr);
+    p.maps = b->maps; p.init_states = b->init_states; p.goal_states = b->goal_states; p.active = b->active;
+    p.pool = s->pool; p.n_nodes = s->n_nodes; p.checks = reinterpret_cast<long long*>(s->checks);
+    p.used = used_out; p.checks_out = reinterpret_cast<long long*>(checks_out); p.status = status_out;
+    HIP_TRY(launch_lsp_sample(p, static_cast<hipStream_t>(hip_stream)));
+    return GNNMP_OK;
+}
+
+extern "C" int gnnmp_lazysp_gather(const gnnmp_lazysp_state* s, int32_t dim, int32_t n_active, const int32_t* slot_of,
+                                   const int32_t* k1_table, int64_t v_rows, float* v_out, int32_t* node_ptr_out,
+                                   int32_t* n_free_out, int32_t* k1_out, void* hip_stream) {
+    if (dim != 2 && dim != 3) return GNNMP_ERR_DIMS;
+    if (!slot_of || !k1_table || !v_out || !node_ptr_out || !n_free_out || !k1_out) return GNNMP_ERR_NULL;
+    if (const int rc = lazysp_state_check(s, false)) return rc;
+    if (v_rows < 0 || n_active < 1 || n_active > s->n_problems) return GNNMP_ERR_ARG;
+    LspGatherParams p;
+    p.A = n_active; p.B = s->n_problems; p.cap = s->cap; p.dim = dim; p.v_rows = v_rows;
+    p.slot_of = slot_of; p.pool = s->pool; p.n_nodes = s->n_nodes; p.k1_table = k1_table;
+    p.v = v_out; p.node_ptr = node_ptr_out; p.n_free_out = n_free_out; p.k1_out = k1_out;
+    HIP_TRY(launch_lsp_gather(p, static_cast<hipStream_t>(hip_stream)));
+    return GNNMP_OK;
+}
+
+extern "C" int gnnmp_lazysp_workspace_bytes(int32_t n_active, int32_t cap, int64_t total_edges, size_t* bytes) {
+    if (!bytes) return GNNMP_ERR_NULL;
+    if (n_active < 1 || cap < 1 || total_edges < 0) return GNNMP_ERR_ARG;
+    *bytes = lsp_carve(n_active, cap, total_edges).total;
+    return GNNMP_OK;
+}
+
+extern "C" int gnnmp_lazysp_lds_nodes(void) { return lsp_lds_nodes(); }
+
+extern "C" int gnnmp_lazysp_round(const gnnmp_lazysp_state* s, int32_t dim, int32_t n_active, const int32_t* slot_of,
+                                  const int64_t* edge_index, int64_t total_edges, const int32_t* edge_ptr, const double* maps,
+                                  int32_t width, void* workspace, size_t workspace_bytes, void* hip_stream) {
+    if (dim != 2 && dim != 3) return GNNMP_ERR_DIMS;
+    if (!edge_index || !edge_ptr || !maps || !workspace) return GNNMP_ERR_NULL;
+    if (const int rc = lazysp_state_check(s, true)) return rc;
+    if (n_active < 1 || n_active > s->n_problems || width < 1 || total_edges < 0) return GNNMP_ERR_ARG;
+    const LspCarve c = lsp_carve(n_active, s->cap, total_edges);
+    if (workspace_bytes < c.total || (reinterpret_cast<uintptr_t>(workspace) & 255)) return GNNMP_ERR_WORKSPACE;
+    char* ws = static_cast<char*>(workspace);
+    LspRoundParams p;
+    p.A = n_active; p.B = s->n_problems; p.cap = s->cap; p.pair_cap = s->pair_cap; p.dim = dim; p.w = width;
+    p.total_edges = total_edges; p.slot_of = slot_of; p.edge_ptr = edge_ptr;
+    p.edge_index = reinterpret_cast<const long long*>(edge_index); p.maps = maps;
+    p.pool = s->pool; p.n_nodes = s->n_nodes; p.pairs = s->pairs; p.n_pairs = s->n_pairs; p.dijkstra_runs = s->dijkstra_runs;
+    p.path_len = s->path_len; p.path = s->path; p.status = s->status; p.solved = s->solved; p.pair_state = s->pair_state;
+    p.checks = reinterpret_cast<long long*>(s->checks);
+    p.ws_cost = reinterpret_cast<double*>(ws + c.cost); p.ws_flag = reinterpret_cast<unsigned char*>(ws + c.flag);
+    p.ws_dist = reinterpret_cast<unsigned long long*>(ws + c.dist); p.ws_prev = reinterpret_cast<int*>(ws + c.prev);
+    p.ws_rb = reinterpret_cast<int*>(ws + c.rb);
+    HIP_TRY(launch_lsp_round(p, static_cast<hipStream_t>(hip_stream)));
     return GNNMP_OK;
 }
 

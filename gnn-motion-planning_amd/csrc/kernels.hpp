@@ -267,6 +267,55 @@ struct MazeCarryParams {
 };
 hipError_t launch_maze_rounds_carry(const MazeCarryParams& p, hipStream_t st);
 
+// ---- the LazySP baseline on maze problems (lazysp_kernels.hip, algorithm/lazy_sp.py:147-196)
+struct LspSampleParams {
+    int B, w, n, cap, dim;                // problems, map width, free draws to append, pool capacity (rows behind goal / start), 2 / 3
+    const double* attempts;               // [M, dim], problem b's block at att_ptr[b]
+    long long M;
+    const long long* att_ptr;             // [B + 1]
+    const double *maps, *init_states, *goal_states;      // [B, w, w], [B, dim], [B, dim]
+    const unsigned char* active;          // [B] or nullptr (= all)
+    double* pool;                         // [B, cap + 2, dim]: row 0 = goal, row 1 = start, then the free draws
+    int* n_nodes;                         // [B] in / out
+    long long* checks;                    // [B] the store's running total: incremented
+    int* used;                            // out [B]
+    long long* checks_out;                // out [B]: this call's checks
+    int* status;                          // out [B]: 0 done, 1 the block ended first, 2 no room / block outside attempts
+};
+hipError_t launch_lsp_sample(const LspSampleParams& p, hipStream_t st);
+
+struct LspGatherParams {
+    int A, B, cap, dim;
+    long long v_rows;
+    const int* slot_of;                   // [A]
+    const double* pool;
+    const int* n_nodes;                   // [B]
+    const int* k1_table;                  // [cap + 3]: k1 by node count
+    float* v;                             // out [v_rows, dim]
+    int *node_ptr, *n_free_out, *k1_out;  // out [A + 1], [A], [A]
+};
+hipError_t launch_lsp_gather(const LspGatherParams& p, hipStream_t st);
+
+struct LspRoundParams {
+    int A, B, cap, pair_cap, dim, w;
+    long long total_edges;                // row stride of edge_index
+    const int* slot_of;                   // [A] or nullptr (= j)
+    const int* edge_ptr;                  // [A + 1]
+    const long long* edge_index;          // [2, total_edges]
+    const double* maps;                   // [B, w, w] by slot
+    const double* pool;                   // the store
+    const int* n_nodes;
+    int *pairs, *n_pairs, *dijkstra_runs, *path_len, *path, *status, *solved;
+    unsigned char* pair_state;
+    long long* checks;
+    double* ws_cost;                      // workspace: [total_edges]
+    unsigned char* ws_flag;               // [total_edges]
+    unsigned long long* ws_dist;          // [A, cap + 3] (problems beyond the LDS node count)
+    int *ws_prev, *ws_rb;                 // [A, cap + 3] each
+};
+hipError_t launch_lsp_round(const LspRoundParams& p, hipStream_t st);
+int lsp_lds_nodes();
+
 // ---- supervision of the explorer's training step (train_episode_kernels.hip, train_explorer.py:124-176)
 struct EpLabelParams {                    // (a) edge_free / edge_cost of construct_graph for maze problems
     int B, dim, w;

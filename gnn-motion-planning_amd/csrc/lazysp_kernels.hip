@@ -1,0 +1,520 @@
+// lazysp_kernels.hip -- the LazySP baseline planner (algorithm/lazy_sp.py:147-196 over algorithm/dijkstra.py:34-76) for
+// batches of maze problems, every problem on its own sample stream.  The host loops over rounds only:
+//   lsp_sample_kernel   informed_sample (lazy_sp.py:78-103): `batch` more free draws appended to a float64 pool per problem,
+//                       every draw through MazeEnv._state_fp with its collision checks counted;
+//   lsp_gather_kernel   the round's float32 node rows, node_ptr, n_free (= N: every LazySP node is free) and k1 in the
+//                       layout gnnmp_graph_build reads;
+//   lsp_round_kernel    the round itself: carried pairs marked in the new graph, edge costs, then Dijkstra / walk the path /
+//                       check its unknown edges / invalidate the first blocked one, until the path is valid or the start is
+//                       unreachable.  One wave per problem; no wave ever waits on another workgroup.
+// Node 0 is the GOAL and node 1 the START (lazy_sp.py:61).  All decisions are float64, one rounded operation at a time.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include "kernels.hpp"
+
+// numpy rounds every float64 operation on its own; the one fused chain is the dot product of np.linalg.norm (lsp_cost)
+#pragma clang fp contract(off)
+
+namespace gnnmp {
+
+namespace {
+
+constexpr int kLspLdsCells = 4096;       // maps up to 64 x 64 are staged into LDS as bytes
+constexpr int kLspMaxLevel = 30;         // bisection levels the walk can address (a segment of L1 length <= 4 splits 7 times)
+
+struct LspMaze {
+    const unsigned char* occ;            // LDS copy (1 = obstacle) or nullptr
+    const double* map;                   // [w, w] row-major map[x][y]
+    int w;
+};
+
+__device__ __forceinline__ void lsp_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+}
+__device__ __forceinline__ int lsp_wave_sum(int x) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off, 64);
+    return x;
+}
+__device__ __forceinline__ unsigned long long lsp_wave_min_u64(unsigned long long k) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const unsigned long long o = __shfl_xor(k, off, 64);
+        k = o < k ? o : k;
+    }
+    return k;
+}
+// all lanes: stage the map (64 lanes)
+__device__ __forceinline__ LspMaze lsp_maze(const double* map, int w, unsigned char* occ, int lane) {
+    LspMaze m{nullptr, map, w};
+    if (w * w <= kLspLdsCells) {
+        for (int i = lane; i < w * w; i += 64) occ[i] = map[i] == 0.0 ? 0 : 1;
+        m.occ = occ;
+    }
+    lsp_sync();
+    return m;
+}
+
+// ---- MazeEnv's checker on float64 states, every in-bounds point query counted (environment/maze_env.py:236-347)
+__device__ __forceinline__ int lsp_cell(double x, int w) {      // ((x + 1.0) * w / 2.0).astype(int), clipped at w - 1
+    const int c = (int)((x + 1.0) * (double)w / 2.0);
+    return c > w - 1 ? w - 1 : c;
+}
+__device__ __forceinline__ bool lsp_valid2(double x, double y) { return x >= -1.0 && x <= 1.0 && y >= -1.0 && y <= 1.0; }
+__device__ __forceinline__ bool lsp_point(const LspMaze& m, double x, double y, int& cnt) {      // _point_in_free_space
+    if (!lsp_valid2(x, y)) return false;
+    cnt += 1;
+    const int idx = lsp_cell(x, m.w) * m.w + lsp_cell(y, m.w);
+    return m.occ ? m.occ[idx] == 0 : m.map[idx] == 0.0;
+}
+// _iterative_check_segment without a stack: the recursion's tree is walked in its own order (a node's midpoint, its left half,
+// its right half; nothing after the first blocked midpoint) by (level, index), and a node's end points are recomputed from
+// the root -- index bit d from the top: 0 = left half -- with the very (l + r) / 2.0 the recursion applies, so every midpoint
+// is the recursion's, bit for bit.  No LDS, no scratch; a node costs `level` halvings (level <= 7 for these mazes).
+__device__ bool lsp_segment(const LspMaze& m, double ax, double ay, double bx, double by, int& cnt) {
+    int level = 0;
+    unsigned idx = 0;
+    while (true) {
+        double lx = ax, ly = ay, rx = bx, ry = by;
+        for (int d = level - 1; d >= 0; --d) {
+            const double hx = (lx + rx) / 2.0, hy = (ly + ry) / 2.0;
+            if ((idx >> d) & 1u) { lx = hx; ly = hy; } else { rx = hx; ry = hy; }
+        }
+        const int dc = abs(lsp_cell(lx, m.w) - lsp_cell(rx, m.w)) + abs(lsp_cell(ly, m.w) - lsp_cell(ry, m.w));
+        const double l1 = fabs(lx - rx) + fabs(ly - ry);
+        if (dc > 1 && l1 > 0.05 && level < kLspMaxLevel) {
+            if (!lsp_point(m, (lx + rx) / 2.0, (ly + ry) / 2.0, cnt)) return false;
+            ++level;
+            idx <<= 1;                                           // the left half comes first
+            continue;
+        }
+        while (level > 0 && (idx & 1u)) { idx >>= 1; --level; }  // a right half is done: so is its parent
+        if (level == 0) return true;
+        idx |= 1u;                                               // the right half of the same parent
+    }
+}
+__device__ bool lsp_edge2(const LspMaze& m, double ax, double ay, double bx, double by, int& cnt) {      // _edge_fp, size 2
+    if (!lsp_valid2(ax, ay) || !lsp_valid2(bx, by)) return false;
+    if (!lsp_point(m, ax, ay, cnt) || !lsp_point(m, bx, by, cnt)) return false;
+    return lsp_segment(m, ax, ay, bx, by, cnt);
+}
+// stick robot: theta = z / LIMITS[2] * pi, ends = centre -+ (STICK_LENGTH / 2.) * (cos, sin)
+__device__ __forceinline__ bool lsp_valid3(double x, double y, double z) { return lsp_valid2(x, y) && z >= -0.4 && z <= 0.4; }
+__device__ __forceinline__ void lsp_ends(double x, double y, double z, double& ax, double& ay, double& bx, double& by) {
+    const double theta = z / 0.4 * 3.141592653589793;
+    const double ox = 0.1 * cos(theta), oy = 0.1 * sin(theta);
+    ax = x - ox; ay = y - oy;
+    bx = x + ox; by = y + oy;
+}
+__device__ bool lsp_stick(const LspMaze& m, double x, double y, double z, int& cnt) {                    // _stick_in_free_space
+    if (!lsp_valid3(x, y, z)) return false;
+    double ax, ay, bx, by;
+    lsp_ends(x, y, z, ax, ay, bx, by);
+    if (!lsp_point(m, ax, ay, cnt) || !lsp_point(m, bx, by, cnt)) return false;
+    return lsp_segment(m, ax, ay, bx, by, cnt);
+}
+// _edge_fp(s, t), size 3, by all 64 lanes; s and t are the same in every lane, and so are the result and `checks`.  The two
+// end configurations are checked by every lane alike; the interior configurations k = 1 .. K - 1 go to the lanes, 64 a pass.
+// Every lane counts its own checks and stops at its own first blocked query; the first failing k decides the edge, and the
+// count is what the sequential loop spends: all of the k below it plus the failing k's own.  No pass follows a failing one.
+__device__ bool lsp_stick_edge_wave(const LspMaze& m, int lane, const double* s, const double* t, long long& checks) {
+    if (!lsp_valid3(s[0], s[1], s[2]) || !lsp_valid3(t[0], t[1], t[2])) return false;
+    int c_ends = 0;
+    const bool ends_ok = lsp_stick(m, s[0], s[1], s[2], c_ends) && lsp_stick(m, t[0], t[1], t[2], c_ends);
+    checks += c_ends;
+    if (!ends_ok) return false;
+    const double d0 = t[0] - s[0], d1 = t[1] - s[1];
+    double d2 = t[2] - s[2];
+    if (fabs(d2) > 0.4) d2 = d2 > 0.0 ? d2 - 0.8 : d2 + 0.8;
+    // distance(): |t - s|, third coordinate min(|d|, ||d| - 0.8|), sqrt of the left-to-right sum of squares
+    const double a0 = fabs(t[0] - s[0]), a1 = fabs(t[1] - s[1]);
+    double a2 = fabs(t[2] - s[2]);
+    const double w2 = fabs(a2 - 0.8);
+    a2 = w2 < a2 ? w2 : a2;
+    const double d = sqrt((a0 * a0 + a1 * a1) + a2 * a2);
+    const int K = (int)(d / 0.015);
+    for (int base = 1; base < K; base += 64) {
+        const int k = base + lane;
+        int cnt = 0;
+        bool good = true;
+        if (k < K) {
+            const double r = (double)k / (double)K;              // k * 1. / K
+            double ax, ay, bx, by;
+            lsp_ends(s[0] + r * d0, s[1] + r * d1, s[2] + r * d2, ax, ay, bx, by);
+            good = lsp_edge2(m, ax, ay, bx, by, cnt);
+        }
+        const unsigned long long bad = __builtin_amdgcn_ballot_w64(!good);
+        const int first = bad ? __builtin_ctzll(bad) : 63;
+        checks += lsp_wave_sum(lane <= first ? cnt : 0);
+        if (bad) return false;
+    }
+    return true;
+}
+
+// np.linalg.norm(t - s) = sqrt(dot(d, d)); numpy's BLAS dot accumulates left to right with fused multiply-adds
+template <int DIM>
+__device__ __forceinline__ double lsp_cost(const double* s, const double* t) {
+    const double d0 = t[0] - s[0], d1 = t[1] - s[1];
+    double acc = d0 * d0;
+    acc = __builtin_fma(d1, d1, acc);
+    if (DIM == 3) { const double d2 = t[2] - s[2]; acc = __builtin_fma(d2, d2, acc); }
+    return sqrt(acc);
+}
+
+// first slot q in [lo, hi) with key[q] >= x (key sorted ascending), hi when none
+__device__ __forceinline__ int lsp_lower_bound(const long long* key, int lo, int hi, long long x) {
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (key[mid] < x) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+// slot of edge (a -> b) in a's out-block, -1 when the graph has no such edge
+__device__ __forceinline__ int lsp_slot(const long long* dst, const int* rb, int a, int b) {
+    const int q = lsp_lower_bound(dst, rb[a], rb[a + 1], (long long)b);
+    return q < rb[a + 1] && dst[q] == b ? q : -1;
+}
+
+}  // namespace
+
+// ---------------------------------------------------------------------------------------------------------------------
+// informed_sample: one wave per problem classifies its own draws [att_ptr[b], att_ptr[b + 1]) 64 at a time.  Pass 1 finds the
+// n-th free draw and the checks of the draws up to it (a block that ends first leaves everything untouched: status 1);
+// pass 2 classifies the consumed draws again and stores the free ones behind the pool's rows in draw order.
+// ---------------------------------------------------------------------------------------------------------------------
+template <int DIM>
+__global__ __launch_bounds__(64) void lsp_sample_kernel(LspSampleParams p) {
+    __shared__ unsigned char occ[kLspLdsCells];
+    const int b = blockIdx.x, lane = threadIdx.x;
+    if (p.active && !p.active[b]) return;
+    const long long a0 = p.att_ptr[b], Mb = p.att_ptr[b + 1] - a0;
+    const int N0 = p.n_nodes[b];
+    const int base = N0 == 0 ? 2 : N0;                           // round 1: goal and start come first
+    if (N0 < 0 || N0 == 1 || (long long)base + p.n > (long long)p.cap + 2 || a0 < 0 || a0 + (Mb > 0 ? Mb : 0) > p.M) {
+        if (lane == 0) { p.status[b] = 2; p.used[b] = 0; p.checks_out[b] = 0; }
+        return;
+    }
+    const LspMaze m = lsp_maze(p.maps + (size_t)b * p.w * p.w, p.w, occ, lane);
+    const double* att = p.attempts + (size_t)a0 * DIM;
+    auto classify = [&](long long idx, int& cnt) {
+        if (DIM == 2) return lsp_point(m, att[2 * idx], att[2 * idx + 1], cnt);
+        return lsp_stick(m, att[3 * idx], att[3 * idx + 1], att[3 * idx + 2], cnt);
+    };
+    int free_before = 0;
+    long long checks = 0, used = -1;
+    for (long long off = 0; off < Mb; off += 64) {
+        const long long idx = off + lane;
+        int cnt = 0;
+        const bool isfree = idx < Mb ? classify(idx, cnt) : false;
+        unsigned long long bal = __builtin_amdgcn_ballot_w64(isfree);
+        const int F = __builtin_popcountll(bal);
+        if (free_before + F >= p.n) {                            // the n-th free draw of this call is in this step
+            for (int skip = p.n - free_before - 1; skip > 0; --skip) bal &= bal - 1;
+            const int t = __builtin_ctzll(bal);
+            checks += lsp_wave_sum(lane <= t ? cnt : 0);
+            used = off + t + 1;
+            break;
+        }
+        free_before += F;
+        checks += lsp_wave_sum(cnt);
+    }
+    if (used < 0) {                                              // the block ended first: nothing is touched
+        if (lane == 0) { p.status[b] = 1; p.used[b] = 0; p.checks_out[b] = 0; }
+        return;
+    }
+    double* pool = p.pool + (size_t)b * (p.cap + 2) * DIM;
+    int fb = 0;
+    for (long long off = 0; off < used; off += 64) {
+        const long long idx = off + lane;
+        int cnt = 0;
+        const bool isfree = idx < used ? classify(idx, cnt) : false;
+        const unsigned long long bal = __builtin_amdgcn_ballot_w64(isfree);
+        if (isfree) {
+            const int incl = __builtin_popcountll(bal & (~0ull >> (63 - lane)));
+            double* row = pool + (size_t)(base + fb + incl - 1) * DIM;
+#pragma unroll
+            for (int c = 0; c < DIM; ++c) row[c] = att[DIM * idx + c];
+        }
+        fb += __builtin_popcountll(bal);
+    }
+    if (lane == 0) {
+        if (N0 == 0) {
+            const double* is = p.init_states + DIM * (size_t)b;
+            const double* gs = p.goal_states + DIM * (size_t)b;
+#pragma unroll
+            for (int c = 0; c < DIM; ++c) { pool[c] = gs[c]; pool[DIM + c] = is[c]; }
+        }
+        p.n_nodes[b] = base + p.n;
+        p.checks[b] += checks;
+        p.used[b] = (int)used;
+        p.checks_out[b] = checks;
+        p.status[b] = 0;
+    }
+}
+
+hipError_t launch_lsp_sample(const LspSampleParams& p, hipStream_t st) {
+    if (p.B <= 0) return hipSuccess;
+    if (p.dim == 3) hipLaunchKernelGGL(lsp_sample_kernel<3>, dim3(p.B), dim3(64), 0, st, p);
+    else hipLaunchKernelGGL(lsp_sample_kernel<2>, dim3(p.B), dim3(64), 0, st, p);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The node rows of a round: workgroup j serves slot slot_of[j]; its row offset is the sum of the node counts of the slots
+// before it in slot_of, added up here (the counts live on the device).  k1 comes from the caller's table by node count (the
+// host's ceil(k ln(q) / ln(100)), so no device logarithm decides an integer).
+// ---------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void lsp_gather_kernel(LspGatherParams p) {
+    const int j = blockIdx.x, lane = threadIdx.x;
+    auto count = [&](int i) {
+        const int s = p.slot_of[i];
+        if (s < 0 || s >= p.B) return 0;
+        const int n = p.n_nodes[s];
+        return n < 0 || n > p.cap + 2 ? 0 : n;
+    };
+    int before = 0;
+    for (int i = lane; i < j; i += 64) before += count(i);
+    before = lsp_wave_sum(before);
+    const int N = count(j);
+    if (lane == 0) {
+        p.node_ptr[j] = before;
+        if (j == p.A - 1) p.node_ptr[p.A] = before + N;
+        p.n_free_out[j] = N;
+        p.k1_out[j] = p.k1_table[N];
+    }
+    if (N == 0 || (long long)before + N > p.v_rows) return;
+    const double* pool = p.pool + (size_t)p.slot_of[j] * (p.cap + 2) * p.dim;
+    float* v = p.v + (size_t)before * p.dim;
+    for (int i = lane; i < N * p.dim; i += 64) v[i] = (float)pool[i];
+}
+
+hipError_t launch_lsp_gather(const LspGatherParams& p, hipStream_t st) {
+    if (p.A <= 0) return hipSuccess;
+    hipLaunchKernelGGL(lsp_gather_kernel, dim3(p.A), dim3(64), 0, st, p);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// One round of one problem per wave.
+//   Graph: the coalesced block of problem j (columns sorted by (source, target), symmetric): node a's out-edges are one
+//   contiguous block sorted by target.  dijkstra() relaxes, for the extracted u, every v with an edge (v -> u) at cost
+//   norm(p[u] - p[v]); the set is symmetric and the norm is too (the differences only change sign), so u's OUT-block serves.
+//   Per edge slot (workspace): its float64 cost and a flag, 0 = unknown, 1 = known valid, 2 = invalidated (dead: out of both
+//   neighbour lists).  Carried pairs are found in the new graph by binary search; one that is no longer an edge marks nothing.
+//   Per node (LDS up to kLspLdsNodes nodes, workspace beyond): dist, prev, out-block starts.  A visited node keeps its
+//   distance with the sign bit set: the scan skips it, and `alt < dist[v]` is false for it as it is in the reference (see
+//   below), so no separate flag is read.
+//   Dijkstra: each lane owns nodes lane, lane + 64, ...; an extraction is one scan of the owned nodes, a wave minimum of
+//   (distance bits, id) -- the reference's min_dist order: least distance, lowest id among equals -- and the relaxation of u's
+//   block, one lane per edge, strict `alt < dist[v]`.
+//   Early exit: the run stops when node 1 is extracted (or at the first infinite minimum: dist[1] is infinite then and the
+//   round ends).  Extraction keys never decrease -- costs are >= 0 and float64 addition is monotone, so every later alt is >=
+//   the key it was built from -- hence a node extracted earlier can never be improved (alt >= du >= dist[v], not strictly
+//   below), and neither dist[1] nor prev along node 1's chain, all extracted before it, can change in the rest of the run.
+//   Path edges: the reference checks them one by one and stops at the first blocked one.  Point robot: the path's edges go to
+//   the lanes 64 a pass; only the edges up to and including the first blocked one in path order are kept -- marked, appended
+//   to the pair list in path order, their checks counted -- later ones stay unknown and uncounted (per-edge counts are
+//   independent, so the total is exact).  Stick robot: one edge at a time, its interpolated sticks over the lanes.
+//   Bounds: a run kills one unordered edge or ends the round, so a round has at most E / 2 + 1 runs; a run extracts at most N
+//   nodes; a walk has at most N nodes.  Exceeding one sets status bit 1 and ends the problem.  Pair list full: status bit 0,
+//   nothing of that pass is written.  Ids outside the graph: status bit 2.
+// ---------------------------------------------------------------------------------------------------------------------
+constexpr int kLspLdsNodes = 1024;
+constexpr unsigned long long kLspInfBits = 0x7ff0000000000000ull;
+constexpr unsigned long long kLspSign = 0x8000000000000000ull;
+
+template <bool LDS, int DIM>
+__device__ __forceinline__ void lsp_round_body(const LspRoundParams& p, int slot, unsigned long long* s_dist, int* s_prev, int* s_rb,
+                                               unsigned char* occ) {
+    const int j = blockIdx.x, lane = threadIdx.x;
+    const int N = p.n_nodes[slot];
+    const int e0 = p.edge_ptr[j], E = p.edge_ptr[j + 1] - e0;
+    const size_t stride = (size_t)p.cap + 3;
+    unsigned long long* dist = LDS ? s_dist : p.ws_dist + (size_t)j * stride;
+    int* prev = LDS ? s_prev : p.ws_prev + (size_t)j * stride;
+    int* rb = LDS ? s_rb : p.ws_rb + (size_t)j * stride;
+    const long long* src = p.edge_index + e0;
+    const long long* dst = p.edge_index + p.total_edges + e0;
+    double* cost = p.ws_cost + e0;
+    unsigned char* flag = p.ws_flag + e0;
+    const double* pts = p.pool + (size_t)slot * (p.cap + 2) * DIM;
+    int* pairs = p.pairs + (size_t)slot * p.pair_cap * 2;
+    unsigned char* pstate = p.pair_state + (size_t)slot * p.pair_cap;
+    int* path = p.path + (size_t)slot * (p.cap + 2);
+    int n_pairs = p.n_pairs[slot];
+    int status = 0, solved = 0, path_len = 0, runs = 0;
+    long long checks = 0;
+
+    const LspMaze m = lsp_maze(p.maps + (size_t)slot * p.w * p.w, p.w, occ, lane);
+    // ---- out-block starts, costs, flags
+    for (int u = lane; u <= N; u += 64) rb[u] = lsp_lower_bound(src, 0, E, (long long)u);
+    bool ok = n_pairs >= 0 && n_pairs <= p.pair_cap;
+    for (int e = lane; e < E; e += 64) {
+        const long long s = src[e], t = dst[e];
+        if (s < 0 || s >= N || t < 0 || t >= N) { ok = false; continue; }
+        cost[e] = lsp_cost<DIM>(pts + s * DIM, pts + t * DIM);
+        flag[e] = 0;
+    }
+    if (!__all(ok)) {
+        if (lane == 0) p.status[slot] |= 4;
+        return;
+    }
+    lsp_sync();
+    // ---- carried pairs: both directions of an invalid pair are dead, of a valid pair known
+    for (int i = lane; i < n_pairs; i += 64) {
+        const int a = pairs[2 * i], c = pairs[2 * i + 1];
+        if (a < 0 || a >= N || c < 0 || c >= N) continue;
+        const int q = lsp_slot(dst, rb, a, c), r = lsp_slot(dst, rb, c, a);
+        if (q >= 0 && r >= 0) flag[q] = flag[r] = pstate[i];
+    }
+    lsp_sync();
+    const int max_runs = (E >> 1) + 1;
+    while (true) {
+        if (runs >= max_runs) { status |= 2; break; }
+        // ---- one Dijkstra run from node 0
+        for (int i = lane; i < N; i += 64) { dist[i] = kLspInfBits; prev[i] = -1; }
+        lsp_sync();
+        if (lane == 0) { dist[0] = 0ull; prev[0] = 0; }
+        lsp_sync();
+        ++runs;
+        bool reached = false;
+        int it = 0;
+        for (; it < N; ++it) {
+            unsigned long long best = ~0ull;
+            int bi = 0x7fffffff;
+            for (int i = lane; i < N; i += 64) {
+                const unsigned long long k = dist[i];            // dist >= 0: bit order = value order; visited: sign bit
+                if (k < best) { best = k; bi = i; }              // ascending ids: the first strict minimum
+            }
+            const unsigned long long w = lsp_wave_min_u64(best);
+            if (w >= kLspInfBits) break;                         // +inf, or everything visited
+            const int u = (int)lsp_wave_min_u64(best == w ? (unsigned long long)(unsigned)bi : ~0ull);
+            if (u == 1) { reached = true; break; }
+            const double du = __longlong_as_double((long long)w);
+            for (int q = rb[u] + lane; q < rb[u + 1]; q += 64) {
+                if (flag[q] == 2) continue;
+                const int v = (int)dst[q];
+                const double alt = du + cost[q];
+                const unsigned long long dv = dist[v];
+                if (!(dv & kLspSign) && alt < __longlong_as_double((long long)dv)) {
+                    dist[v] = (unsigned long long)__double_as_longlong(alt);
+                    prev[v] = u;
+                }
+            }
+            if (lane == 0) dist[u] = w | kLspSign;
+            lsp_sync();
+        }
+        if (!reached) {
+            if (it >= N) status |= 2;                            // N extractions without meeting node 1 or infinity
+            break;                                               // dist[1] is infinite: the round ends
+        }
+        // ---- the path from node 1 along prev (every lane walks it; lane 0 writes)
+        int L = 0, cur = 1;
+        bool walk_ok = true;
+        if (lane == 0) path[0] = 1;
+        while (cur != 0) {
+            cur = prev[cur];
+            if (cur < 0 || cur >= N || L + 1 >= N) { walk_ok = false; break; }
+            ++L;
+            if (lane == 0) path[L] = cur;
+        }
+        if (!walk_ok) { status |= 2; break; }
+        lsp_sync();
+        // ---- its unknown edges
+        bool feasible = true, full = false;
+        if (DIM == 2) {
+            for (int base = 0; base < L && feasible; base += 64) {
+                const int i = base + lane;
+                bool unknown = false, blocked = false;
+                int cnt = 0, n1 = 0, n2 = 0, q = -1;
+                if (i < L) {
+                    n1 = path[i]; n2 = path[i + 1];
+                    q = lsp_slot(dst, rb, n1, n2);
+                    if (q >= 0 && flag[q] == 0) {
+                        unknown = true;
+                        const double* a = pts + (size_t)n1 * 2;
+                        const double* c = pts + (size_t)n2 * 2;
+                        blocked = !lsp_edge2(m, a[0], a[1], c[0], c[1], cnt);
+                    }
+                }
+                const unsigned long long bad = __builtin_amdgcn_ballot_w64(blocked);
+                const int first = bad ? __builtin_ctzll(bad) : 63;
+                const bool keep = unknown && lane <= first;
+                const unsigned long long kb = __builtin_amdgcn_ballot_w64(keep);
+                const int n_new = __builtin_popcountll(kb);
+                if (n_pairs + n_new > p.pair_cap) { full = true; break; }
+                if (keep) {
+                    const int pos = n_pairs + __builtin_popcountll(kb & ((1ull << lane) - 1ull));
+                    const unsigned char st = blocked ? 2 : 1;
+                    pairs[2 * pos] = n1; pairs[2 * pos + 1] = n2; pstate[pos] = st;
+                    flag[q] = st;
+                    const int r = lsp_slot(dst, rb, n2, n1);
+                    if (r >= 0) flag[r] = st;
+                }
+                checks += lsp_wave_sum(keep ? cnt : 0);
+                n_pairs += n_new;
+                lsp_sync();
+                if (bad) feasible = false;
+            }
+        } else {
+            for (int i = 0; i < L; ++i) {
+                const int n1 = path[i], n2 = path[i + 1];
+                const int q = lsp_slot(dst, rb, n1, n2);
+                if (q < 0 || flag[q] != 0) continue;             // known valid (a dead edge is never on a path)
+                if (n_pairs + 1 > p.pair_cap) { full = true; break; }
+                const bool fr = lsp_stick_edge_wave(m, lane, pts + (size_t)n1 * 3, pts + (size_t)n2 * 3, checks);
+                const unsigned char st = fr ? 1 : 2;
+                if (lane == 0) {
+                    pairs[2 * n_pairs] = n1; pairs[2 * n_pairs + 1] = n2; pstate[n_pairs] = st;
+                    flag[q] = st;
+                    const int r = lsp_slot(dst, rb, n2, n1);
+                    if (r >= 0) flag[r] = st;
+                }
+                ++n_pairs;
+                lsp_sync();
+                if (!fr) { feasible = false; break; }
+            }
+        }
+        if (full) { status |= 1; break; }
+        if (feasible) { solved = 1; path_len = L + 1; break; }
+    }
+    if (lane == 0) {
+        p.n_pairs[slot] = n_pairs;
+        p.checks[slot] += checks;
+        p.dijkstra_runs[slot] += runs;
+        p.status[slot] |= status;
+        p.solved[slot] = solved;
+        p.path_len[slot] = path_len;
+    }
+}
+
+template <int DIM>
+__global__ __launch_bounds__(64) void lsp_round_kernel(LspRoundParams p) {
+    __shared__ unsigned long long s_dist[kLspLdsNodes];
+    __shared__ int s_prev[kLspLdsNodes];
+    __shared__ int s_rb[kLspLdsNodes + 1];
+    __shared__ unsigned char occ[kLspLdsCells];
+    const int slot = p.slot_of ? p.slot_of[blockIdx.x] : (int)blockIdx.x;
+    if (slot < 0 || slot >= p.B) return;
+    if (p.solved[slot] || p.status[slot]) return;                // finished problems are left as they are
+    const int N = p.n_nodes[slot];
+    const int E = p.edge_ptr[blockIdx.x + 1] - p.edge_ptr[blockIdx.x];
+    if (N < 2 || N > p.cap + 2 || E < 0 || p.edge_ptr[blockIdx.x] < 0 || (long long)p.edge_ptr[blockIdx.x + 1] > p.total_edges) {
+        if (threadIdx.x == 0) p.status[slot] |= 4;
+        return;
+    }
+    if (N <= kLspLdsNodes) lsp_round_body<true, DIM>(p, slot, s_dist, s_prev, s_rb, occ);
+    else lsp_round_body<false, DIM>(p, slot, s_dist, s_prev, s_rb, occ);
+}
+
+hipError_t launch_lsp_round(const LspRoundParams& p, hipStream_t st) {
+    if (p.A <= 0) return hipSuccess;
+    if (p.dim == 3) hipLaunchKernelGGL(lsp_round_kernel<3>, dim3(p.A), dim3(64), 0, st, p);
+    else hipLaunchKernelGGL(lsp_round_kernel<2>, dim3(p.A), dim3(64), 0, st, p);
+    return hipGetLastError();
+}
+
+int lsp_lds_nodes() { return kLspLdsNodes; }
+
+}  // namespace gnnmp

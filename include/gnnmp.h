@@ -652,6 +652,94 @@ int gnnmp_mt19937_uniform(const gnnmp_mt_uniform_batch* batch, uint32_t* state, 
                           int32_t* status_out, void* hip_stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The LazySP baseline on maze problems (algorithm/lazy_sp.py:147-196 over algorithm/dijkstra.py:34-76), batched, every
+ * problem on its own sample stream: problem b computes what np.random.seed(s_b); LazySP(env, batch_size, T, k).plan() of that
+ * problem alone computes (eval_bit.eval_lazysp's one global stream over consecutive problems is NOT reproduced).  The host
+ * loops over rounds only; round r of all unfinished problems is
+ *   gnnmp_lazysp_sample    informed_sample: `batch` more free draws into a float64 pool          lazy_sp.py:78-103, 154
+ *   gnnmp_lazysp_gather    the round's float32 node rows, node_ptr, n_free, k1                   lazy_sp.py:125-126, 159
+ *   gnnmp_graph_build      coalesce(knn_graph(float32 points, k1, loop=True) + flipped)         lazy_sp.py:126-128
+ *   gnnmp_lazysp_round     Dijkstra / walk / check / invalidate until the round ends            lazy_sp.py:162-193
+ * Node 0 is the GOAL and node 1 the START (lazy_sp.py:61).  The per-problem state lives in caller-allocated device arrays,
+ * one fixed-size slot per problem; a fresh store is all zeros.  `cap` >= the free draws a problem can ever hold.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct {
+    int32_t n_problems, cap, pair_cap;
+    double* pool;                /* [B, cap + 2, dim]  row 0 = goal state, row 1 = init state, then the free draws in draw order */
+    int32_t* n_nodes;            /* [B]  rows in use; 0 = nothing sampled yet                                              */
+    int32_t* pairs;              /* [B, pair_cap, 2]  every edge (n1, n2) the planner checked, in the order it checked them  */
+    uint8_t* pair_state;         /* [B, pair_cap]  1 = free (valid_edges), 2 = blocked (invalid_edges); the 2s in list order
+                                  * are the order in which edges were invalidated                                           */
+    int32_t* n_pairs;            /* [B]                                                                                    */
+    int64_t* checks;             /* [B]  collision checks so far, sampling included                                        */
+    int32_t* dijkstra_runs;      /* [B]  dijkstra() calls so far                                                           */
+    int32_t* path_len;           /* [B]  nodes of the solution path, 0 = none                                              */
+    int32_t* path;               /* [B, cap + 2]  node ids start -> goal (1 ... 0); scratch while a problem is unsolved     */
+    int32_t* solved;             /* [B]  1 = a fully valid path was found                                                  */
+    int32_t* status;             /* [B]  sticky bits: 1 = the pair list was full, 2 = a loop bound was hit, 4 = bad graph   */
+} gnnmp_lazysp_state;
+
+/* Pairs a problem's list can reach: every checked pair is an unordered non-loop edge of SOME round's graph and is checked at
+ * most once, and round r's graph (k1_r nearest + reversed on N_r = 2 + r * batch nodes) has at most min(k1_r * N_r,
+ * N_r (N_r - 1) / 2) of them; k1 = k1_by_round[r - 1] for r = 1 .. n_rounds (host array: the caller's ceil(k ln N / ln 100)).
+ * GNNMP_ERR_NULL / GNNMP_ERR_ARG (batch < 1, n_rounds < 1, a k1 < 1, or a sum beyond 2^30). */
+int gnnmp_lazysp_pair_cap(int32_t batch, int32_t n_rounds, const int32_t* k1_by_round, int64_t* pair_cap);
+
+/* Rejection sampling that APPENDS `batch->n_free` free draws to every active problem's float64 pool.  The batch struct and its
+ * att_ptr convention are gnnmp_maze_sample_streams' (problem b owns attempts [att_ptr[b], att_ptr[b + 1]), float64
+ * [n_attempts, dim], host-drawn or filled by gnnmp_mt19937_uniform; active; att_ptr_host checked when given; batch->cap is not
+ * read, the store's is).  A draw is free iff _state_fp holds for the float64 draw: dim 2 one point query (one check), dim 3
+ * the stick with gnnmp_stick_sample's classification and 0 .. 9 checks; rejected draws are dropped.  n_nodes[b] == 0 on entry:
+ * goal / init state go to rows 0 / 1 first.  state->checks[b] is INCREMENTED by the checks of the draws consumed (those up to
+ * and including the n_free-th free one).  used_out / checks_out / status_out [B] as gnnmp_maze_sample_streams: status 0 =
+ * done; 1 = the block ended before the n_free-th free draw, pool and counts untouched, used / checks 0: hand that problem a
+ * longer block; 2 = no room in the pool (n_nodes + n_free > cap + 2) or the block lies outside attempts: untouched.  One wave
+ * per problem, one launch on hip_stream; no allocation, no synchronisation, no atomics, deterministic.
+ * GNNMP_ERR_DIMS (dim not 2 / 3), GNNMP_ERR_NULL, GNNMP_ERR_ARG (n_problems / width / n_free < 1, n_problems differing from
+ * the store's, cap < n_free, n_attempts < 0, a bad att_ptr_host); nothing is launched then. */
+int gnnmp_lazysp_sample(const gnnmp_maze_streams_batch* batch, int32_t dim, const gnnmp_lazysp_state* state, int32_t* used_out,
+                        int64_t* checks_out, int32_t* status_out, void* hip_stream);
+
+/* The node rows of a round for the n_active problems slot_of[0 .. n_active) (device, distinct slots): v_out = float32 of the
+ * pool rows, compact, in slot_of order; node_ptr_out [A + 1]; n_free_out [A] = the node counts (every LazySP node is free, so
+ * gnnmp_graph_build's second kNN pass repeats the first); k1_out [A] = k1_table[node count], k1_table [cap + 3] (device) being
+ * the caller's ceil(k ln N / ln 100) by node count -- the layout gnnmp_graph_build reads.  The offsets are summed on the
+ * device; nothing is read back.  A problem that would not fit v_rows is left out of v_out (its node_ptr entry is still
+ * written); a slot outside the store counts as empty.  One launch.  GNNMP_ERR_DIMS / GNNMP_ERR_NULL / GNNMP_ERR_ARG
+ * (n_active outside [1, n_problems], v_rows < 0, cap < 1). */
+int gnnmp_lazysp_gather(const gnnmp_lazysp_state* state, int32_t dim, int32_t n_active, const int32_t* slot_of,
+                        const int32_t* k1_table, int64_t v_rows, float* v_out, int32_t* node_ptr_out, int32_t* n_free_out,
+                        int32_t* k1_out, void* hip_stream);
+
+/* Workspace of gnnmp_lazysp_round (256-byte aligned): per edge a float64 cost and a flag, per problem the node state used
+ * beyond the LDS node count.  GNNMP_ERR_NULL / GNNMP_ERR_ARG (n_active < 1, cap < 1, total_edges < 0). */
+int gnnmp_lazysp_workspace_bytes(int32_t n_active, int32_t cap, int64_t total_edges, size_t* bytes);
+/* Problems up to this many nodes keep dist / prev / block starts in LDS; larger ones use the workspace. */
+int gnnmp_lazysp_lds_nodes(void);
+
+/* One round of LazySP for the n_active problems slot_of[j] (NULL = j), each independent, one wave per problem, one launch.
+ * edge_index [2, total_edges] (row stride total_edges) / edge_ptr [A + 1]: the round's coalesced graphs as gnnmp_graph_build
+ * wrote them (columns of problem j sorted by (source, target), symmetric, graph-local ids); maps [B, width, width] BY SLOT.
+ *   - carried pairs are looked up in the new graph: both directions of an invalid pair are dead (out of both neighbour
+ *     lists), those of a valid pair need no check; a pair that is no longer an edge marks nothing and stays in the list;
+ *   - edge cost = np.linalg.norm(points[t] - points[s]) on the float64 pool rows (numpy's fused dot for dim 2 / 3);
+ *   - repeat: dijkstra from node 0 (least distance, lowest id among equals, strict improvement; stopped when node 1 is
+ *     extracted, which cannot change dist[1] or its prev chain); dist[1] infinite ends the round; else the path is walked from
+ *     node 1 along prev and its unknown edges are checked with _edge_fp on the float64 states -- in parallel, keeping only
+ *     those up to and including the first blocked one in path order, so pairs, flags and the check count are the sequential
+ *     loop's; a blocked edge is invalidated and dijkstra runs again; a fully valid path sets solved, path_len, path.
+ * Updated in the store: pairs / pair_state / n_pairs (appended), checks and dijkstra_runs (incremented), path, path_len,
+ * solved, status.  A slot with solved or status already set is skipped.  status bit 1: the pair list was full (the pairs of
+ * that pass are not written: nothing is ever written outside the slot); bit 2: more dijkstra runs than E / 2 + 1, more
+ * extractions than nodes, or a walk longer than the node count; bit 4: node count outside [2, cap + 2], an edge block outside
+ * edge_index or a node id outside the graph.  Any bit ends the problem.
+ * GNNMP_ERR_DIMS / GNNMP_ERR_NULL / GNNMP_ERR_ARG (n_active outside [1, n_problems], width < 1, total_edges < 0) /
+ * GNNMP_ERR_WORKSPACE (workspace too small); nothing is launched then. */
+int gnnmp_lazysp_round(const gnnmp_lazysp_state* state, int32_t dim, int32_t n_active, const int32_t* slot_of,
+                       const int64_t* edge_index, int64_t total_edges, const int32_t* edge_ptr, const double* maps, int32_t width,
+                       void* workspace, size_t workspace_bytes, void* hip_stream);
+
+/* ------------------------------------------------------------------------------------------
  * Supervision of the explorer's training step (train_explorer.py:124-176): edge labels, shortest paths to the goal,
  * the greedy roll-out of the detached policy and the frontier / label of the loss, for a batch of problems.
  *   gnnmp_episode_label_maze      construct_graph's collision checks and costs     algorithm/dijkstra.py:15-31
