@@ -6,7 +6,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('GNNMP_LIB') or os.path.join(_HERE, 'libgnnmp.so')      # GNNMP_LIB: an experiment build (tools/diag/build_variant.sh)
 
-ABI_VERSION = 5                        # include/gnnmp.h gnnmp_abi_version(): what this binding was written against
+ABI_VERSION = 6                        # include/gnnmp.h gnnmp_abi_version(): what this binding was written against
 
 c_float_p = ctypes.POINTER(ctypes.c_float)
 c_int32_p = ctypes.POINTER(ctypes.c_int32)
@@ -87,6 +87,20 @@ class LazySPState(ctypes.Structure):
                 ('pool', ctypes.c_void_p), ('n_nodes', ctypes.c_void_p), ('pairs', ctypes.c_void_p), ('pair_state', ctypes.c_void_p),
                 ('n_pairs', ctypes.c_void_p), ('checks', ctypes.c_void_p), ('dijkstra_runs', ctypes.c_void_p),
                 ('path_len', ctypes.c_void_p), ('path', ctypes.c_void_p), ('solved', ctypes.c_void_p), ('status', ctypes.c_void_p)]
+
+
+class RRTStarBatch(ctypes.Structure):
+    _fields_ = [('n_problems', ctypes.c_int32), ('dim', ctypes.c_int32), ('width', ctypes.c_int32), ('t_max', ctypes.c_int32),
+                ('stop_when_success', ctypes.c_int32), ('draws_per_problem', ctypes.c_int64), ('maps', ctypes.c_void_p),
+                ('init_states', ctypes.c_void_p), ('goal_states', ctypes.c_void_p), ('draws', ctypes.c_void_p)]
+
+
+class RRTStarTree(ctypes.Structure):
+    _fields_ = [('states', ctypes.c_void_p), ('parents', ctypes.c_void_p), ('rewired_parents', ctypes.c_void_p),
+                ('flags', ctypes.c_void_p), ('costs', ctypes.c_void_p), ('path_lengths', ctypes.c_void_p),
+                ('cumulated_checks', ctypes.c_void_p), ('path', ctypes.c_void_p), ('n_nodes', ctypes.c_void_p),
+                ('success', ctypes.c_void_p), ('last_iter', ctypes.c_void_p), ('used', ctypes.c_void_p), ('path_len', ctypes.c_void_p),
+                ('status', ctypes.c_void_p)]
 
 
 class MtUniformBatch(ctypes.Structure):
@@ -222,6 +236,9 @@ def lib():
     L.gnnmp_lazysp_lds_nodes.argtypes = []
     L.gnnmp_lazysp_round.argtypes = [ctypes.POINTER(LazySPState), ctypes.c_int32, ctypes.c_int32, vp, vp, ctypes.c_int64, vp, vp,
                                      ctypes.c_int32, vp, sz, vp]
+    L.gnnmp_rrtstar_workspace_bytes.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(sz)]
+    L.gnnmp_rrtstar_lds_nodes.argtypes = []
+    L.gnnmp_rrtstar_plan.argtypes = [ctypes.POINTER(RRTStarBatch), ctypes.POINTER(RRTStarTree), vp, sz, vp]
     L.gnnmp_maze_steer.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, vp, vp, vp, vp, vp, vp, vp, vp]
     L.gnnmp_stick_steer.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.gnnmp_episode_label_maze.argtypes = [ctypes.POINTER(EpisodeGraphs), ctypes.c_int32, ctypes.c_int32, vp, vp, vp, vp, vp]

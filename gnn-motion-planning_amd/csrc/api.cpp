@@ -248,7 +248,7 @@ extern "C" const char* gnnmp_status_string(int s) {
 }
 extern "C" const char* gnnmp_last_hip_error(void) { return g_hip_error.c_str(); }
 // 2: stage list of gnnmp_explorer_profile_read (fused message passing); 3: device-side status words (gnnmp_*_status*)
-extern "C" int gnnmp_abi_version(void) { return 5; }
+extern "C" int gnnmp_abi_version(void) { return 6; }
 
 // ---------------------------------------------------------------------------------------------
 // explorer handle
@@ -1787,6 +1787,66 @@ extern "C" int gnnmp_lazysp_round(const gnnmp_lazysp_state* s, int32_t dim, int3
     p.ws_dist = reinterpret_cast<unsigned long long*>(ws + c.dist); p.ws_prev = reinterpret_cast<int*>(ws + c.prev);
     p.ws_rb = reinterpret_cast<int*>(ws + c.rb);
     HIP_TRY(launch_lsp_round(p, static_cast<hipStream_t>(hip_stream)));
+    return GNNMP_OK;
+}
+
+// =============================================================================================
+// the RRT* baseline on maze problems (rrtstar_kernels.hip; algorithm/tsa.py:12-139, 222-281)
+// =============================================================================================
+namespace {
+struct RrtCarve { size_t x, y, z, c, f, total; };
+RrtCarve rrt_carve(int n_problems, int t_max) {
+    RrtCarve c{0, 0, 0, 0, 0, 0};
+    if ((long long)t_max + 1 <= rrtstar_lds_nodes()) return c;   // the node state fits LDS: no workspace
+    const size_t nodes = (size_t)n_problems * ((size_t)t_max + 1);
+    size_t off = 0;
+    c.x = off; off = lsp_align(off + sizeof(double) * nodes);
+    c.y = off; off = lsp_align(off + sizeof(double) * nodes);
+    c.z = off; off = lsp_align(off + sizeof(double) * nodes);
+    c.c = off; off = lsp_align(off + sizeof(double) * nodes);
+    c.f = off; off = lsp_align(off + nodes);
+    c.total = off;
+    return c;
+}
+}  // namespace
+
+extern "C" int gnnmp_rrtstar_workspace_bytes(int32_t n_problems, int32_t t_max, size_t* bytes) {
+    if (!bytes) return GNNMP_ERR_NULL;
+    if (n_problems < 1 || t_max < 1 || t_max == INT32_MAX) return GNNMP_ERR_ARG;
+    *bytes = rrt_carve(n_problems, t_max).total;
+    return GNNMP_OK;
+}
+
+extern "C" int gnnmp_rrtstar_lds_nodes(void) { return rrtstar_lds_nodes(); }
+
+extern "C" int gnnmp_rrtstar_plan(const gnnmp_rrtstar_batch* b, const gnnmp_rrtstar_tree* t, void* workspace, size_t workspace_bytes,
+                                  void* hip_stream) {
+    if (!b || !t) return GNNMP_ERR_NULL;
+    if (b->dim != 2 && b->dim != 3) return GNNMP_ERR_DIMS;
+    if (!b->maps || !b->init_states || !b->goal_states || !b->draws) return GNNMP_ERR_NULL;
+    if (!t->states || !t->parents || !t->rewired_parents || !t->flags || !t->costs || !t->path_lengths || !t->cumulated_checks ||
+        !t->path || !t->n_nodes || !t->success || !t->last_iter || !t->used || !t->path_len || !t->status)
+        return GNNMP_ERR_NULL;
+    if (b->n_problems < 1 || b->width < 1 || b->t_max < 1 || b->t_max == INT32_MAX) return GNNMP_ERR_ARG;
+    if (b->draws_per_problem < 2 + b->dim || b->draws_per_problem > INT32_MAX) return GNNMP_ERR_ARG;      // one iteration at least
+    const RrtCarve c = rrt_carve(b->n_problems, b->t_max);
+    if (c.total) {
+        if (!workspace) return GNNMP_ERR_NULL;
+        if (workspace_bytes < c.total || (reinterpret_cast<uintptr_t>(workspace) & 255)) return GNNMP_ERR_WORKSPACE;
+    }
+    char* ws = static_cast<char*>(workspace);
+    RrtParams p;
+    p.B = b->n_problems; p.w = b->width; p.t_max = b->t_max; p.stop = b->stop_when_success ? 1 : 0; p.dim = b->dim;
+    p.draw_len = b->draws_per_problem;
+    p.maps = b->maps; p.init_states = b->init_states; p.goal_states = b->goal_states; p.draws = b->draws;
+    p.states = t->states; p.parents = t->parents; p.rewired = t->rewired_parents; p.flags = t->flags; p.costs = t->costs;
+    p.path_lengths = t->path_lengths; p.cum_checks = reinterpret_cast<long long*>(t->cumulated_checks); p.path = t->path;
+    p.n_nodes = t->n_nodes; p.success = t->success; p.last_iter = t->last_iter; p.used = t->used; p.path_len = t->path_len;
+    p.status = t->status;
+    p.ws_x = reinterpret_cast<double*>(ws + c.x); p.ws_y = reinterpret_cast<double*>(ws + c.y);
+    p.ws_z = reinterpret_cast<double*>(ws + c.z); p.ws_c = reinterpret_cast<double*>(ws + c.c);
+    p.ws_f = reinterpret_cast<unsigned char*>(ws + c.f);
+    HIP_TRY(launch_rrtstar_plan(p, static_cast<hipStream_t>(hip_stream)));
     return GNNMP_OK;
 }
 

@@ -316,6 +316,25 @@ struct LspRoundParams {
 hipError_t launch_lsp_round(const LspRoundParams& p, hipStream_t st);
 int lsp_lds_nodes();
 
+// ---- the RRT* baseline on maze problems (rrtstar_kernels.hip, algorithm/tsa.py:12-139, 222-281)
+struct RrtParams {
+    int B, w, t_max, stop, dim;           // problems, map width, iterations, stop_when_success, 2 / 3
+    long long draw_len;                   // raw doubles per problem
+    const double *maps, *init_states, *goal_states;      // [B, w, w], [B, dim], [B, dim]
+    const double* draws;                  // [B, draw_len] doubles of [0, 1)
+    double* states;                       // out [B, t_max + 1, dim]
+    int *parents, *rewired;               // out [B, t_max + 1], -1 for the root
+    unsigned char* flags;                 // out [B, t_max + 1]: bit 0 freesp, bit 1 in_goal_region
+    double *costs, *path_lengths;         // out [B, t_max + 1]
+    long long* cum_checks;                // out [B, t_max + 1]
+    int* path;                            // out [B, t_max + 1]
+    int *n_nodes, *success, *last_iter, *used, *path_len, *status;      // out [B]
+    double *ws_x, *ws_y, *ws_z, *ws_c;    // workspace [B, t_max + 1] each (trees beyond the LDS node count)
+    unsigned char* ws_f;
+};
+hipError_t launch_rrtstar_plan(const RrtParams& p, hipStream_t st);
+int rrtstar_lds_nodes();
+
 // ---- supervision of the explorer's training step (train_episode_kernels.hip, train_explorer.py:124-176)
 struct EpLabelParams {                    // (a) edge_free / edge_cost of construct_graph for maze problems
     int B, dim, w;

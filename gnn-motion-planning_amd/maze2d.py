@@ -182,6 +182,14 @@ class Maze2D:
     def in_goal_region(self, state):
         return bool(self.distance(state, self.goal_state) < RRT_EPS and self._state_fp(state))
 
+    def step(self, state, new_state):
+        """``env.step(state, new_state=new_state)`` (maze_env.py:181-208): x and y clipped to the bounds IN PLACE, then the edge
+        query, and only for a free edge the goal test (one more counted ``_state_fp`` when within RRT_EPS of the goal).
+        Returns (new_state, no_collision, done)."""
+        new_state[:2] = new_state[:2].clip(-LIMITS, LIMITS)
+        no_collision = self._edge_fp(state, new_state)
+        return new_state, no_collision, bool(no_collision and self.in_goal_region(new_state))
+
     # ------------------------------------------------------------------ collision checks
     def _cell(self, state):
         w = self.width
@@ -343,6 +351,10 @@ class Maze3D(Maze2D):
     def interpolate(self, a, b, ratio):
         """Point at `ratio` of the way from a to b along the short orientation arc (maze_env.py:151-170)."""
         return self._wrap_orientation(a + self._wrap_orientation(b - a) * ratio)
+
+    def step(self, state, new_state):
+        """:meth:`Maze2D.step` with the orientation brought back into its period as well (maze_env.py:189-196), in place."""
+        return super().step(state, self._wrap_orientation(new_state))
 
     @staticmethod
     def _ends(coord):

@@ -740,6 +740,77 @@ int gnnmp_lazysp_round(const gnnmp_lazysp_state* state, int32_t dim, int32_t n_a
                        void* workspace, size_t workspace_bytes, void* hip_stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The RRT* baseline on maze problems -- eval_rrt.py's NEXT_plan(env, model=None, T=t_max, g_explore_eps=1., stop_when_success)
+ * (algorithm/tsa.py:12-139, 222-281 over algorithm/search_tree.py:5-98 and environment/maze_env.py:127-208, 266-347): a
+ * goal-biased RRT with RRT*-style rewiring of the newest node -- batched, every problem on its own sample stream: problem b
+ * computes what np.random.seed(s_b); env.init_new_problem(i_b); NEXT_plan(...) of that problem alone computes (eval_rrt's one
+ * global stream over consecutive problems is NOT reproduced).  The whole t_max loop of all problems is ONE launch, one wave
+ * per problem; per iteration: the sample (1 or 2 + dim raw doubles), the nearest non-terminal node (lowest index among
+ * equals), RRT_steer, env.step with every collision check counted (the goal test of a free edge included), the insertion --
+ * EVERY new state joins the tree, collided ones too -- and RRTS_rewire_last's two passes.  All decisions are float64, one
+ * rounded operation at a time.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct {
+    int32_t n_problems, dim, width;      /* dim 2 = point robot, 3 = stick robot; maps are width x width              */
+    int32_t t_max, stop_when_success;    /* NEXT_plan's T; non-zero: the loop ends with the first node in the goal region */
+    int64_t draws_per_problem;           /* doubles in a problem's block; t_max * (2 + dim) always suffices             */
+    const double* maps;                  /* [B, width, width]  0 = free                                                 */
+    const double* init_states;           /* [B, dim]                                                                    */
+    const double* goal_states;           /* [B, dim]                                                                    */
+    const double* draws;                 /* [B, draws_per_problem]  the RAW doubles of [0, 1) of the problem's generator
+                                          * (RandomState.random_sample; gnnmp_mt19937_uniform with dim 1, low 0, range 1), in
+                                          * draw order: an iteration takes one (rand() < 0.05: the sample is the goal state)
+                                          * or 2 + dim (a second rand() that is dropped, then low + (high - low) * d per
+                                          * coordinate, the transform applied here)                                     */
+} gnnmp_rrtstar_batch;
+
+typedef struct {                         /* all out; rows of a problem behind its n_nodes are left as they were         */
+    double* states;                      /* [B, t_max + 1, dim]  row 0 = init state, row i + 1 = the new state of iteration i */
+    int32_t* parents;                    /* [B, t_max + 1]  the node a state was grown from; -1 for the root             */
+    int32_t* rewired_parents;            /* [B, t_max + 1]  after rewiring                                               */
+    uint8_t* flags;                      /* [B, t_max + 1]  bit 0 = freesp, bit 1 = in_goal_region                        */
+    double* costs;                       /* [B, t_max + 1]  2 for collided nodes                                         */
+    double* path_lengths;                /* [B, t_max + 1]  -1 until a node reaches the goal region                       */
+    int64_t* cumulated_checks;           /* [B, t_max + 1]  collision checks after every iteration; 0 for the root        */
+    int32_t* path;                       /* [B, t_max + 1]  search_tree.path(): node ids root -> last node along
+                                          * rewired_parents; path_len entries, 0 unless the last node is in the goal region */
+    int32_t* n_nodes;                    /* [B]  iterations run + 1                                                      */
+    int32_t* success;                    /* [B]  1 = some first step of an iteration ended in the goal region            */
+    int32_t* last_iter;                  /* [B]  NEXT_plan's returned i: index of the last iteration run                  */
+    int32_t* used;                       /* [B]  doubles consumed from the block                                         */
+    int32_t* path_len;                   /* [B]                                                                          */
+    int32_t* status;                     /* [B]  0, or bits: 1 = the draw block ended before an iteration had its doubles
+                                          * (the tree holds the iterations before it; nothing is read beyond the block),
+                                          * 2 = rewired_parents hold a cycle (the reference would not return): no path     */
+} gnnmp_rrtstar_tree;
+
+/* Workspace of gnnmp_rrtstar_plan (256-byte aligned): node coordinates, cost and flags (8 dim + 9 bytes a node, sized for
+ * dim 3) of every problem when t_max + 1 exceeds gnnmp_rrtstar_lds_nodes(), else 0 bytes (the node state lives in LDS and
+ * workspace may be NULL).  GNNMP_ERR_NULL / GNNMP_ERR_ARG (n_problems < 1, t_max < 1). */
+int gnnmp_rrtstar_workspace_bytes(int32_t n_problems, int32_t t_max, size_t* bytes);
+/* Trees of up to this many nodes (t_max + 1) keep their node state in LDS; longer runs use the workspace. */
+int gnnmp_rrtstar_lds_nodes(void);
+
+/* RRT* for batch->n_problems maze problems, one launch on hip_stream: no allocation, no synchronisation, no atomics,
+ * deterministic.  Semantics as restated above and in gnnmp.rrtstar.plan_host; in particular
+ *   - distance = sqrt((dx^2 + dy^2) + dz^2), dz = min(|dz|, ||dz| - 0.8|) for the stick;
+ *   - env.step(a, new): x, y clipped to +-1, z wrapped, _edge_fp(a, new) -- both _valid_state, both counted _state_fp in that
+ *     order, then the bisection (point) or the K = int(d / 0.015) interpolated sticks (stick) -- and ONLY for a free edge the
+ *     goal test, which counts one more _state_fp(new) when new is within RRT_EPS of the goal;
+ *   - rewiring, newest node free: near = distance < 3 RRT_EPS over ALL earlier nodes; pass 1 in index order over the free near
+ *     nodes, a candidate checked (env.step(node, new)) only if dist + cost beats the RUNNING minimum; pass 2 over all near
+ *     nodes, collided ones (cost 2) included: checked if min_cost + dist < cost, a free edge sets the node's cost and rewired
+ *     parent, descendants keep their costs;
+ *   - success comes from the first step of an iteration only; path_lengths[-1] changes only when the newest node is in the
+ *     goal region.
+ * All argument errors come back before anything is launched: GNNMP_ERR_NULL (a NULL struct or array; workspace when
+ * gnnmp_rrtstar_workspace_bytes is not 0), GNNMP_ERR_DIMS (dim not 2 / 3), GNNMP_ERR_ARG (n_problems / width / t_max < 1,
+ * draws_per_problem < 2 + dim -- shorter than one iteration -- or beyond 2^31 - 1), GNNMP_ERR_WORKSPACE (too small or
+ * misaligned). */
+int gnnmp_rrtstar_plan(const gnnmp_rrtstar_batch* batch, const gnnmp_rrtstar_tree* tree, void* workspace, size_t workspace_bytes,
+                       void* hip_stream);
+
+/* ------------------------------------------------------------------------------------------
  * Supervision of the explorer's training step (train_explorer.py:124-176): edge labels, shortest paths to the goal,
  * the greedy roll-out of the detached policy and the frontier / label of the loss, for a batch of problems.
  *   gnnmp_episode_label_maze      construct_graph's collision checks and costs     algorithm/dijkstra.py:15-31
