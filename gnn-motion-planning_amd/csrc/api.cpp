@@ -1321,11 +1321,17 @@ extern "C" int gnnmp_smoother_forward_ex(const gnnmp_smoother* h, const gnnmp_sm
         HIP_TRY(hipMemsetAsync(p.tile_cnt, 0, sizeof(int) * 4, st));  // the tile-list counters (then re-armed by the graph stage itself)
     else
         p.tile_cnt = nullptr;                                          // no lists: the graph stage skips the bookkeeping
+    int force_fallback = 0;
+    {   // GNNMP_SM_FORCE_FALLBACK=1|2|3: the d = 128 message kernels take their flag-timeout fallback on all / even / odd edge tiles
+        // or rounds without polling (the tests; read per call)
+        const char* env = getenv("GNNMP_SM_FORCE_FALLBACK");
+        if (env) force_fallback = atoi(env);
+    }
     for (int it = 0; it < loop; ++it) {
         p.init_from_path = it == 0 ? 1 : 0;
         p.out = it == loop - 1 ? out_path : nullptr;
         p.parity = it & 1;
-        HIP_TRY(launch_sm_iter(D, h->dims.mlp_dtype, p, st));
+        HIP_TRY(launch_sm_iter(D, h->dims.mlp_dtype, p, st, force_fallback));
     }
     return GNNMP_OK;
 }

@@ -688,8 +688,20 @@ __device__ long long g_sm_trace[8 * 8192];
 #else
 #define SM_TRC(k) do {} while (0)
 #endif
-template <int D, int P>
-__global__ __launch_bounds__(D * 2, D == 128 ? 4 : 1) void sm_msg_split_kernel(SmParams p) {
+// Test switch GNNMP_SM_FORCE_FALLBACK (read per forward call, gnnmp_smoother_forward_ex): the FORCE instantiations of the two message
+// kernels below treat the target flags of chosen edge tiles / rounds as not arrived WITHOUT polling and leave s_ready / s_notready
+// as an exhausted poll loop would, so the fallback (target half computed by the edge workgroup) runs deterministically.  Mode 1:
+// every edge tile / round; 2: the even ones; 3: the odd ones (split kernel: parity of blockIdx.x - n_troles; stream kernel: parity of
+// the workgroup's visit (r - (blockIdx.x - wgs_t)) / wgs_e).  Target workgroups publish as usual; forcing never waits on anything.
+// Only the FORCE instantiations take the mode (a trailing argument pack: empty for FORCE = false, one int for FORCE = true), so
+// the default instantiations keep their arguments and their code (profiles/sm_force_fallback_isa.txt).
+// g_sm_fallbacks counts the forced fallbacks taken: one per edge tile (split) or edge round (stream), FORCE instantiations only.
+__device__ unsigned long long g_sm_fallbacks;
+__device__ __forceinline__ bool sm_forced(int mode, int index) { return mode == 1 || (mode == 2 && !(index & 1)) || (mode == 3 && (index & 1)); }
+
+template <int D, int P, bool FORCE, typename... Mode>
+__global__ __launch_bounds__(D * 2, D == 128 ? 4 : 1) void sm_msg_split_kernel(SmParams p, Mode... force_mode) {
+    static_assert(sizeof...(Mode) == (FORCE ? 1 : 0), "the mode goes to the FORCE instantiations only");
     constexpr int NT = D / 32;
     __shared__ float xbuf[2][NT * 16 * 64];
     __shared__ int s_ready;
@@ -736,19 +748,25 @@ __global__ __launch_bounds__(D * 2, D == 128 ? 4 : 1) void sm_msg_split_kernel(S
         sm_exchange_put(xbuf[1], wave, mine, lane);
         SM_TRC(1);
         if (n_troles > 0) {
+            bool forced = false;                         // workgroup-uniform
+            if constexpr (FORCE) forced = sm_forced((0 + ... + force_mode), (int)blockIdx.x - n_troles);
             if (wave == 0) {                             // the flags of the path tiles this edge tile's targets live in
                 bool ready = false;
-                for (int spin = 0; spin < 256 && !ready; ++spin) {
-                    // relaxed: an acquire here would invalidate the CU's L1 (every wave's weight operands) on every poll; the
-                    // one acquire fence below, after the flags are up, is what orders the row loads
-                    const int f = __hip_atomic_load(&p.tgt_flag[trow >> 5], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    ready = __all(f != 0);
-                    if (!ready) __builtin_amdgcn_s_sleep(8);
+                if (!FORCE || !forced) {                 // forced: no poll, s_ready as after an exhausted budget.  (A guard around the
+                    // loop, not a term of its condition: that alone gave the default instantiations another exit test.)
+                    for (int spin = 0; spin < 256 && !ready; ++spin) {
+                        // relaxed: an acquire here would invalidate the CU's L1 (every wave's weight operands) on every poll; the
+                        // one acquire fence below, after the flags are up, is what orders the row loads
+                        const int f = __hip_atomic_load(&p.tgt_flag[trow >> 5], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        ready = __all(f != 0);
+                        if (!ready) __builtin_amdgcn_s_sleep(8);
+                    }
                 }
                 if (lane == 0) s_ready = ready ? 1 : 0;
             }
             __syncthreads();
             target_half = s_ready == 0;                  // the rare path: a flag did not show up in time
+            if constexpr (FORCE) { if (forced && target_half && threadIdx.x == 0) atomicAdd(&g_sm_fallbacks, 1ULL); }
             SM_TRC(2);
         } else {
             target_half = true;
@@ -812,8 +830,9 @@ __global__ __launch_bounds__(D * 2, D == 128 ? 4 : 1) void sm_msg_split_kernel(S
 // round waits for its targets' flags after the source half (bounded), and if one does not show up the whole workgroup computes the
 // target half itself -- same bits, so the wait can never hang a launch (another stream may keep the target workgroups off the device).
 // ---------------------------------------------------------------------------------------------------
-template <int D, int P>
-__global__ __launch_bounds__(512, 1) void sm_msg_stream_kernel(SmParams p, int wgs_t, int rounds_e) {
+template <int D, int P, bool FORCE, typename... Mode>
+__global__ __launch_bounds__(512, 1) void sm_msg_stream_kernel(SmParams p, int wgs_t, int rounds_e, Mode... force_mode) {
+    static_assert(sizeof...(Mode) == (FORCE ? 1 : 0), "the mode goes to the FORCE instantiations only");
     constexpr int NT = D / 32;
     constexpr int TF = Prec<P>::TF;
     constexpr int CH = NT * TF;                           // floats of one column (NT tiles) of a packed matrix
@@ -942,6 +961,8 @@ __global__ __launch_bounds__(512, 1) void sm_msg_stream_kernel(SmParams p, int w
         const int src = valid ? p.e_src[e] : 0, dst = valid ? p.e_dst[e] : 0;
         const int trow = sm_poff(p, b) + dst;             // the target's row in the padded path space
         if (threadIdx.x == 0) s_notready = 0;             // (ordered before the reads below by the barriers of the source half)
+        bool forced = false;                              // workgroup-uniform
+        if constexpr (FORCE) forced = sm_forced((0 + ... + force_mode), (r - ((int)blockIdx.x - wgs_t)) / wgs_e);     // this workgroup's visit
         f32x16 xs[NT], z[NT];
 #ifdef GNNMP_SM_TRACE
         asm volatile("s_waitcnt vmcnt(0)" :: "v"(src), "v"(dst) : "memory");
@@ -951,11 +972,13 @@ __global__ __launch_bounds__(512, 1) void sm_msg_stream_kernel(SmParams p, int w
         SM_STRC_M(2);
         {
             bool ready = !active;
-            for (int spin = 0; spin < 4096 && !ready; ++spin) {
-                // relaxed: an acquire here would invalidate the CU's L1 on every poll; the one acquire fence below orders the row loads
-                const int f = __hip_atomic_load(&p.tgt_flag[trow >> 5], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                ready = __all(f != 0);
-                if (!ready) __builtin_amdgcn_s_sleep(8);
+            if (!FORCE || !forced) {                      // forced: no poll, s_notready as after an exhausted budget (a guard, as above)
+                for (int spin = 0; spin < 4096 && !ready; ++spin) {
+                    // relaxed: an acquire here would invalidate the CU's L1 on every poll; the one acquire fence below orders the row loads
+                    const int f = __hip_atomic_load(&p.tgt_flag[trow >> 5], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    ready = __all(f != 0);
+                    if (!ready) __builtin_amdgcn_s_sleep(8);
+                }
             }
             if (!ready && lane == 0) s_notready = 1;
         }
@@ -973,6 +996,7 @@ __global__ __launch_bounds__(512, 1) void sm_msg_stream_kernel(SmParams p, int w
             asm volatile("" ::: "memory");
             __builtin_amdgcn_s_barrier();
             ++step;                                        // the slot wsrc's column went to counts as consumed
+            if constexpr (FORCE) { if (forced && threadIdx.x == 0) atomicAdd(&g_sm_fallbacks, 1ULL); }
             f32x16 xd[NT];
             node_code(sm_node_in(p, b, dst), false, W + p.L.wdst, xd, active);
             BOp<P> xb[NT];
@@ -1149,7 +1173,7 @@ static hipError_t launch_sm_graph(const SmParams& p, hipStream_t st) {
 }
 
 template <int D, int P>
-static hipError_t launch_sm_iter_t(const SmParams& p, hipStream_t st) {
+static hipError_t launch_sm_iter_t(const SmParams& p, hipStream_t st, int force) {
     {
         hipError_t e = launch_sm_graph(p, st);
         if (e != hipSuccess) return e;
@@ -1172,10 +1196,14 @@ static hipError_t launch_sm_iter_t(const SmParams& p, hipStream_t st) {
             }
             const size_t lds = (size_t)2 * (D / 32) * Prec<P>::TF * sizeof(float);
             static std::once_flag once;
-            std::call_once(once, [&] { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(sm_msg_stream_kernel<D, P>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); });
+            std::call_once(once, [&] {
+                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(sm_msg_stream_kernel<D, P, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(sm_msg_stream_kernel<D, P, true, int>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            });
             // target workgroups first (lowest block ids: dispatched first, gone after ~10 us), then one resident edge workgroup per CU
             const int grid = wgs_t + (rounds_e < cus ? rounds_e : cus);
-            hipLaunchKernelGGL((sm_msg_stream_kernel<D, P>), dim3(grid), dim3(512), lds, st, p, wgs_t, rounds_e);
+            if (force) hipLaunchKernelGGL((sm_msg_stream_kernel<D, P, true, int>), dim3(grid), dim3(512), lds, st, p, wgs_t, rounds_e, force);
+            else hipLaunchKernelGGL((sm_msg_stream_kernel<D, P, false>), dim3(grid), dim3(512), lds, st, p, wgs_t, rounds_e);
             LAUNCH_CHECK();
             hipLaunchKernelGGL((sm_node_split_kernel<D, P>), dim3(p.n_ptiles), dim3(D * 2), 0, st, p);
             LAUNCH_CHECK();
@@ -1183,7 +1211,12 @@ static hipError_t launch_sm_iter_t(const SmParams& p, hipStream_t st) {
         }
     }
     if (split) {
-        hipLaunchKernelGGL((sm_msg_split_kernel<D, P>), dim3(p.n_etiles + (p.tgt_flag ? p.n_ptiles : 0)), dim3(D * 2), 0, st, p);
+        const dim3 grid(p.n_etiles + (p.tgt_flag ? p.n_ptiles : 0));
+        bool launched = false;
+        if constexpr (D == 128) {                          // GNNMP_SM_FORCE_FALLBACK: the forcing instantiations exist at d = 128 only
+            if (force) { hipLaunchKernelGGL((sm_msg_split_kernel<D, P, true, int>), grid, dim3(D * 2), 0, st, p, force); launched = true; }
+        }
+        if (!launched) hipLaunchKernelGGL((sm_msg_split_kernel<D, P, false>), grid, dim3(D * 2), 0, st, p);
         LAUNCH_CHECK();
         hipLaunchKernelGGL((sm_node_split_kernel<D, P>), dim3(p.n_ptiles), dim3(D * 2), 0, st, p);
         LAUNCH_CHECK();
@@ -1206,16 +1239,29 @@ bool sm_wants_tile_lists(int D, int P, int n_etiles) {
     return D == 128 && P == 0 && (stream_env >= 0 ? stream_env != 0 : n_etiles >= kSmStreamMinTiles);
 }
 
-hipError_t launch_sm_iter(int D, int P, const SmParams& p, hipStream_t st) {
+hipError_t launch_sm_iter(int D, int P, const SmParams& p, hipStream_t st, int force_fallback) {
+    const int force = force_fallback >= 1 && force_fallback <= 3 ? force_fallback : 0;
     switch (D) {
-        case 32: return P ? launch_sm_iter_t<32, 1>(p, st) : launch_sm_iter_t<32, 0>(p, st);
-        case 64: return P ? launch_sm_iter_t<64, 1>(p, st) : launch_sm_iter_t<64, 0>(p, st);
-        case 128: return P ? launch_sm_iter_t<128, 1>(p, st) : launch_sm_iter_t<128, 0>(p, st);
+        case 32: return P ? launch_sm_iter_t<32, 1>(p, st, force) : launch_sm_iter_t<32, 0>(p, st, force);
+        case 64: return P ? launch_sm_iter_t<64, 1>(p, st, force) : launch_sm_iter_t<64, 0>(p, st, force);
+        case 128: return P ? launch_sm_iter_t<128, 1>(p, st, force) : launch_sm_iter_t<128, 0>(p, st, force);
     }
     return hipErrorInvalidValue;
 }
 
 }  // namespace gnnmp
+
+// forced fallbacks taken since the last reset (GNNMP_SM_FORCE_FALLBACK, see g_sm_fallbacks): waits for the device, then reads and
+// optionally zeroes the counter.  A test hook of the gnnmp_debug_* family: not part of the C ABI of gnnmp.h.
+extern "C" int gnnmp_debug_sm_fallbacks(unsigned long long* out, int reset) {
+    if (hipDeviceSynchronize() != hipSuccess) return -1;
+    if (out && hipMemcpyFromSymbol(out, HIP_SYMBOL(gnnmp::g_sm_fallbacks), sizeof(unsigned long long)) != hipSuccess) return -1;
+    if (reset) {
+        const unsigned long long zero = 0;
+        if (hipMemcpyToSymbol(HIP_SYMBOL(gnnmp::g_sm_fallbacks), &zero, sizeof(zero)) != hipSuccess) return -1;
+    }
+    return 0;
+}
 
 #ifdef GNNMP_SM_TRACE
 extern "C" int gnnmp_debug_sm_trace(long long* dst, int n_wgs) {

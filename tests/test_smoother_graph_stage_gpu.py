@@ -71,9 +71,10 @@ def test_one_launch_graph_stage_equals_two_launch_form_bitwise(case, tmp_path):
 
 @pytest.mark.parametrize('case', ['c7', 'c14'])
 def test_message_kernel_without_target_role_same_bits(case, tmp_path):
-    """The split message kernel's edge tiles normally continue from the target rows its first workgroups publish; the path
-    that computes the target half inside the edge tile (taken when a flag does not show up within the polling budget, and
-    with GNNMP_SM_NO_TARGET_ROLE=1) must give the same bits."""
+    """The split message kernel's edge tiles normally continue from the target rows its first workgroups publish; without a
+    target role (GNNMP_SM_NO_TARGET_ROLE=1: no target workgroups in the grid, every edge tile computes the target half itself)
+    the bits must be the same.  This is the no-target-role form only; the flag timeout with target workgroups present (block
+    ids offset by their number, some edge tiles falling back and others not) is tests/test_smoother_fallback_gpu.py."""
     outs = []
     for no_target in ('0', '1'):
         out = str(tmp_path / ('out_%s.pt' % no_target))
