@@ -18,7 +18,10 @@ from . import lazysp  # noqa: F401,E402  (the LazySP baseline on maze problems: 
 from .lazysp import eval_lazysp_device, plan_host as lazysp_plan_host, plan_maze_batch as plan_lazysp_maze_batch  # noqa: F401,E402
 from . import rrtstar  # noqa: F401,E402  (the RRT* baseline on maze problems: gnnmp_rrtstar_*)
 from .rrtstar import eval_rrt_device, plan_host as rrtstar_plan_host, plan_maze_batch as plan_rrtstar_maze_batch  # noqa: F401,E402
+from . import bitstar  # noqa: F401,E402  (the BIT* baseline on maze problems: gnnmp_bitstar_*)
+from .bitstar import eval_bit_device, plan_host as bitstar_plan_host, plan_maze_batch as plan_bitstar_maze_batch  # noqa: F401,E402
 
 __all__ = ['graph_build', 'hostenv', 'synth', 'GraphBatch', 'EncoderProcessDecoder', 'ModelSmoother', 'SmoothBatch', 'episodes',
            'oracle_smooth', 'frontier', 'rng', 'lazysp', 'eval_lazysp_device', 'lazysp_plan_host', 'plan_lazysp_maze_batch', 'rrtstar',
-           'eval_rrt_device', 'rrtstar_plan_host', 'plan_rrtstar_maze_batch']
+           'eval_rrt_device', 'rrtstar_plan_host', 'plan_rrtstar_maze_batch', 'bitstar', 'eval_bit_device', 'bitstar_plan_host',
+           'plan_bitstar_maze_batch']

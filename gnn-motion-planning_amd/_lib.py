@@ -6,7 +6,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('GNNMP_LIB') or os.path.join(_HERE, 'libgnnmp.so')      # GNNMP_LIB: an experiment build (tools/diag/build_variant.sh)
 
-ABI_VERSION = 6                        # include/gnnmp.h gnnmp_abi_version(): what this binding was written against
+ABI_VERSION = 7                        # include/gnnmp.h gnnmp_abi_version(): what this binding was written against
 
 c_float_p = ctypes.POINTER(ctypes.c_float)
 c_int32_p = ctypes.POINTER(ctypes.c_int32)
@@ -101,6 +101,19 @@ class RRTStarTree(ctypes.Structure):
                 ('cumulated_checks', ctypes.c_void_p), ('path', ctypes.c_void_p), ('n_nodes', ctypes.c_void_p),
                 ('success', ctypes.c_void_p), ('last_iter', ctypes.c_void_p), ('used', ctypes.c_void_p), ('path_len', ctypes.c_void_p),
                 ('status', ctypes.c_void_p)]
+
+
+class BITStarBatch(ctypes.Structure):
+    _fields_ = [('n_problems', ctypes.c_int32), ('dim', ctypes.c_int32), ('width', ctypes.c_int32), ('batch', ctypes.c_int32),
+                ('n_batches', ctypes.c_int32), ('n_nodes', ctypes.c_int32), ('flags', ctypes.c_int32), ('edge_cap', ctypes.c_int64),
+                ('maps', ctypes.c_void_p), ('pool', ctypes.c_void_p), ('r_by_batch', ctypes.c_void_p),
+                ('checks_by_batch', ctypes.c_void_p)]
+
+
+class BITStarResult(ctypes.Structure):
+    _fields_ = [('g', ctypes.c_void_p), ('parents', ctypes.c_void_p), ('vertices', ctypes.c_void_p), ('path', ctypes.c_void_p),
+                ('n_vertices', ctypes.c_void_p), ('batches_run', ctypes.c_void_p), ('success', ctypes.c_void_p),
+                ('path_len', ctypes.c_void_p), ('status', ctypes.c_void_p), ('counters', ctypes.c_void_p)]
 
 
 class MtUniformBatch(ctypes.Structure):
@@ -239,6 +252,10 @@ def lib():
     L.gnnmp_rrtstar_workspace_bytes.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(sz)]
     L.gnnmp_rrtstar_lds_nodes.argtypes = []
     L.gnnmp_rrtstar_plan.argtypes = [ctypes.POINTER(RRTStarBatch), ctypes.POINTER(RRTStarTree), vp, sz, vp]
+    L.gnnmp_bitstar_sample.argtypes = [ctypes.POINTER(MazeStreamsBatch), ctypes.c_int32, ctypes.c_int32, vp, vp, vp, vp, vp]
+    L.gnnmp_bitstar_workspace_bytes.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, ctypes.POINTER(sz)]
+    L.gnnmp_bitstar_lds_nodes.argtypes = []
+    L.gnnmp_bitstar_plan.argtypes = [ctypes.POINTER(BITStarBatch), ctypes.POINTER(BITStarResult), vp, sz, vp]
     L.gnnmp_maze_steer.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, vp, vp, vp, vp, vp, vp, vp, vp]
     L.gnnmp_stick_steer.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.gnnmp_episode_label_maze.argtypes = [ctypes.POINTER(EpisodeGraphs), ctypes.c_int32, ctypes.c_int32, vp, vp, vp, vp, vp]

@@ -248,7 +248,7 @@ extern "C" const char* gnnmp_status_string(int s) {
 }
 extern "C" const char* gnnmp_last_hip_error(void) { return g_hip_error.c_str(); }
 // 2: stage list of gnnmp_explorer_profile_read (fused message passing); 3: device-side status words (gnnmp_*_status*)
-extern "C" int gnnmp_abi_version(void) { return 6; }
+extern "C" int gnnmp_abi_version(void) { return 7; }
 
 // ---------------------------------------------------------------------------------------------
 // explorer handle
@@ -1853,6 +1853,89 @@ extern "C" int gnnmp_rrtstar_plan(const gnnmp_rrtstar_batch* b, const gnnmp_rrts
     p.ws_z = reinterpret_cast<double*>(ws + c.z); p.ws_c = reinterpret_cast<double*>(ws + c.c);
     p.ws_f = reinterpret_cast<unsigned char*>(ws + c.f);
     HIP_TRY(launch_rrtstar_plan(p, static_cast<hipStream_t>(hip_stream)));
+    return GNNMP_OK;
+}
+
+// =============================================================================================
+// the BIT* baseline on maze problems (bitstar_kernels.hip; algorithm/bit_star.py:18-334)
+// =============================================================================================
+namespace {
+struct BitCarve { size_t eval, esrc, etgt, vval, flag, total; };
+BitCarve bit_carve(int n_problems, int n_nodes, long long edge_cap) {
+    BitCarve c{0, 0, 0, 0, 0, 0};
+    const size_t edges = (size_t)n_problems * (size_t)edge_cap, nodes = (size_t)n_problems * (size_t)n_nodes;
+    size_t off = 0;
+    c.eval = off; off = lsp_align(off + sizeof(double) * edges);
+    c.esrc = off; off = lsp_align(off + sizeof(int) * edges);
+    c.etgt = off; off = lsp_align(off + sizeof(int) * edges);
+    c.vval = off; off = lsp_align(off + sizeof(double) * nodes);
+    c.flag = off; off = lsp_align(off + nodes);
+    c.total = off;
+    return c;
+}
+bool bit_sizes_ok(int n_problems, int n_nodes, long long edge_cap) {
+    return n_problems >= 1 && n_nodes >= 3 && edge_cap >= 1 && edge_cap <= (long long)n_nodes * (n_nodes - 1);
+}
+}  // namespace
+
+extern "C" int gnnmp_bitstar_sample(const gnnmp_maze_streams_batch* b, int32_t dim, int32_t n_batches, double* pool,
+                                    int64_t* used_by_batch, int64_t* checks_by_batch, int32_t* status_out, void* hip_stream) {
+    if (dim != 2 && dim != 3) return GNNMP_ERR_DIMS;
+    if (!b || !pool || !used_by_batch || !checks_by_batch || !status_out) return GNNMP_ERR_NULL;
+    if (!b->attempts || !b->att_ptr || !b->maps || !b->init_states || !b->goal_states) return GNNMP_ERR_NULL;
+    if (b->n_problems < 1 || b->width < 1 || b->n_free < 1 || n_batches < 1 || b->n_attempts < 0) return GNNMP_ERR_ARG;
+    if ((long long)b->cap < 2 + (long long)n_batches * b->n_free) return GNNMP_ERR_ARG;
+    if (b->att_ptr_host) {
+        if (b->att_ptr_host[0] < 0 || b->att_ptr_host[b->n_problems] > b->n_attempts) return GNNMP_ERR_ARG;
+        for (int i = 0; i < b->n_problems; ++i)
+            if (b->att_ptr_host[i + 1] < b->att_ptr_host[i]) return GNNMP_ERR_ARG;
+    }
+    BitSampleParams p;
+    p.B = b->n_problems; p.w = b->width; p.batch = b->n_free; p.n_batches = n_batches; p.rows = b->cap; p.dim = dim;
+    p.attempts = b->attempts; p.M = b->n_attempts; p.att_ptr = reinterpret_cast<const long long*>(b->att_ptr);
+    p.maps = b->maps; p.init_states = b->init_states; p.goal_states = b->goal_states; p.active = b->active;
+    p.pool = pool; p.used_by_batch = reinterpret_cast<long long*>(used_by_batch);
+    p.checks_by_batch = reinterpret_cast<long long*>(checks_by_batch); p.status = status_out;
+    HIP_TRY(launch_bit_sample(p, static_cast<hipStream_t>(hip_stream)));
+    return GNNMP_OK;
+}
+
+extern "C" int gnnmp_bitstar_workspace_bytes(int32_t n_problems, int32_t n_nodes, int64_t edge_cap, size_t* bytes) {
+    if (!bytes) return GNNMP_ERR_NULL;
+    if (!bit_sizes_ok(n_problems, n_nodes, edge_cap)) return GNNMP_ERR_ARG;
+    *bytes = bit_carve(n_problems, n_nodes, edge_cap).total;
+    return GNNMP_OK;
+}
+
+extern "C" int gnnmp_bitstar_lds_nodes(void) { return bit_lds_nodes(); }
+
+extern "C" int gnnmp_bitstar_plan(const gnnmp_bitstar_batch* b, const gnnmp_bitstar_result* r, void* workspace, size_t workspace_bytes,
+                                  void* hip_stream) {
+    if (!b || !r) return GNNMP_ERR_NULL;
+    if (b->dim != 2 && b->dim != 3) return GNNMP_ERR_DIMS;
+    if (!b->maps || !b->pool || !b->r_by_batch || !b->checks_by_batch) return GNNMP_ERR_NULL;
+    if (!r->g || !r->parents || !r->vertices || !r->path || !r->n_vertices || !r->batches_run || !r->success || !r->path_len ||
+        !r->status || !r->counters)
+        return GNNMP_ERR_NULL;
+    if (b->width < 1 || b->batch < 1 || b->n_batches < 1 || (b->flags & ~1)) return GNNMP_ERR_ARG;
+    if ((long long)b->n_nodes < 2 + (long long)b->n_batches * b->batch) return GNNMP_ERR_ARG;
+    if (!bit_sizes_ok(b->n_problems, b->n_nodes, b->edge_cap)) return GNNMP_ERR_ARG;
+    if (!workspace) return GNNMP_ERR_NULL;
+    const BitCarve c = bit_carve(b->n_problems, b->n_nodes, b->edge_cap);
+    if (workspace_bytes < c.total || (reinterpret_cast<uintptr_t>(workspace) & 255)) return GNNMP_ERR_WORKSPACE;
+    char* ws = static_cast<char*>(workspace);
+    BitPlanParams p;
+    p.B = b->n_problems; p.w = b->width; p.batch = b->batch; p.n_batches = b->n_batches; p.rows = b->n_nodes; p.dim = b->dim;
+    p.flags = b->flags; p.edge_cap = b->edge_cap;
+    p.maps = b->maps; p.pool = b->pool; p.r_by_batch = b->r_by_batch;
+    p.checks_by_batch = reinterpret_cast<const long long*>(b->checks_by_batch);
+    p.g = r->g; p.parents = r->parents; p.vertices = r->vertices; p.path = r->path; p.n_vertices = r->n_vertices;
+    p.batches_run = r->batches_run; p.success = r->success; p.path_len = r->path_len; p.status = r->status;
+    p.counters = reinterpret_cast<long long*>(r->counters);
+    p.ws_eval = reinterpret_cast<double*>(ws + c.eval); p.ws_esrc = reinterpret_cast<int*>(ws + c.esrc);
+    p.ws_etgt = reinterpret_cast<int*>(ws + c.etgt); p.ws_vval = reinterpret_cast<double*>(ws + c.vval);
+    p.ws_flag = reinterpret_cast<unsigned char*>(ws + c.flag);
+    HIP_TRY(launch_bit_plan(p, static_cast<hipStream_t>(hip_stream)));
     return GNNMP_OK;
 }
 

@@ -335,6 +335,36 @@ struct RrtParams {
 hipError_t launch_rrtstar_plan(const RrtParams& p, hipStream_t st);
 int rrtstar_lds_nodes();
 
+// ---- the BIT* baseline on maze problems (bitstar_kernels.hip, algorithm/bit_star.py:18-334)
+struct BitSampleParams {
+    int B, w, batch, n_batches, rows, dim;   // problems, map width, free draws a batch, batches, pool rows a problem, 2 / 3
+    const double* attempts;               // [M, dim], problem b's block at att_ptr[b]
+    long long M;
+    const long long* att_ptr;             // [B + 1]
+    const double *maps, *init_states, *goal_states;      // [B, w, w], [B, dim], [B, dim]
+    const unsigned char* active;          // [B] or nullptr (= all)
+    double* pool;                         // out [B, rows, dim]: row 0 = start, row 1 = goal, then the free draws
+    long long *used_by_batch, *checks_by_batch;          // out [B, n_batches]: cumulative attempts / sampling checks
+    int* status;                          // out [B]: 0 done, 1 the block ended first, 2 block outside attempts
+};
+hipError_t launch_bit_sample(const BitSampleParams& p, hipStream_t st);
+
+struct BitPlanParams {
+    int B, w, batch, n_batches, rows, dim, flags;
+    long long edge_cap;                   // entries of a problem's edge queue
+    const double *maps, *pool, *r_by_batch;              // [B, w, w], [B, rows, dim], [B, n_batches]
+    const long long* checks_by_batch;     // [B, n_batches]
+    double* g;                            // out [B, rows]
+    int *parents, *vertices, *path;       // out [B, rows]
+    int *n_vertices, *batches_run, *success, *path_len, *status;      // out [B]
+    long long* counters;                  // out [B, 8]
+    double *ws_eval, *ws_vval;            // workspace: [B, edge_cap], [B, rows] (problems beyond the LDS node count)
+    int *ws_esrc, *ws_etgt;               // [B, edge_cap] each
+    unsigned char* ws_flag;               // [B, rows]
+};
+hipError_t launch_bit_plan(const BitPlanParams& p, hipStream_t st);
+int bit_lds_nodes();
+
 // ---- supervision of the explorer's training step (train_episode_kernels.hip, train_explorer.py:124-176)
 struct EpLabelParams {                    // (a) edge_free / edge_cost of construct_graph for maze problems
     int B, dim, w;

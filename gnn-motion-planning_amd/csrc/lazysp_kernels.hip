@@ -22,15 +22,7 @@ namespace {
 
 // the counted float64 checker (lsp_maze, lsp_point, lsp_segment, lsp_edge2, lsp_stick, lsp_stick_edge_wave): maze_f64.hpp
 
-// np.linalg.norm(t - s) = sqrt(dot(d, d)); numpy's BLAS dot accumulates left to right with fused multiply-adds
-template <int DIM>
-__device__ __forceinline__ double lsp_cost(const double* s, const double* t) {
-    const double d0 = t[0] - s[0], d1 = t[1] - s[1];
-    double acc = d0 * d0;
-    acc = __builtin_fma(d1, d1, acc);
-    if (DIM == 3) { const double d2 = t[2] - s[2]; acc = __builtin_fma(d2, d2, acc); }
-    return sqrt(acc);
-}
+// np.linalg.norm(t - s) with its fused dot product (lsp_cost): maze_f64.hpp too
 
 // first slot q in [lo, hi) with key[q] >= x (key sorted ascending), hi when none
 __device__ __forceinline__ int lsp_lower_bound(const long long* key, int lo, int hi, long long x) {

@@ -50,6 +50,16 @@ __device__ __forceinline__ LspMaze lsp_maze(const double* map, int w, unsigned c
     return m;
 }
 
+// np.linalg.norm(t - s) = sqrt(dot(d, d)); numpy's BLAS dot accumulates left to right with fused multiply-adds
+template <int DIM>
+__device__ __forceinline__ double lsp_cost(const double* s, const double* t) {
+    const double d0 = t[0] - s[0], d1 = t[1] - s[1];
+    double acc = d0 * d0;
+    acc = __builtin_fma(d1, d1, acc);
+    if (DIM == 3) { const double d2 = t[2] - s[2]; acc = __builtin_fma(d2, d2, acc); }
+    return sqrt(acc);
+}
+
 // ---- MazeEnv's checker on float64 states, every in-bounds point query counted (environment/maze_env.py:236-347)
 __device__ __forceinline__ int lsp_cell(double x, int w) {      // ((x + 1.0) * w / 2.0).astype(int), clipped at w - 1
     const int c = (int)((x + 1.0) * (double)w / 2.0);

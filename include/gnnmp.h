@@ -811,6 +811,84 @@ int gnnmp_rrtstar_plan(const gnnmp_rrtstar_batch* batch, const gnnmp_rrtstar_tre
                        void* hip_stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The BIT* baseline on maze problems -- eval_bit.eval_bit's BITStar(env, batch_size, T, sampling=None).plan(INF,
+ * time_budget=300, refine_time_budget=0) and get_best_path() (algorithm/bit_star.py:18-334 over
+ * environment/maze_env.py:236-347) -- batched, every problem on its own sample stream: problem b computes what
+ * np.random.seed(s_b); env.init_new_problem(i_b); BITStar(...).plan(...) of that problem alone computes (eval_bit's one global
+ * stream over consecutive problems is NOT reproduced).  Reproduced is the search for the FIRST solution: with
+ * refine_time_budget = 0 the loop ends with the iteration that reaches the goal, c_best is infinite at every sampling call,
+ * prune removes nothing; refinement and the wall-clock budgets are not.  Node 0 is the START, node 1 the GOAL, then the free
+ * draws in order.  All decisions are float64, one rounded operation at a time; the radius comes from the host.
+ *   gnnmp_bitstar_sample    the free draws of all n_batches batches, per batch the attempts and checks    bit_star.py:111-140
+ *   gnnmp_bitstar_plan      the search                                                                    bit_star.py:212-334
+ * ---------------------------------------------------------------------------------------- */
+/* Sampling.  `batch` is a gnnmp_maze_streams_batch as gnnmp_maze_sample_streams reads it: n_free = free draws per BIT* batch,
+ * cap = rows per problem of pool (>= 2 + n_batches * n_free), problem b's attempts (float64 [n_attempts, dim], the states
+ * bounds[:, 0] + random(dim) * ranges in draw order) at [att_ptr[b], att_ptr[b + 1]).  One launch, one wave per active problem.
+ * A draw is free iff _state_fp holds (counted).  pool [B, cap, dim]: row 0 the init state, row 1 the goal state, then the
+ * n_batches * n_free free draws in order.  used_by_batch / checks_by_batch [B, n_batches]: attempts consumed and sampling
+ * checks spent when batch k was complete (cumulative).  status_out [B]: 0; 1 = the block ended before the last batch was
+ * complete -- pool and tables of that problem are untouched, hand it a longer block; 2 = the block lies outside attempts.
+ * GNNMP_ERR_DIMS (dim not 2 / 3) / GNNMP_ERR_NULL / GNNMP_ERR_ARG (n_problems, width, n_free or n_batches < 1, cap too small,
+ * n_attempts < 0, att_ptr_host not ascending inside [0, n_attempts]); nothing is launched then. */
+int gnnmp_bitstar_sample(const gnnmp_maze_streams_batch* batch, int32_t dim, int32_t n_batches, double* pool,
+                         int64_t* used_by_batch, int64_t* checks_by_batch, int32_t* status_out, void* hip_stream);
+
+typedef struct {
+    int32_t n_problems, dim, width;      /* dim 2 = point robot, 3 = stick robot; maps are width x width              */
+    int32_t batch, n_batches;            /* free draws per batch; ceil(t_max / batch) batches at most                  */
+    int32_t n_nodes;                     /* rows per problem of pool and of the per-node outputs, >= 2 + n_batches * batch */
+    int32_t flags;                       /* bit 0: keep the node state in the outputs and the workspace whatever the node
+                                          * count (the path of problems beyond gnnmp_bitstar_lds_nodes(); same results);
+                                          * other bits must be 0                                                       */
+    int64_t edge_cap;                    /* entries of a problem's edge queue, 1 .. n_nodes * (n_nodes - 1)             */
+    const double* maps;                  /* [B, width, width]  0 = free                                                 */
+    const double* pool;                  /* [B, n_nodes, dim]  gnnmp_bitstar_sample's                                   */
+    const double* r_by_batch;            /* [B, n_batches]  the radius after batch k: radius_init() * (log(q) / q) ** (1 / dim)
+                                          * with the reference's own expressions, computed by the host                  */
+    const int64_t* checks_by_batch;      /* [B, n_batches]  gnnmp_bitstar_sample's                                      */
+} gnnmp_bitstar_batch;
+
+typedef struct {                         /* all out                                                                     */
+    double* g;                           /* [B, n_nodes]  g_scores by node id, inf off the tree                         */
+    int32_t* parents;                    /* [B, n_nodes]  edges[x] by node id, -1 = none                                */
+    int32_t* vertices;                   /* [B, n_nodes]  node ids in the order they joined the tree; n_vertices entries, -1 behind */
+    int32_t* path;                       /* [B, n_nodes]  get_best_path(): node ids start -> goal; path_len entries      */
+    int32_t* n_vertices;                 /* [B]                                                                         */
+    int32_t* batches_run;                /* [B]  batches drawn: T = batches_run * batch                                 */
+    int32_t* success;                    /* [B]  1 = g_scores[goal] is finite                                           */
+    int32_t* path_len;                   /* [B]                                                                         */
+    int32_t* status;                     /* [B]  0, or bits: 1 = the edge queue was full (run the problem again with a larger
+                                          * edge_cap), 2 = a loop bound was hit or the parents hold a cycle, 4 = a radius that
+                                          * is not positive or a negative check count (tables not filled).  Any bit ends the
+                                          * problem; the other problems of the batch are not affected                  */
+    int64_t* counters;                   /* [B, 8]  collision checks (sampling of the batches drawn + edges),
+                                          * vertex_expansions, edge_pops, edge_checks, rewired, filtered, max_edge_queue,
+                                          * ties_at_pop                                                                 */
+} gnnmp_bitstar_result;
+
+/* Workspace of gnnmp_bitstar_plan (256-byte aligned): per problem the edge queue (16 bytes an entry) and per node the queued
+ * value and a flag byte (the per-node part is sized at every node count).  GNNMP_ERR_NULL / GNNMP_ERR_ARG (n_problems < 1, n_nodes < 3, edge_cap outside
+ * [1, n_nodes * (n_nodes - 1)]). */
+int gnnmp_bitstar_workspace_bytes(int32_t n_problems, int32_t n_nodes, int64_t edge_cap, size_t* bytes);
+/* Launches of up to this many nodes per problem (2 + n_batches * batch) keep their node state in LDS; larger ones, and those
+ * with bit 0 of flags set, use the outputs and the workspace. */
+int gnnmp_bitstar_lds_nodes(void);
+
+/* BIT* for batch->n_problems maze problems, one launch on hip_stream, one wave per problem: no allocation, no
+ * synchronisation, no atomics, deterministic.  Semantics as restated above and in gnnmp.bitstar.plan_host; in particular
+ *   - a batch is drawn only when both queues are empty; the loop test T < t_max stands at the top of every iteration, so the
+ *     iteration that draws the last batch still pops one edge;
+ *   - both queues pop in heapq's tuple order: value, then the source point's coordinates, then the target point's;
+ *   - distance = np.linalg.norm(a - b) in all dim coordinates (left-to-right fused dot product), no wrap of the angle;
+ *   - an accepted edge removes every queued edge with the same target; descendants keep their costs.
+ * All argument errors come back before anything is launched: GNNMP_ERR_NULL (a NULL struct, array or workspace),
+ * GNNMP_ERR_DIMS (dim not 2 / 3), GNNMP_ERR_ARG (n_problems / width / batch / n_batches < 1, n_nodes < 2 + n_batches * batch,
+ * edge_cap outside [1, n_nodes * (n_nodes - 1)], flags beyond bit 0), GNNMP_ERR_WORKSPACE (too small or misaligned). */
+int gnnmp_bitstar_plan(const gnnmp_bitstar_batch* batch, const gnnmp_bitstar_result* result, void* workspace,
+                       size_t workspace_bytes, void* hip_stream);
+
+/* ------------------------------------------------------------------------------------------
  * Supervision of the explorer's training step (train_explorer.py:124-176): edge labels, shortest paths to the goal,
  * the greedy roll-out of the detached policy and the frontier / label of the loss, for a batch of problems.
  *   gnnmp_episode_label_maze      construct_graph's collision checks and costs     algorithm/dijkstra.py:15-31
