@@ -20,8 +20,11 @@ from . import rrtstar  # noqa: F401,E402  (the RRT* baseline on maze problems: g
 from .rrtstar import eval_rrt_device, plan_host as rrtstar_plan_host, plan_maze_batch as plan_rrtstar_maze_batch  # noqa: F401,E402
 from . import bitstar  # noqa: F401,E402  (the BIT* baseline on maze problems: gnnmp_bitstar_*)
 from .bitstar import eval_bit_device, plan_host as bitstar_plan_host, plan_maze_batch as plan_bitstar_maze_batch  # noqa: F401,E402
+from . import next_model, next_plan  # noqa: F401,E402  (the NEXT planning network on maze problems: gnnmp_next_*; NEXT_plan on the host)
+from .next_model import Model2D, NextNet  # noqa: F401,E402
+from .next_plan import plan_host as next_plan_host  # noqa: F401,E402
 
 __all__ = ['graph_build', 'hostenv', 'synth', 'GraphBatch', 'EncoderProcessDecoder', 'ModelSmoother', 'SmoothBatch', 'episodes',
            'oracle_smooth', 'frontier', 'rng', 'lazysp', 'eval_lazysp_device', 'lazysp_plan_host', 'plan_lazysp_maze_batch', 'rrtstar',
            'eval_rrt_device', 'rrtstar_plan_host', 'plan_rrtstar_maze_batch', 'bitstar', 'eval_bit_device', 'bitstar_plan_host',
-           'plan_bitstar_maze_batch']
+           'plan_bitstar_maze_batch', 'next_model', 'next_plan', 'Model2D', 'NextNet', 'next_plan_host']

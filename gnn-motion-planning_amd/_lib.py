@@ -6,7 +6,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('GNNMP_LIB') or os.path.join(_HERE, 'libgnnmp.so')      # GNNMP_LIB: an experiment build (tools/diag/build_variant.sh)
 
-ABI_VERSION = 7                        # include/gnnmp.h gnnmp_abi_version(): what this binding was written against
+ABI_VERSION = 8                        # include/gnnmp.h gnnmp_abi_version(): what this binding was written against
 
 c_float_p = ctypes.POINTER(ctypes.c_float)
 c_int32_p = ctypes.POINTER(ctypes.c_int32)
@@ -114,6 +114,17 @@ class BITStarResult(ctypes.Structure):
     _fields_ = [('g', ctypes.c_void_p), ('parents', ctypes.c_void_p), ('vertices', ctypes.c_void_p), ('path', ctypes.c_void_p),
                 ('n_vertices', ctypes.c_void_p), ('batches_run', ctypes.c_void_p), ('success', ctypes.c_void_p),
                 ('path_len', ctypes.c_void_p), ('status', ctypes.c_void_p), ('counters', ctypes.c_void_p)]
+
+
+class NextPbForward(ctypes.Structure):
+    _fields_ = [('n_problems', ctypes.c_int32), ('dim', ctypes.c_int32), ('width', ctypes.c_int32), ('iters', ctypes.c_int32),
+                ('maps', ctypes.c_void_p), ('goals', ctypes.c_void_p), ('weights', ctypes.c_void_p), ('pb_rep', ctypes.c_void_p)]
+
+
+class NextStateForward(ctypes.Structure):
+    _fields_ = [('n_states', ctypes.c_int32), ('n_problems', ctypes.c_int32), ('dim', ctypes.c_int32), ('width', ctypes.c_int32),
+                ('states', ctypes.c_void_p), ('problem_of_state', ctypes.c_void_p), ('pb_rep', ctypes.c_void_p),
+                ('weights', ctypes.c_void_p), ('y', ctypes.c_void_p), ('status', ctypes.c_void_p)]
 
 
 class MtUniformBatch(ctypes.Structure):
@@ -256,6 +267,9 @@ def lib():
     L.gnnmp_bitstar_workspace_bytes.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, ctypes.POINTER(sz)]
     L.gnnmp_bitstar_lds_nodes.argtypes = []
     L.gnnmp_bitstar_plan.argtypes = [ctypes.POINTER(BITStarBatch), ctypes.POINTER(BITStarResult), vp, sz, vp]
+    L.gnnmp_next_weights_floats.argtypes = [ctypes.c_int32, ctypes.POINTER(sz)]
+    L.gnnmp_next_pb_forward.argtypes = [ctypes.POINTER(NextPbForward), vp]
+    L.gnnmp_next_state_forward.argtypes = [ctypes.POINTER(NextStateForward), vp]
     L.gnnmp_maze_steer.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, vp, vp, vp, vp, vp, vp, vp, vp]
     L.gnnmp_stick_steer.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.gnnmp_episode_label_maze.argtypes = [ctypes.POINTER(EpisodeGraphs), ctypes.c_int32, ctypes.c_int32, vp, vp, vp, vp, vp]

@@ -248,7 +248,7 @@ extern "C" const char* gnnmp_status_string(int s) {
 }
 extern "C" const char* gnnmp_last_hip_error(void) { return g_hip_error.c_str(); }
 // 2: stage list of gnnmp_explorer_profile_read (fused message passing); 3: device-side status words (gnnmp_*_status*)
-extern "C" int gnnmp_abi_version(void) { return 7; }
+extern "C" int gnnmp_abi_version(void) { return 8; }
 
 // ---------------------------------------------------------------------------------------------
 // explorer handle
@@ -1936,6 +1936,45 @@ extern "C" int gnnmp_bitstar_plan(const gnnmp_bitstar_batch* b, const gnnmp_bits
     p.ws_etgt = reinterpret_cast<int*>(ws + c.etgt); p.ws_vval = reinterpret_cast<double*>(ws + c.vval);
     p.ws_flag = reinterpret_cast<unsigned char*>(ws + c.flag);
     HIP_TRY(launch_bit_plan(p, static_cast<hipStream_t>(hip_stream)));
+    return GNNMP_OK;
+}
+
+// =============================================================================================
+// the NEXT planning network on maze problems (next_kernels.hip; next_model/model2D.py:84-210)
+// =============================================================================================
+extern "C" int gnnmp_next_weights_floats(int32_t dim, size_t* n_floats) {
+    if (!n_floats) return GNNMP_ERR_NULL;
+    if (dim != 2 && dim != 3) return GNNMP_ERR_DIMS;
+    *n_floats = next_weights_floats();
+    return GNNMP_OK;
+}
+
+extern "C" int gnnmp_next_pb_forward(const gnnmp_next_pb* d, void* hip_stream) {
+    if (!d) return GNNMP_ERR_NULL;
+    if (d->dim != 2 && d->dim != 3) return GNNMP_ERR_DIMS;
+    if (d->width != 15) return GNNMP_ERR_DIMS;
+    if (d->n_problems < 0 || d->iters < 0) return GNNMP_ERR_ARG;
+    if (!d->maps || !d->goals || !d->weights || !d->pb_rep) return GNNMP_ERR_NULL;
+    if (d->n_problems == 0) return GNNMP_OK;
+    NextPbParams p;
+    p.B = d->n_problems; p.dim = d->dim; p.iters = d->iters;
+    p.maps = d->maps; p.goals = d->goals; p.weights = d->weights; p.pb_rep = d->pb_rep;
+    HIP_TRY(launch_next_pb_forward(p, static_cast<hipStream_t>(hip_stream)));
+    return GNNMP_OK;
+}
+
+extern "C" int gnnmp_next_state_forward(const gnnmp_next_states* d, void* hip_stream) {
+    if (!d) return GNNMP_ERR_NULL;
+    if (d->dim != 2 && d->dim != 3) return GNNMP_ERR_DIMS;
+    if (d->width != 15) return GNNMP_ERR_DIMS;
+    if (d->n_states < 0 || d->n_problems < 0) return GNNMP_ERR_ARG;
+    if (!d->states || !d->problem_of_state || !d->pb_rep || !d->weights || !d->y || !d->status) return GNNMP_ERR_NULL;
+    if (d->n_states == 0) return GNNMP_OK;
+    NextStateParams p;
+    p.S = d->n_states; p.B = d->n_problems; p.dim = d->dim;
+    p.states = d->states; p.problem_of_state = d->problem_of_state; p.pb_rep = d->pb_rep; p.weights = d->weights; p.y = d->y;
+    p.status = d->status;
+    HIP_TRY(launch_next_state_forward(p, static_cast<hipStream_t>(hip_stream)));
     return GNNMP_OK;
 }
 

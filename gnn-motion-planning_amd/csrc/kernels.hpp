@@ -335,6 +335,25 @@ struct RrtParams {
 hipError_t launch_rrtstar_plan(const RrtParams& p, hipStream_t st);
 int rrtstar_lds_nodes();
 
+// ---- the NEXT planning network on maze problems (next_kernels.hip, next_model/model2D.py:84-210)
+struct NextPbParams {
+    int B, dim, iters;                    // problems, 2 / 3, LSTM rounds
+    const float *maps, *goals;            // [B, 15, 15], [B, dim]
+    const float* weights;                 // next_weights_floats() packed floats
+    float* pb_rep;                        // out [B, 64, 15, 15]
+};
+struct NextStateParams {
+    int S, B, dim;                        // states, problems, 2 / 3
+    const float* states;                  // [S, dim]
+    const int* problem_of_state;          // [S]
+    const float *pb_rep, *weights;        // [B, 64, 15, 15]
+    float* y;                             // out [S, dim + 1]
+    int* status;                          // [2], accumulated: rows outside [0, B), last such row + 1
+};
+hipError_t launch_next_pb_forward(const NextPbParams& p, hipStream_t st);
+hipError_t launch_next_state_forward(const NextStateParams& p, hipStream_t st);
+size_t next_weights_floats();
+
 // ---- the BIT* baseline on maze problems (bitstar_kernels.hip, algorithm/bit_star.py:18-334)
 struct BitSampleParams {
     int B, w, batch, n_batches, rows, dim;   // problems, map width, free draws a batch, batches, pool rows a problem, 2 / 3

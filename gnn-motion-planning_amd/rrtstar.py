@@ -83,6 +83,57 @@ def distances(states, to_state, dim):
     return np.sqrt(np.sum(gap ** 2, axis=-1))
 
 
+def rewire_last(env, goal, states, rewired, freesp, in_goal, costs, path_lengths, nearest, stats):
+    """``RRTS_rewire_last`` (tsa.py:222-281) on the tree lists, whose last entries are the node just inserted from ``nearest``:
+    sets its cost (and ``path_lengths[-1]`` when it is in the goal region), rewires it and then its neighbours, in place.
+    ``stats`` counts as :func:`plan_host` describes."""
+    dim = env.config_dim
+    new_state, free = states[-1], freesp[-1]
+
+    def rewire_step(j):                      # env.step(cur_tree[j], new_state) inside RRTS_rewire_last
+        if dim == 3:
+            stats['max_rewire_k'] = max(stats['max_rewire_k'], int(distances(states[j], new_state, dim)[0] / 0.015))
+        _, free_j, _ = env.step(states[j], new_state)
+        if free_j and distances(new_state, goal, dim)[0] < RRT_EPS:
+            stats['goal_rechecks'] += 1
+        return free_j
+
+    if not free:
+        costs[-1] = float(OBS_COST)
+        return
+    tree = np.array(states[:-1])
+    dists = distances(tree, new_state, dim)
+    near = np.flatnonzero(dists < NEIGHBOR_R)
+    n_coll = int(sum(not freesp[j] for j in near))
+    stats['max_near'] = max(stats['max_near'], len(near))
+    if len(near) > 64:
+        stats['max_near_collided'] = max(stats['max_near_collided'], n_coll)
+    min_cost, min_j = dists[nearest] + costs[nearest], nearest
+    for j in near:
+        if not freesp[j]:
+            continue
+        cost_new = dists[j] + costs[j]
+        if cost_new < min_cost and rewire_step(j):
+            min_cost, min_j = cost_new, int(j)
+    rewired[-1] = min_j
+    costs[-1] = float(min_cost)
+    if in_goal[-1] and (path_lengths[-1] < 0 or path_lengths[-1] > min_cost):      # set_cost (search_tree.py:56-63)
+        path_lengths[-1] = float(min_cost)
+    for j in near:
+        cost_new = min_cost + dists[j]
+        if cost_new < costs[j]:
+            if not freesp[j]:
+                stats['collided_second_pass'] += 1
+            if rewire_step(j):
+                costs[j] = float(cost_new)
+                rewired[j] = len(states) - 1
+                stats['rewired'] += 1
+
+
+def new_stats():
+    return dict(direct_steer=0, collided_second_pass=0, goal_rechecks=0, rewired=0, max_near=0, max_near_collided=0, max_rewire_k=0)
+
+
 def plan_host(problem, seed, t_max=1000, stop_when_success=True):
     """``np.random.seed(seed); NEXT_plan(env, model=None, T=t_max, g_explore_eps=1., stop_when_success=...)`` for one maze
     problem (a dict with ``map``, ``init_state``, ``goal_state``; 2 coordinates = point robot, 3 = stick robot) on a private
@@ -103,17 +154,8 @@ def plan_host(problem, seed, t_max=1000, stop_when_success=True):
     # search_tree.py:5-19
     states = [np.asarray(env.init_state, dtype=np.float64).reshape(dim).copy()]
     parents, rewired, freesp, in_goal, costs, path_lengths, cum = [-1], [-1], [True], [False], [0.], [-1.], [0]
-    stats = dict(direct_steer=0, collided_second_pass=0, goal_rechecks=0, rewired=0, max_near=0, max_near_collided=0, max_rewire_k=0)
+    stats = new_stats()
     pos, success, i = 0, False, -1
-
-    def rewire_step(j, new_state):           # env.step(cur_tree[j], new_state) inside RRTS_rewire_last
-        before = env.collision_check_count
-        if dim == 3:
-            stats['max_rewire_k'] = max(stats['max_rewire_k'], int(distances(states[j], new_state, dim)[0] / 0.015))
-        _, free, _ = env.step(states[j], new_state)
-        if free and distances(new_state, goal, dim)[0] < RRT_EPS:
-            stats['goal_rechecks'] += 1
-        return free, env.collision_check_count - before
 
     for i in range(int(t_max)):
         sample, pos = next_sample(raw, pos, goal, low, ranges)
@@ -137,37 +179,7 @@ def plan_host(problem, seed, t_max=1000, stop_when_success=True):
         in_goal.append(bool(done))
         path_lengths.append(path_lengths[-1])
         costs.append(-1.)
-        # RRTS_rewire_last (tsa.py:233-281)
-        if not free:
-            costs[-1] = float(OBS_COST)
-        else:
-            tree = np.array(states[:-1])
-            dists = distances(tree, new_state, dim)
-            near = np.flatnonzero(dists < NEIGHBOR_R)
-            n_coll = int(sum(not freesp[j] for j in near))
-            stats['max_near'] = max(stats['max_near'], len(near))
-            if len(near) > 64:
-                stats['max_near_collided'] = max(stats['max_near_collided'], n_coll)
-            min_cost, min_j = dists[nearest] + costs[nearest], nearest
-            for j in near:
-                if not freesp[j]:
-                    continue
-                cost_new = dists[j] + costs[j]
-                if cost_new < min_cost and rewire_step(j, new_state)[0]:
-                    min_cost, min_j = cost_new, int(j)
-            rewired[-1] = min_j
-            costs[-1] = float(min_cost)
-            if in_goal[-1] and (path_lengths[-1] < 0 or path_lengths[-1] > min_cost):      # set_cost (search_tree.py:56-63)
-                path_lengths[-1] = float(min_cost)
-            for j in near:
-                cost_new = min_cost + dists[j]
-                if cost_new < costs[j]:
-                    if not freesp[j]:
-                        stats['collided_second_pass'] += 1
-                    if rewire_step(j, new_state)[0]:
-                        costs[j] = float(cost_new)
-                        rewired[j] = len(states) - 1
-                        stats['rewired'] += 1
+        rewire_last(env, goal, states, rewired, freesp, in_goal, costs, path_lengths, nearest, stats)
         cum.append(int(env.collision_check_count))
         if success and stop_when_success:
             break

@@ -16,6 +16,8 @@
  *   gnnmp_explorer_forward_ex / gnnmp_smoother_forward_ex, gnnmp_*_status*          (ABI 4 / ABI 3)
  *       no counterpart: what the reference reports by raising (a node id outside the graph: tensor indexing, model.py:120) or does
  *       not have at all (it attends over ALL obstacles it is given, model.py:125-130), reported without synchronising the forward
+ *   gnnmp_next_weights_floats / gnnmp_next_pb_forward / gnnmp_next_state_forward      (ABI 8)
+ *       PPN.pb_forward / PPN.state_forward, batched           next_model/model2D.py:151-210 (calls model2D.py:244, 254)
  *   gnnmp_graph_workspace_bytes / gnnmp_graph_build
  *       create_data's edge construction                       eval_gnn.py:159-164
  *   gnnmp_maze_sample
@@ -887,6 +889,53 @@ int gnnmp_bitstar_lds_nodes(void);
  * edge_cap outside [1, n_nodes * (n_nodes - 1)], flags beyond bit 0), GNNMP_ERR_WORKSPACE (too small or misaligned). */
 int gnnmp_bitstar_plan(const gnnmp_bitstar_batch* batch, const gnnmp_bitstar_result* result, void* workspace,
                        size_t workspace_bytes, void* hip_stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The NEXT planning network on maze problems (ABI 8) -- the PPN of next_model/model2D.py:84-210 with env_width 15,
+ * cap = g = 8, latent 64; dim 2 = point robot (next_2), 3 = stick robot (next_3).  Batched over problems and over states:
+ *   gnnmp_next_pb_forward      pb_rep of B problems: the goal attention (1 x 1-conv MLP 4-16-16-32-32-64-1 over the 225 cells,
+ *                              softmax over cells, times softmax(dim-64-8 MLP)), hidden (3 x 3, 9 -> 64), h0 / c0 (3 x 3, 64 -> 64)
+ *                              and `iters` rounds of { conv 3 x 3 64 -> 64 on h; LSTMCell(64, 64) per cell }, in exact fp32 MFMA
+ *   gnnmp_next_state_forward   y = [action mean, value] of S states, each read out of its problem's pb_rep through the state
+ *                              attention, the sum over cells and cap (accumulated in double) and the policy MLP 8-128-64-(dim+1)
+ * The last coordinate of every goal and state is divided by 0.4 (LIMITS[2]) in float32 first; for dim 2 that is y, and the 2-D
+ * attention sees the divided y.  Cell (row i, column j) enters the attention as [s0, s1, j, i].  Both calls run on hip_stream
+ * and do not synchronise or allocate; results are bit-identical from run to run.
+ *
+ * Packed weights (gnnmp_next_weights_floats floats, the same count for both dim; gnnmp.next_model.pack_weights writes them):
+ * the attention's six shared layers as [out][in] weight then bias (the last bias padded to 4 floats), its dim-64-8 MLP (first
+ * layer [64][3], column 2 zero for dim 2), the policy MLP (last layer padded to [4][64] + 4), then hidden / h0 / c0 / conv as
+ * [9 taps x (cin padded to 16s) / 16][4 column tiles][64 lanes][4 steps] + 64 biases and the LSTM as [8][16][64][4] over
+ * K = [input 64 | hidden 64], N = the 256 gate rows, + 256 summed biases: element (k group, tile, lane, step) is
+ * weight[k = 16 group + 4 (lane / 16) + step][n = 16 tile + lane % 16].
+ * ---------------------------------------------------------------------------------------- */
+typedef struct {
+    int32_t n_problems, dim, width;      /* B >= 0 (0: nothing is done); dim 2 / 3; width must be 15                      */
+    int32_t iters;                       /* LSTM rounds >= 0; the reference runs 20; 0 returns h0                         */
+    const float* maps;                   /* [B, 15, 15]  0 = free                                                          */
+    const float* goals;                  /* [B, dim]                                                                       */
+    const float* weights;                /* packed, see above                                                              */
+    float* pb_rep;                       /* out [B, 64, 15, 15]: pb_forward(...) viewed as [B, g * cap, H, W], c = 8 g + cap */
+} gnnmp_next_pb;
+
+typedef struct {
+    int32_t n_states, n_problems, dim, width;   /* S >= 0 (0: nothing is done), B >= 0, dim 2 / 3, width must be 15        */
+    const float* states;                 /* [S, dim]                                                                       */
+    const int32_t* problem_of_state;     /* [S]  any order, repeats allowed                                                */
+    const float* pb_rep;                 /* [B, 64, 15, 15]                                                                */
+    const float* weights;                /* packed, see above                                                              */
+    float* y;                            /* out [S, dim + 1]: the action mean, then the value                              */
+    int32_t* status;                     /* [2] device-writable, ACCUMULATED (zero it first): [0] += states whose
+                                          * problem_of_state is outside [0, B) -- such a row reads no pb_rep, is not clamped and
+                                          * gets NaN in y; the other rows are unaffected -- [1] = max(last such row + 1)       */
+} gnnmp_next_states;
+
+/* GNNMP_ERR_NULL (n_floats), GNNMP_ERR_DIMS (dim not 2 / 3). */
+int gnnmp_next_weights_floats(int32_t dim, size_t* n_floats);
+/* All argument errors come back before anything is launched, in this order: GNNMP_ERR_NULL (the struct), GNNMP_ERR_DIMS (dim not
+ * 2 / 3, width not 15), GNNMP_ERR_ARG (n_problems / n_states < 0, iters < 0), GNNMP_ERR_NULL (an array). */
+int gnnmp_next_pb_forward(const gnnmp_next_pb* desc, void* hip_stream);
+int gnnmp_next_state_forward(const gnnmp_next_states* desc, void* hip_stream);
 
 /* ------------------------------------------------------------------------------------------
  * Supervision of the explorer's training step (train_explorer.py:124-176): edge labels, shortest paths to the goal,
