@@ -6,7 +6,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('GNNMP_LIB') or os.path.join(_HERE, 'libgnnmp.so')      # GNNMP_LIB: an experiment build (tools/diag/build_variant.sh)
 
-ABI_VERSION = 8                        # include/gnnmp.h gnnmp_abi_version(): what this binding was written against
+ABI_VERSION = 9                        # include/gnnmp.h gnnmp_abi_version(): what this binding was written against
 
 c_float_p = ctypes.POINTER(ctypes.c_float)
 c_int32_p = ctypes.POINTER(ctypes.c_int32)
@@ -125,6 +125,17 @@ class NextStateForward(ctypes.Structure):
     _fields_ = [('n_states', ctypes.c_int32), ('n_problems', ctypes.c_int32), ('dim', ctypes.c_int32), ('width', ctypes.c_int32),
                 ('states', ctypes.c_void_p), ('problem_of_state', ctypes.c_void_p), ('pb_rep', ctypes.c_void_p),
                 ('weights', ctypes.c_void_p), ('y', ctypes.c_void_p), ('status', ctypes.c_void_p)]
+
+
+class NextPlanBatch(ctypes.Structure):
+    _fields_ = RRTStarBatch._fields_ + [('g_explore_eps', ctypes.c_double), ('c', ctypes.c_double), ('k', ctypes.c_int32),
+                                        ('eps_rows', ctypes.c_int32), ('scale', ctypes.c_float), ('pb_rep', ctypes.c_void_p),
+                                        ('weights', ctypes.c_void_p), ('eps', ctypes.c_void_p)]
+
+
+class NextPlanTree(ctypes.Structure):
+    _fields_ = RRTStarTree._fields_ + [('expanded_by_rrt', ctypes.c_void_p), ('state_values', ctypes.c_void_p), ('w', ctypes.c_void_p),
+                                       ('visits', ctypes.c_void_p), ('w_sum', ctypes.c_void_p), ('guided', ctypes.c_void_p)]
 
 
 class MtUniformBatch(ctypes.Structure):
@@ -270,6 +281,8 @@ def lib():
     L.gnnmp_next_weights_floats.argtypes = [ctypes.c_int32, ctypes.POINTER(sz)]
     L.gnnmp_next_pb_forward.argtypes = [ctypes.POINTER(NextPbForward), vp]
     L.gnnmp_next_state_forward.argtypes = [ctypes.POINTER(NextStateForward), vp]
+    L.gnnmp_next_plan_max_nodes.argtypes = []
+    L.gnnmp_next_plan.argtypes = [ctypes.POINTER(NextPlanBatch), ctypes.POINTER(NextPlanTree), vp]
     L.gnnmp_maze_steer.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, vp, vp, vp, vp, vp, vp, vp, vp]
     L.gnnmp_stick_steer.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.gnnmp_episode_label_maze.argtypes = [ctypes.POINTER(EpisodeGraphs), ctypes.c_int32, ctypes.c_int32, vp, vp, vp, vp, vp]

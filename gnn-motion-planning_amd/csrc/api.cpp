@@ -248,7 +248,7 @@ extern "C" const char* gnnmp_status_string(int s) {
 }
 extern "C" const char* gnnmp_last_hip_error(void) { return g_hip_error.c_str(); }
 // 2: stage list of gnnmp_explorer_profile_read (fused message passing); 3: device-side status words (gnnmp_*_status*)
-extern "C" int gnnmp_abi_version(void) { return 8; }
+extern "C" int gnnmp_abi_version(void) { return 9; }
 
 // ---------------------------------------------------------------------------------------------
 // explorer handle
@@ -1975,6 +1975,40 @@ extern "C" int gnnmp_next_state_forward(const gnnmp_next_states* d, void* hip_st
     p.states = d->states; p.problem_of_state = d->problem_of_state; p.pb_rep = d->pb_rep; p.weights = d->weights; p.y = d->y;
     p.status = d->status;
     HIP_TRY(launch_next_state_forward(p, static_cast<hipStream_t>(hip_stream)));
+    return GNNMP_OK;
+}
+
+// =============================================================================================
+// NEXT's guided tree loop on maze problems (next_plan_kernels.hip; algorithm/tsa.py:12-81, 141-220)
+// =============================================================================================
+extern "C" int gnnmp_next_plan_max_nodes(void) { return next_plan_max_nodes(); }
+
+extern "C" int gnnmp_next_plan(const gnnmp_next_plan_batch* b, const gnnmp_next_plan_tree* t, void* hip_stream) {
+    if (!b || !t) return GNNMP_ERR_NULL;
+    if (b->dim != 2 && b->dim != 3) return GNNMP_ERR_DIMS;
+    if (b->width != 15) return GNNMP_ERR_DIMS;
+    if (!b->maps || !b->init_states || !b->goal_states || !b->draws || !b->pb_rep || !b->weights || !b->eps) return GNNMP_ERR_NULL;
+    if (!t->states || !t->parents || !t->rewired_parents || !t->flags || !t->costs || !t->path_lengths || !t->cumulated_checks ||
+        !t->path || !t->n_nodes || !t->success || !t->last_iter || !t->used || !t->path_len || !t->status || !t->expanded_by_rrt ||
+        !t->state_values || !t->w || !t->visits || !t->w_sum || !t->guided)
+        return GNNMP_ERR_NULL;
+    if (b->n_problems < 1 || b->t_max < 1 || (long long)b->t_max + 1 > next_plan_max_nodes()) return GNNMP_ERR_ARG;
+    if (b->k < 1 || b->k > 16 || b->eps_rows < 1) return GNNMP_ERR_ARG;
+    if (b->draws_per_problem < 2 + b->dim || b->draws_per_problem > INT32_MAX) return GNNMP_ERR_ARG;      // one iteration at least
+    NextPlanParams p;
+    p.t.B = b->n_problems; p.t.w = b->width; p.t.t_max = b->t_max; p.t.stop = b->stop_when_success ? 1 : 0; p.t.dim = b->dim;
+    p.t.draw_len = b->draws_per_problem;
+    p.t.maps = b->maps; p.t.init_states = b->init_states; p.t.goal_states = b->goal_states; p.t.draws = b->draws;
+    p.t.states = t->states; p.t.parents = t->parents; p.t.rewired = t->rewired_parents; p.t.flags = t->flags; p.t.costs = t->costs;
+    p.t.path_lengths = t->path_lengths; p.t.cum_checks = reinterpret_cast<long long*>(t->cumulated_checks); p.t.path = t->path;
+    p.t.n_nodes = t->n_nodes; p.t.success = t->success; p.t.last_iter = t->last_iter; p.t.used = t->used; p.t.path_len = t->path_len;
+    p.t.status = t->status;
+    p.t.ws_x = p.t.ws_y = p.t.ws_z = p.t.ws_c = nullptr; p.t.ws_f = nullptr;
+    p.g_explore_eps = b->g_explore_eps; p.c = b->c; p.k = b->k; p.eps_rows = b->eps_rows; p.scale = b->scale;
+    p.pb_rep = b->pb_rep; p.weights = b->weights; p.eps = b->eps;
+    p.by_rrt = t->expanded_by_rrt; p.state_values = t->state_values; p.w = t->w; p.visits = t->visits; p.w_sum = t->w_sum;
+    p.guided = t->guided;
+    HIP_TRY(launch_next_plan(p, static_cast<hipStream_t>(hip_stream)));
     return GNNMP_OK;
 }
 

@@ -354,6 +354,24 @@ hipError_t launch_next_pb_forward(const NextPbParams& p, hipStream_t st);
 hipError_t launch_next_state_forward(const NextStateParams& p, hipStream_t st);
 size_t next_weights_floats();
 
+// ---- NEXT's guided tree loop on maze problems (next_plan_kernels.hip, algorithm/tsa.py:12-81, 141-220)
+struct NextPlanParams {
+    RrtParams t;                          // the RRT* fields (the workspace pointers are unused: the node state lives in LDS)
+    double g_explore_eps, c;              // the RRT branch's share of the non-goal iterations; the exploration weight of the scores
+    int k, eps_rows;                      // candidates of a guided step (1 .. 16); rows of eps per problem
+    float scale;                          // diagonal of the Cholesky factor of the policy's covariance
+    const float *pb_rep, *weights;        // [B, 64, 15, 15], next_weights_floats() packed floats
+    const float* eps;                     // [B, eps_rows, k, dim] standard normal draws
+    signed char* by_rrt;                  // out [B, t_max + 1]: 1 RRT branch, 0 guided, -1 the root
+    float* state_values;                  // out [B, t_max + 1]
+    double* w;                            // out [B, t_max + 1]
+    int* visits;                          // out [B, t_max + 1]
+    double* w_sum;                        // out [B]
+    int* guided;                          // out [B]: rows of eps used
+};
+hipError_t launch_next_plan(const NextPlanParams& p, hipStream_t st);
+int next_plan_max_nodes();
+
 // ---- the BIT* baseline on maze problems (bitstar_kernels.hip, algorithm/bit_star.py:18-334)
 struct BitSampleParams {
     int B, w, batch, n_batches, rows, dim;   // problems, map width, free draws a batch, batches, pool rows a problem, 2 / 3

@@ -26,6 +26,7 @@
 #include <math.h>
 #include "kernels.hpp"
 #include "maze_f64.hpp"
+#include "rrt_tree.hpp"
 
 // numpy rounds every float64 operation on its own
 #pragma clang fp contract(off)
@@ -35,49 +36,6 @@ namespace gnnmp {
 namespace {
 
 constexpr int kRrtLdsNodes = 1024;       // t_max + 1 <= this: 33 KB (stick) of node state per wave next to the 4 KB map
-constexpr double kRrtEps = 5e-2;         // env_config.py RRT_EPS: steering step and goal radius
-constexpr double kRrtModelEps = 0.05;    // tsa.py:13 model_eps
-constexpr double kRrtNearR = 5e-2 * 3;   // tsa.py:234 env.RRT_EPS * 3, rounded as Python rounds it
-constexpr double kRrtObsCost = 2.0;      // tsa.py:222 obs_cost
-constexpr unsigned char kRrtFree = 1, kRrtGoal = 2;
-
-// env.distance: |b - a| per coordinate, the orientation gap the short way round, sqrt((dx^2 + dy^2) + dz^2)
-template <int DIM>
-__device__ __forceinline__ double rrt_dist(const double* a, const double* b) {
-    const double a0 = fabs(b[0] - a[0]), a1 = fabs(b[1] - a[1]);
-    double s = a0 * a0 + a1 * a1;
-    if (DIM == 3) {
-        double a2 = fabs(b[2] - a[2]);
-        const double w2 = fabs(a2 - 0.8);
-        a2 = w2 < a2 ? w2 : a2;                                  // np.min((d, |d - 0.8|))
-        s = s + a2 * a2;
-    }
-    return sqrt(s);
-}
-__device__ __forceinline__ double rrt_wrap(double z) {           // maze_env.py:155-159: one period back into [-0.4, 0.4]
-    if (fabs(z) > 0.4) z = z > 0.0 ? z - 0.8 : z + 0.8;
-    return z;
-}
-// env.step(s, new_state = t) by all 64 lanes, s and t the same in every lane (t already clipped and wrapped): -> no_collision,
-// the same in every lane; `checks` grows by what the call counts, the goal test of a free edge included.
-template <int DIM>
-__device__ __forceinline__ bool rrt_step(const LspMaze& m, int lane, const double* s, const double* t, bool near_goal, long long& checks) {
-    bool fr;
-    if (DIM == 2) {
-        int cnt = 0;
-        fr = lsp_edge2(m, s[0], s[1], t[0], t[1], cnt);
-        if (fr && near_goal) lsp_point(m, t[0], t[1], cnt);
-        checks += cnt;
-    } else {
-        fr = lsp_stick_edge_wave(m, lane, s, t, checks);
-        if (fr && near_goal) {
-            int cnt = 0;
-            lsp_stick(m, t[0], t[1], t[2], cnt);
-            checks += cnt;
-        }
-    }
-    return fr;
-}
 
 template <bool LDS, int DIM>
 __device__ __forceinline__ void rrt_body(const RrtParams& p, double* s_x, double* s_y, double* s_z, double* s_c, unsigned char* s_f,
@@ -108,10 +66,7 @@ __device__ __forceinline__ void rrt_body(const RrtParams& p, double* s_x, double
         parents[0] = -1; rewired[0] = -1; plen_out[0] = -1.0; cum[0] = 0;
     }
     lsp_sync();
-    auto node = [&](int j, double* out) {
-        out[0] = nx[j]; out[1] = ny[j];
-        if (DIM == 3) out[2] = nz[j];
-    };
+    const RrtNodes<DIM> tree{nx, ny, nz, nc, nf};
     int n = 1, status = 0, last_i = -1;
     long long checks = 0, pos = 0;
     bool success = false;
@@ -131,34 +86,12 @@ __device__ __forceinline__ void rrt_body(const RrtParams& p, double* s_x, double
             if (DIM == 3) smp[2] = -0.4 + 0.8 * draws[pos + 4];
             pos += 2 + DIM;
         }
-        // ---- nearest non-terminal node
-        unsigned long long best = ~0ull;
-        int bi = 0x7fffffff;
-        for (int j = lane; j < n; j += 64) {
-            if (nf[j] != kRrtFree) continue;
-            double q[3];
-            node(j, q);
-            const unsigned long long k = (unsigned long long)__double_as_longlong(rrt_dist<DIM>(q, smp));      // d >= 0: bit order
-            if (k < best) { best = k; bi = j; }                  // ascending ids: the first strict minimum
-        }
-        const unsigned long long wmin = lsp_wave_min_u64(best);
-        const int ni = (int)lsp_wave_min_u64(best == wmin ? (unsigned long long)(unsigned)bi : ~0ull);
-        const double dmin = __longlong_as_double((long long)wmin);
-        double near[3], nw[3] = {0.0, 0.0, 0.0};
-        node(ni, near);
-        // ---- RRT_steer, then step's clip and wrap
-        if (dmin < kRrtEps) {
-#pragma unroll
-            for (int c = 0; c < DIM; ++c) nw[c] = smp[c];
-        } else {
-            const double ratio = kRrtEps / dmin;
-            nw[0] = near[0] + (smp[0] - near[0]) * ratio;
-            nw[1] = near[1] + (smp[1] - near[1]) * ratio;
-            if (DIM == 3) nw[2] = rrt_wrap(near[2] + rrt_wrap(smp[2] - near[2]) * ratio);
-        }
-        nw[0] = fmin(fmax(nw[0], -1.0), 1.0);
-        nw[1] = fmin(fmax(nw[1], -1.0), 1.0);
-        if (DIM == 3) nw[2] = rrt_wrap(nw[2]);
+        // ---- nearest non-terminal node, RRT_steer, then step's clip and wrap
+        double dmin, near[3], nw[3] = {0.0, 0.0, 0.0};
+        const int ni = rrt_nearest<DIM>(tree, n, lane, smp, dmin);
+        tree.get(ni, near);
+        rrt_steer<DIM>(near, smp, dmin, nw);
+        rrt_clip<DIM>(nw);
         const bool near_goal = rrt_dist<DIM>(nw, goal) < kRrtEps;
         const bool fr = rrt_step<DIM>(m, lane, near, nw, near_goal, checks);
         const bool done = fr && near_goal;                       // (_state_fp(new) holds: the free edge checked it)
@@ -171,63 +104,7 @@ __device__ __forceinline__ void rrt_body(const RrtParams& p, double* s_x, double
             nc[n] = kRrtObsCost;                                 // a collided node's cost; a free one's is set below
             parents[n] = ni; rewired[n] = ni;
         }
-        if (fr) {
-            // ---- RRTS_rewire_last, pass 1: the cheapest free neighbour with a free edge becomes the parent
-            double min_cost = rrt_dist<DIM>(near, nw) + nc[ni];
-            int min_j = ni;
-            for (int base = 0; base < n; base += 64) {
-                const int j = base + lane;
-                bool cand = false;
-                if (j < n && (nf[j] & kRrtFree)) {
-                    double q[3];
-                    node(j, q);
-                    const double d = rrt_dist<DIM>(q, nw);
-                    cand = d < kRrtNearR && d + nc[j] < min_cost;
-                }
-                unsigned long long todo = __builtin_amdgcn_ballot_w64(cand);
-                while (todo) {                                   // at most 64 bits, lowest index first
-                    const int jj = base + __builtin_ctzll(todo);
-                    todo &= todo - 1;
-                    double q[3];
-                    node(jj, q);
-                    const double cost_new = rrt_dist<DIM>(q, nw) + nc[jj];
-                    if (cost_new < min_cost && rrt_step<DIM>(m, lane, q, nw, near_goal, checks)) { min_cost = cost_new; min_j = jj; }
-                }
-            }
-            if (done && (plen < 0.0 || plen > min_cost)) plen = min_cost;      // set_cost (search_tree.py:56-63)
-            // ---- pass 2: every near node the new one improves, collided ones included
-            for (int base = 0; base < n; base += 64) {
-                const int j = base + lane;
-                bool cand = false;
-                double q[3] = {0.0, 0.0, 0.0}, cost_new = 0.0;
-                if (j < n) {
-                    node(j, q);
-                    const double d = rrt_dist<DIM>(q, nw);
-                    cost_new = min_cost + d;
-                    cand = d < kRrtNearR && cost_new < nc[j];
-                }
-                if (DIM == 2) {
-                    int cnt = 0;
-                    if (cand) {
-                        const bool ok = lsp_edge2(m, q[0], q[1], nw[0], nw[1], cnt);
-                        if (ok && near_goal) lsp_point(m, nw[0], nw[1], cnt);
-                        if (ok) { nc[j] = cost_new; rewired[j] = n; }
-                    }
-                    checks += lsp_wave_sum(cnt);
-                } else {
-                    unsigned long long todo = __builtin_amdgcn_ballot_w64(cand);
-                    while (todo) {
-                        const int src = __builtin_ctzll(todo), jj = base + src;
-                        todo &= todo - 1;
-                        double qq[3];
-                        node(jj, qq);
-                        const bool ok = rrt_step<DIM>(m, lane, qq, nw, near_goal, checks);
-                        if (ok && lane == src) { nc[j] = cost_new; rewired[j] = n; }
-                    }
-                }
-            }
-            if (lane == 0) { nc[n] = min_cost; rewired[n] = min_j; }
-        }
+        if (fr) rrt_rewire<DIM>(m, lane, tree, rewired, n, ni, near, nw, near_goal, done, plen, checks);      // RRTS_rewire_last
         if (lane == 0) { plen_out[n] = plen; cum[n] = checks; }
         ++n;
         last_i = it;
@@ -244,20 +121,9 @@ __device__ __forceinline__ void rrt_body(const RrtParams& p, double* s_x, double
         p.flags[row + j] = nf[j];
     }
     if (lane == 0) {
-        int L = 0;
-        if (nf[n - 1] & kRrtGoal) {
-            int cur = n - 1;
-            L = 1;
-            while (cur != 0 && L <= n) {
-                cur = rewired[cur];
-                if (cur < 0 || cur >= n) { L = n + 1; break; }
-                ++L;
-            }
-            if (L > n) { status |= 2; L = 0; }                   // a cycle: the reference would not return
-            int* path = p.path + row;
-            cur = n - 1;
-            for (int k = L - 1; k >= 0; --k) { path[k] = cur; cur = rewired[cur]; }
-        }
+        bool cycle;
+        const int L = rrt_path(nf, rewired, n, p.path + row, cycle);
+        if (cycle) status |= 2;                                  // the reference would not return
         p.n_nodes[b] = n;
         p.success[b] = success ? 1 : 0;
         p.last_iter[b] = last_i;

@@ -18,6 +18,8 @@
  *       not have at all (it attends over ALL obstacles it is given, model.py:125-130), reported without synchronising the forward
  *   gnnmp_next_weights_floats / gnnmp_next_pb_forward / gnnmp_next_state_forward      (ABI 8)
  *       PPN.pb_forward / PPN.state_forward, batched           next_model/model2D.py:151-210 (calls model2D.py:244, 254)
+ *   gnnmp_next_plan / gnnmp_next_plan_max_nodes                                       (ABI 9)
+ *       NEXT_plan with a model, batched, one launch            algorithm/tsa.py:12-81, 141-220 (call eval_next.py:65)
  *   gnnmp_graph_workspace_bytes / gnnmp_graph_build
  *       create_data's edge construction                       eval_gnn.py:159-164
  *   gnnmp_maze_sample
@@ -936,6 +938,80 @@ int gnnmp_next_weights_floats(int32_t dim, size_t* n_floats);
  * 2 / 3, width not 15), GNNMP_ERR_ARG (n_problems / n_states < 0, iters < 0), GNNMP_ERR_NULL (an array). */
 int gnnmp_next_pb_forward(const gnnmp_next_pb* desc, void* hip_stream);
 int gnnmp_next_state_forward(const gnnmp_next_states* desc, void* hip_stream);
+
+/* ------------------------------------------------------------------------------------------
+ * NEXT's guided planner on maze problems (ABI 9) -- eval_next.py's NEXT_plan(env, model, T=t_max, g_explore_eps=0.1,
+ * stop_when_success, c=1, k=10) (algorithm/tsa.py:12-81, 141-220 over algorithm/search_tree.py) as
+ * gnnmp.next_plan.plan_host restates it -- batched, every problem on its own streams, the whole t_max loop of all problems in
+ * ONE launch, one workgroup of 256 threads per problem.  It is gnnmp_rrtstar_plan's iteration plus the branch a model adds.
+ * Per iteration the raw double r0 is read: r0 < 0.05 -> the sample is the goal state (1 double); else r1 is read and
+ * r1 < g_explore_eps -> the RRT step (2 + dim doubles, as gnnmp_rrtstar_plan); else the guided step (2 doubles):
+ *   - select: the first maximum over the non-terminal nodes of (double)state_value + c * sqrt(log(w_sum) / w);
+ *   - one network evaluation of that parent gives the action mean; the k actions are fl32(mean + fl32(scale * eps[g][j])) --
+ *     two float32 roundings -- with g the problem's count of guided iterations so far;
+ *   - candidates parent + (double)action, x and y clipped to +-1, the angle wrapped, no collision check; k network
+ *     evaluations give their values Q_j, w_j = w(candidate) over the tree as it stands; the first maximum of
+ *     (double)Q_j + c * sqrt(log(w_sum) / w_j) is stepped to with the counted env.step(parent, candidate).  k = 1 takes the
+ *     only candidate without evaluating it.
+ * Insertion, both branches: one network evaluation of the new state (its value), visits[parent] += 1, w_sum -= w[parent],
+ * w[parent] recomputed over the tree INCLUDING the new state, w_sum += w[parent], w[new] over the same tree, w_sum += w[new]
+ * (three separately rounded operations), then RRTS_rewire_last.  w(s) = sum over the nodes of max(exp(-(dist / 0.05)^2), 1e-3)
+ * in double, in a fixed order.  A network evaluation has the bits gnnmp_next_state_forward gives for the float32 state.
+ * UCB_type 'GP' and Model3D (the arm families) are not built.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct {
+    int32_t n_problems, dim, width;      /* dim 2 = point robot, 3 = stick robot; width must be 15                      */
+    int32_t t_max, stop_when_success;    /* NEXT_plan's T, t_max + 1 <= gnnmp_next_plan_max_nodes(); non-zero: the loop ends
+                                          * with the first node in the goal region                                      */
+    int64_t draws_per_problem;           /* doubles in a problem's block; t_max * (2 + dim) always suffices             */
+    const double* maps;                  /* [B, 15, 15]  0 = free                                                       */
+    const double* init_states;           /* [B, dim]                                                                    */
+    const double* goal_states;           /* [B, dim]                                                                    */
+    const double* draws;                 /* [B, draws_per_problem]  the RAW doubles of [0, 1) of the problem's generator  */
+    double g_explore_eps;                /* the reference runs 0.1                                                      */
+    double c;                            /* exploration weight of both scores; the reference runs 1                     */
+    int32_t k;                           /* candidates of a guided step, 1 .. 16; the reference runs 10                 */
+    int32_t eps_rows;                    /* rows of eps per problem, >= 1; t_max always suffices                        */
+    float scale;                         /* float32 diagonal of the Cholesky factor of eye * std^2: 0.015f at the default std */
+    const float* pb_rep;                 /* [B, 64, 15, 15]  gnnmp_next_pb_forward's                                    */
+    const float* weights;                /* packed, gnnmp_next_weights_floats floats                                    */
+    const float* eps;                    /* [B, eps_rows, k, dim]  standard normal draws; row g feeds the problem's g-th
+                                          * guided iteration                                                            */
+} gnnmp_next_plan_batch;
+
+typedef struct {                         /* all out; rows of a problem behind its n_nodes are left as they were         */
+    double* states;                      /* [B, t_max + 1, dim]  as gnnmp_rrtstar_tree, down to status                  */
+    int32_t* parents;
+    int32_t* rewired_parents;
+    uint8_t* flags;
+    double* costs;
+    double* path_lengths;
+    int64_t* cumulated_checks;
+    int32_t* path;
+    int32_t* n_nodes;
+    int32_t* success;
+    int32_t* last_iter;
+    int32_t* used;
+    int32_t* path_len;
+    int32_t* status;                     /* [B]  0, or bits: 1 and 2 as gnnmp_rrtstar_tree; 4 = the eps block ended before a
+                                          * guided iteration (the tree holds the iterations before it; nothing is read beyond
+                                          * the block); 8 = a score was not finite.  Any of 1, 4, 8 ends the problem        */
+    int8_t* expanded_by_rrt;             /* [B, t_max + 1]  1 = goal or RRT step, 0 = guided step, -1 for the root       */
+    float* state_values;                 /* [B, t_max + 1]  the network's value of every node                            */
+    double* w;                           /* [B, t_max + 1]                                                               */
+    int32_t* visits;                     /* [B, t_max + 1]  1 for the root plus one per child                            */
+    double* w_sum;                       /* [B]                                                                          */
+    int32_t* guided;                     /* [B]  guided iterations run = rows of eps used                                */
+} gnnmp_next_plan_tree;
+
+/* Trees are capped at this many nodes (t_max + 1): the node state lives in LDS next to the problem's pb_rep. */
+int gnnmp_next_plan_max_nodes(void);
+
+/* One launch on hip_stream: no allocation, no synchronisation, no atomics, deterministic (w included).  All argument errors
+ * come back before anything is launched: GNNMP_ERR_NULL (a NULL struct or array), GNNMP_ERR_DIMS (dim not 2 / 3, width not
+ * 15), GNNMP_ERR_ARG (n_problems / t_max < 1, t_max + 1 above gnnmp_next_plan_max_nodes(), k outside 1 .. 16, eps_rows < 1,
+ * draws_per_problem < 2 + dim -- shorter than one iteration -- or beyond 2^31 - 1). */
+int gnnmp_next_plan(const gnnmp_next_plan_batch* batch, const gnnmp_next_plan_tree* tree, void* hip_stream);
 
 /* ------------------------------------------------------------------------------------------
  * Supervision of the explorer's training step (train_explorer.py:124-176): edge labels, shortest paths to the goal,
