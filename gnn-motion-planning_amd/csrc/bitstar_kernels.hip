@@ -12,7 +12,7 @@
 #include "kernels.hpp"
 #include "maze_f64.hpp"
 
-// numpy rounds every float64 operation on its own; the one fused chain is the dot product of np.linalg.norm (lsp_cost)
+// numpy rounds every float64 operation on its own; the one fused chain is the dot product of np.linalg.norm (mz_cost)
 #pragma clang fp contract(off)
 
 namespace gnnmp {
@@ -83,7 +83,7 @@ __device__ __forceinline__ void bit_wave_argmin(double& val, int& idx, const Les
 // ---------------------------------------------------------------------------------------------------------------------
 template <int DIM>
 __global__ __launch_bounds__(64) void bit_sample_kernel(BitSampleParams p) {
-    __shared__ unsigned char occ[kLspLdsCells];
+    __shared__ unsigned char occ[kMzLdsCells];
     const int b = blockIdx.x, lane = threadIdx.x;
     if (p.active && !p.active[b]) return;
     const long long a0 = p.att_ptr[b], Mb = p.att_ptr[b + 1] - a0;
@@ -92,11 +92,11 @@ __global__ __launch_bounds__(64) void bit_sample_kernel(BitSampleParams p) {
         return;
     }
     const long long total = (long long)p.n_batches * p.batch;
-    const LspMaze m = lsp_maze(p.maps + (size_t)b * p.w * p.w, p.w, occ, lane);
+    const MzMaze m = mz_maze(p.maps + (size_t)b * p.w * p.w, p.w, occ, lane);
     const double* att = p.attempts + (size_t)a0 * DIM;
     auto classify = [&](long long idx, int& cnt) {
-        if (DIM == 2) return lsp_point(m, att[2 * idx], att[2 * idx + 1], cnt);
-        return lsp_stick(m, att[3 * idx], att[3 * idx + 1], att[3 * idx + 2], cnt);
+        if (DIM == 2) return mz_point(m, att[2 * idx], att[2 * idx + 1], cnt);
+        return mz_stick(m, att[3 * idx], att[3 * idx + 1], att[3 * idx + 2], cnt);
     };
     long long free_before = 0, used = -1;
     for (long long off = 0; off < Mb; off += 64) {
@@ -137,11 +137,11 @@ __global__ __launch_bounds__(64) void bit_sample_kernel(BitSampleParams p) {
             unsigned long long bb = bal;
             for (long long skip = (long long)k * p.batch - fb - 1; skip > 0; --skip) bb &= bb - 1;
             const int t = __builtin_ctzll(bb);
-            const long long upto = checks + lsp_wave_sum(lane <= t ? cnt : 0);
+            const long long upto = checks + wave_sum(lane <= t ? cnt : 0);
             if (lane == 0) { used_out[k - 1] = off + t + 1; checks_out[k - 1] = upto; }
             ++k;
         }
-        checks += lsp_wave_sum(cnt);
+        checks += wave_sum(cnt);
         fb += F;
     }
     if (lane == 0) {
@@ -207,7 +207,7 @@ __device__ __forceinline__ void bit_plan_body(const BitPlanParams& p, double* s_
     const BitVertexLess<DIM> vless{pts};
     const BitEdgeLess<DIM> eless{pts, es, et};
 
-    const LspMaze m = lsp_maze(p.maps + (size_t)b * p.w * p.w, p.w, occ, lane);
+    const MzMaze m = mz_maze(p.maps + (size_t)b * p.w * p.w, p.w, occ, lane);
     if (LDS)
         for (int i = lane; i < n_nodes * DIM; i += 64) s_pts[i] = pool[i];
     for (int i = lane; i < rows; i += 64) {
@@ -219,7 +219,7 @@ __device__ __forceinline__ void bit_plan_body(const BitPlanParams& p, double* s_
         par[i] = -1;
         fl[i] = i == 0 ? kBitVertex : 0;
     }
-    lsp_sync();
+    wave_sync();
 
     const long long n_cap = 2 + (long long)p.n_batches * p.batch;
     const long long bound = (long long)p.n_batches * (n_cap * n_cap + 2 * n_cap + 4);
@@ -237,11 +237,11 @@ __device__ __forceinline__ void bit_plan_body(const BitPlanParams& p, double* s_
             for (int i = lane; i < N; i += 64) {
                 if (fl[i] & kBitVertex) {
                     fl[i] = kBitVertex | kBitQueued | kBitOld;
-                    vval[i] = g[i] + lsp_cost<DIM>(goal, pts + (size_t)i * DIM);
+                    vval[i] = g[i] + mz_cost<DIM>(goal, pts + (size_t)i * DIM);
                 }
             }
             nvq = nv;
-            lsp_sync();
+            wave_sync();
         }
         bool empty = false;
         int ei = -1;
@@ -257,7 +257,7 @@ __device__ __forceinline__ void bit_plan_body(const BitPlanParams& p, double* s_
                 if (v < lmin) { lmin = v; lcnt = 1; } else if (v == lmin) ++lcnt;
             }
             bit_wave_argmin(bv, vi, vless);
-            const int vties = lsp_wave_sum(vi >= 0 && lmin == bv ? lcnt : 0);
+            const int vties = wave_sum(vi >= 0 && lmin == bv ? lcnt : 0);
             double be = inf;
             lmin = inf; lcnt = 0; ei = -1;
             for (long long q = lane; q < ne; q += 64) {
@@ -266,7 +266,7 @@ __device__ __forceinline__ void bit_plan_body(const BitPlanParams& p, double* s_
                 if (v < lmin) { lmin = v; lcnt = 1; } else if (v == lmin) ++lcnt;
             }
             bit_wave_argmin(be, ei, eless);
-            const int eties = lsp_wave_sum(ei >= 0 && lmin == be ? lcnt : 0);
+            const int eties = wave_sum(ei >= 0 && lmin == be ? lcnt : 0);
             if (vi < 0 && ei < 0) { empty = true; break; }       // the reference's heappop raises: on to the next batch
             if (vi < 0 || (ei >= 0 && !(bv <= be))) {            // bestVertexQueueValue() > bestEdgeQueueValue(): the edge step
                 n_ties += eties > 1;
@@ -284,11 +284,11 @@ __device__ __forceinline__ void bit_plan_body(const BitPlanParams& p, double* s_
                 bool push = false;
                 double val = 0.0;
                 if (i < N) {
-                    const double d = lsp_cost<DIM>(pts + (size_t)i * DIM, pts + (size_t)v * DIM);
+                    const double d = mz_cost<DIM>(pts + (size_t)i * DIM, pts + (size_t)v * DIM);
                     if (d <= rad) {
                         if (!(fl[i] & kBitVertex)) push = true;
                         else push = !v_old && par[i] != v && gv + d < g[i];
-                        val = (gv + d) + lsp_cost<DIM>(goal, pts + (size_t)i * DIM);
+                        val = (gv + d) + mz_cost<DIM>(goal, pts + (size_t)i * DIM);
                     }
                 }
                 const unsigned long long bal = __builtin_amdgcn_ballot_w64(push);
@@ -304,38 +304,38 @@ __device__ __forceinline__ void bit_plan_body(const BitPlanParams& p, double* s_
             max_q = ne > max_q ? ne : max_q;
             if (lane == 0) fl[v] &= (unsigned char)~kBitQueued;
             --nvq;
-            lsp_sync();
+            wave_sync();
         }
         if (status) break;
         if (empty) continue;
         // ---- the best edge: popped (the last entry fills the hole), checked, accepted if it improves its target
         const int s = es[ei], t = et[ei];
-        lsp_sync();
+        wave_sync();
         if (lane == 0 && ei != ne - 1) { ev[ei] = ev[ne - 1]; es[ei] = es[ne - 1]; et[ei] = et[ne - 1]; }
         --ne;
         ++n_pops;
         ++n_checks;
-        lsp_sync();
+        wave_sync();
         bool isfree;
         if (DIM == 2) {
             int cnt = 0;
-            isfree = lsp_edge2(m, pts[2 * (size_t)s], pts[2 * (size_t)s + 1], pts[2 * (size_t)t], pts[2 * (size_t)t + 1], cnt);
+            isfree = mz_edge2(m, pts[2 * (size_t)s], pts[2 * (size_t)s + 1], pts[2 * (size_t)t], pts[2 * (size_t)t + 1], cnt);
             edge_checks_cnt += cnt;
         } else {
-            isfree = lsp_stick_edge_wave(m, lane, pts + (size_t)s * 3, pts + (size_t)t * 3, edge_checks_cnt);
+            isfree = mz_stick_edge_wave(m, lane, pts + (size_t)s * 3, pts + (size_t)t * 3, edge_checks_cnt);
         }
         if (isfree) {
-            const double new_g = g[s] + lsp_cost<DIM>(pts + (size_t)t * DIM, pts + (size_t)s * DIM);
+            const double new_g = g[s] + mz_cost<DIM>(pts + (size_t)t * DIM, pts + (size_t)s * DIM);
             if (new_g < g[t]) {
                 const bool was_vertex = fl[t] & kBitVertex;
-                lsp_sync();
+                wave_sync();
                 if (lane == 0) {
                     g[t] = new_g;
                     par[t] = s;
                     if (!was_vertex) {
                         fl[t] = kBitVertex | kBitQueued;
                         vert[nv] = t;
-                        vval[t] = new_g + lsp_cost<DIM>(goal, pts + (size_t)t * DIM);
+                        vval[t] = new_g + mz_cost<DIM>(goal, pts + (size_t)t * DIM);
                     }
                 }
                 if (was_vertex) ++n_rew; else { ++nv; ++nvq; }
@@ -348,17 +348,17 @@ __device__ __forceinline__ void bit_plan_body(const BitPlanParams& p, double* s_
                     int ks = 0, kt = 0;
                     if (keep) { kv = ev[q]; ks = es[q]; kt = et[q]; }
                     const unsigned long long bal = __builtin_amdgcn_ballot_w64(keep);
-                    lsp_sync();                                  // every lane has its entry before any slot is overwritten
+                    wave_sync();                                  // every lane has its entry before any slot is overwritten
                     if (keep) {
                         const long long pos = w + __builtin_popcountll(bal & ((1ull << lane) - 1ull));
                         ev[pos] = kv; es[pos] = ks; et[pos] = kt;
                     }
                     w += __builtin_popcountll(bal);
-                    lsp_sync();
+                    wave_sync();
                 }
                 n_filt += ne - w;
                 ne = w;
-                lsp_sync();
+                wave_sync();
             }
         }
         if (g[1] < inf) { success = 1; break; }                  // refine_time_budget = 0: the first solution ends the run
@@ -402,7 +402,7 @@ __global__ __launch_bounds__(64) void bit_plan_kernel(BitPlanParams p) {
     __shared__ double s_g[kBitLdsNodes], s_vval[kBitLdsNodes], s_pts[kBitLdsNodes * DIM];
     __shared__ int s_par[kBitLdsNodes];
     __shared__ unsigned char s_fl[kBitLdsNodes];
-    __shared__ unsigned char occ[kLspLdsCells];
+    __shared__ unsigned char occ[kMzLdsCells];
     if (2 + (long long)p.n_batches * p.batch <= kBitLdsNodes && !(p.flags & 1))
         bit_plan_body<true, DIM>(p, s_g, s_vval, s_pts, s_par, s_fl, occ);
     else

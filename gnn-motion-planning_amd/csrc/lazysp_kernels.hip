@@ -13,28 +13,21 @@
 #include "kernels.hpp"
 #include "maze_f64.hpp"
 
-// numpy rounds every float64 operation on its own; the one fused chain is the dot product of np.linalg.norm (lsp_cost)
+// numpy rounds every float64 operation on its own; the one fused chain is the dot product of np.linalg.norm (mz_cost)
 #pragma clang fp contract(off)
 
 namespace gnnmp {
 
 namespace {
 
-// the counted float64 checker (lsp_maze, lsp_point, lsp_segment, lsp_edge2, lsp_stick, lsp_stick_edge_wave): maze_f64.hpp
+// the counted float64 checker (mz_maze, mz_point, mz_segment, mz_edge2, mz_stick, mz_stick_edge_wave): maze_f64.hpp
 
-// np.linalg.norm(t - s) with its fused dot product (lsp_cost): maze_f64.hpp too
+// np.linalg.norm(t - s) with its fused dot product (mz_cost): maze_f64.hpp too; wave_sync, the wave reductions and
+// lower_bound: wave64.hpp
 
-// first slot q in [lo, hi) with key[q] >= x (key sorted ascending), hi when none
-__device__ __forceinline__ int lsp_lower_bound(const long long* key, int lo, int hi, long long x) {
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (key[mid] < x) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
 // slot of edge (a -> b) in a's out-block, -1 when the graph has no such edge
 __device__ __forceinline__ int lsp_slot(const long long* dst, const int* rb, int a, int b) {
-    const int q = lsp_lower_bound(dst, rb[a], rb[a + 1], (long long)b);
+    const int q = lower_bound(dst, rb[a], rb[a + 1], (long long)b);
     return q < rb[a + 1] && dst[q] == b ? q : -1;
 }
 
@@ -47,7 +40,7 @@ __device__ __forceinline__ int lsp_slot(const long long* dst, const int* rb, int
 // ---------------------------------------------------------------------------------------------------------------------
 template <int DIM>
 __global__ __launch_bounds__(64) void lsp_sample_kernel(LspSampleParams p) {
-    __shared__ unsigned char occ[kLspLdsCells];
+    __shared__ unsigned char occ[kMzLdsCells];
     const int b = blockIdx.x, lane = threadIdx.x;
     if (p.active && !p.active[b]) return;
     const long long a0 = p.att_ptr[b], Mb = p.att_ptr[b + 1] - a0;
@@ -57,11 +50,11 @@ __global__ __launch_bounds__(64) void lsp_sample_kernel(LspSampleParams p) {
         if (lane == 0) { p.status[b] = 2; p.used[b] = 0; p.checks_out[b] = 0; }
         return;
     }
-    const LspMaze m = lsp_maze(p.maps + (size_t)b * p.w * p.w, p.w, occ, lane);
+    const MzMaze m = mz_maze(p.maps + (size_t)b * p.w * p.w, p.w, occ, lane);
     const double* att = p.attempts + (size_t)a0 * DIM;
     auto classify = [&](long long idx, int& cnt) {
-        if (DIM == 2) return lsp_point(m, att[2 * idx], att[2 * idx + 1], cnt);
-        return lsp_stick(m, att[3 * idx], att[3 * idx + 1], att[3 * idx + 2], cnt);
+        if (DIM == 2) return mz_point(m, att[2 * idx], att[2 * idx + 1], cnt);
+        return mz_stick(m, att[3 * idx], att[3 * idx + 1], att[3 * idx + 2], cnt);
     };
     int free_before = 0;
     long long checks = 0, used = -1;
@@ -74,12 +67,12 @@ __global__ __launch_bounds__(64) void lsp_sample_kernel(LspSampleParams p) {
         if (free_before + F >= p.n) {                            // the n-th free draw of this call is in this step
             for (int skip = p.n - free_before - 1; skip > 0; --skip) bal &= bal - 1;
             const int t = __builtin_ctzll(bal);
-            checks += lsp_wave_sum(lane <= t ? cnt : 0);
+            checks += wave_sum(lane <= t ? cnt : 0);
             used = off + t + 1;
             break;
         }
         free_before += F;
-        checks += lsp_wave_sum(cnt);
+        checks += wave_sum(cnt);
     }
     if (used < 0) {                                              // the block ended first: nothing is touched
         if (lane == 0) { p.status[b] = 1; p.used[b] = 0; p.checks_out[b] = 0; }
@@ -137,7 +130,7 @@ __global__ __launch_bounds__(64) void lsp_gather_kernel(LspGatherParams p) {
     };
     int before = 0;
     for (int i = lane; i < j; i += 64) before += count(i);
-    before = lsp_wave_sum(before);
+    before = wave_sum(before);
     const int N = count(j);
     if (lane == 0) {
         p.node_ptr[j] = before;
@@ -208,21 +201,21 @@ __device__ __forceinline__ void lsp_round_body(const LspRoundParams& p, int slot
     int status = 0, solved = 0, path_len = 0, runs = 0;
     long long checks = 0;
 
-    const LspMaze m = lsp_maze(p.maps + (size_t)slot * p.w * p.w, p.w, occ, lane);
+    const MzMaze m = mz_maze(p.maps + (size_t)slot * p.w * p.w, p.w, occ, lane);
     // ---- out-block starts, costs, flags
-    for (int u = lane; u <= N; u += 64) rb[u] = lsp_lower_bound(src, 0, E, (long long)u);
+    for (int u = lane; u <= N; u += 64) rb[u] = lower_bound(src, 0, E, (long long)u);
     bool ok = n_pairs >= 0 && n_pairs <= p.pair_cap;
     for (int e = lane; e < E; e += 64) {
         const long long s = src[e], t = dst[e];
         if (s < 0 || s >= N || t < 0 || t >= N) { ok = false; continue; }
-        cost[e] = lsp_cost<DIM>(pts + s * DIM, pts + t * DIM);
+        cost[e] = mz_cost<DIM>(pts + s * DIM, pts + t * DIM);
         flag[e] = 0;
     }
     if (!__all(ok)) {
         if (lane == 0) p.status[slot] |= 4;
         return;
     }
-    lsp_sync();
+    wave_sync();
     // ---- carried pairs: both directions of an invalid pair are dead, of a valid pair known
     for (int i = lane; i < n_pairs; i += 64) {
         const int a = pairs[2 * i], c = pairs[2 * i + 1];
@@ -230,15 +223,15 @@ __device__ __forceinline__ void lsp_round_body(const LspRoundParams& p, int slot
         const int q = lsp_slot(dst, rb, a, c), r = lsp_slot(dst, rb, c, a);
         if (q >= 0 && r >= 0) flag[q] = flag[r] = pstate[i];
     }
-    lsp_sync();
+    wave_sync();
     const int max_runs = (E >> 1) + 1;
     while (true) {
         if (runs >= max_runs) { status |= 2; break; }
         // ---- one Dijkstra run from node 0
         for (int i = lane; i < N; i += 64) { dist[i] = kLspInfBits; prev[i] = -1; }
-        lsp_sync();
+        wave_sync();
         if (lane == 0) { dist[0] = 0ull; prev[0] = 0; }
-        lsp_sync();
+        wave_sync();
         ++runs;
         bool reached = false;
         int it = 0;
@@ -249,9 +242,9 @@ __device__ __forceinline__ void lsp_round_body(const LspRoundParams& p, int slot
                 const unsigned long long k = dist[i];            // dist >= 0: bit order = value order; visited: sign bit
                 if (k < best) { best = k; bi = i; }              // ascending ids: the first strict minimum
             }
-            const unsigned long long w = lsp_wave_min_u64(best);
+            const unsigned long long w = wave_min_u64(best);
             if (w >= kLspInfBits) break;                         // +inf, or everything visited
-            const int u = (int)lsp_wave_min_u64(best == w ? (unsigned long long)(unsigned)bi : ~0ull);
+            const int u = (int)wave_min_u64(best == w ? (unsigned long long)(unsigned)bi : ~0ull);
             if (u == 1) { reached = true; break; }
             const double du = __longlong_as_double((long long)w);
             for (int q = rb[u] + lane; q < rb[u + 1]; q += 64) {
@@ -265,7 +258,7 @@ __device__ __forceinline__ void lsp_round_body(const LspRoundParams& p, int slot
                 }
             }
             if (lane == 0) dist[u] = w | kLspSign;
-            lsp_sync();
+            wave_sync();
         }
         if (!reached) {
             if (it >= N) status |= 2;                            // N extractions without meeting node 1 or infinity
@@ -282,7 +275,7 @@ __device__ __forceinline__ void lsp_round_body(const LspRoundParams& p, int slot
             if (lane == 0) path[L] = cur;
         }
         if (!walk_ok) { status |= 2; break; }
-        lsp_sync();
+        wave_sync();
         // ---- its unknown edges
         bool feasible = true, full = false;
         if (DIM == 2) {
@@ -297,7 +290,7 @@ __device__ __forceinline__ void lsp_round_body(const LspRoundParams& p, int slot
                         unknown = true;
                         const double* a = pts + (size_t)n1 * 2;
                         const double* c = pts + (size_t)n2 * 2;
-                        blocked = !lsp_edge2(m, a[0], a[1], c[0], c[1], cnt);
+                        blocked = !mz_edge2(m, a[0], a[1], c[0], c[1], cnt);
                     }
                 }
                 const unsigned long long bad = __builtin_amdgcn_ballot_w64(blocked);
@@ -314,9 +307,9 @@ __device__ __forceinline__ void lsp_round_body(const LspRoundParams& p, int slot
                     const int r = lsp_slot(dst, rb, n2, n1);
                     if (r >= 0) flag[r] = st;
                 }
-                checks += lsp_wave_sum(keep ? cnt : 0);
+                checks += wave_sum(keep ? cnt : 0);
                 n_pairs += n_new;
-                lsp_sync();
+                wave_sync();
                 if (bad) feasible = false;
             }
         } else {
@@ -325,7 +318,7 @@ __device__ __forceinline__ void lsp_round_body(const LspRoundParams& p, int slot
                 const int q = lsp_slot(dst, rb, n1, n2);
                 if (q < 0 || flag[q] != 0) continue;             // known valid (a dead edge is never on a path)
                 if (n_pairs + 1 > p.pair_cap) { full = true; break; }
-                const bool fr = lsp_stick_edge_wave(m, lane, pts + (size_t)n1 * 3, pts + (size_t)n2 * 3, checks);
+                const bool fr = mz_stick_edge_wave(m, lane, pts + (size_t)n1 * 3, pts + (size_t)n2 * 3, checks);
                 const unsigned char st = fr ? 1 : 2;
                 if (lane == 0) {
                     pairs[2 * n_pairs] = n1; pairs[2 * n_pairs + 1] = n2; pstate[n_pairs] = st;
@@ -334,7 +327,7 @@ __device__ __forceinline__ void lsp_round_body(const LspRoundParams& p, int slot
                     if (r >= 0) flag[r] = st;
                 }
                 ++n_pairs;
-                lsp_sync();
+                wave_sync();
                 if (!fr) { feasible = false; break; }
             }
         }
@@ -356,7 +349,7 @@ __global__ __launch_bounds__(64) void lsp_round_kernel(LspRoundParams p) {
     __shared__ unsigned long long s_dist[kLspLdsNodes];
     __shared__ int s_prev[kLspLdsNodes];
     __shared__ int s_rb[kLspLdsNodes + 1];
-    __shared__ unsigned char occ[kLspLdsCells];
+    __shared__ unsigned char occ[kMzLdsCells];
     const int slot = p.slot_of ? p.slot_of[blockIdx.x] : (int)blockIdx.x;
     if (slot < 0 || slot >= p.B) return;
     if (p.solved[slot] || p.status[slot]) return;                // finished problems are left as they are

@@ -18,6 +18,7 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include "kernels.hpp"
+#include "maze_f64.hpp"
 
 // numpy evaluates every float32 operation on its own: no fused multiply-add anywhere in this file (hipcc's default
 // is -ffp-contract=fast-honor-pragmas, and HIP's __fmul_rn / __fadd_rn are plain operators that WOULD be fused;
@@ -34,15 +35,11 @@ __device__ __forceinline__ float f_mul(float x, float y) { return x * y; }
 __device__ __forceinline__ float f_div(float x, float y) { return x / y; }        // correctly rounded (hipcc default)
 __device__ __forceinline__ float f_sqrt(float x) { return __builtin_sqrtf(x); }   // correctly rounded (hipcc default)
 
-constexpr int kMazeLdsCells = 4096;      // maps up to 64 x 64 are staged into LDS as bytes
 constexpr int kMazeLdsNodes = 1024;      // problems up to this many nodes keep their per-node explore state in LDS
 
-struct MazeCtx {
-    const double* map;          // [w, w] occupancy (1 = obstacle), row-major map[x][y]
-    const unsigned char* occ;   // LDS copy (1 = obstacle) or nullptr for maps beyond kMazeLdsCells
-    int w;
+struct MazeCtx : MzMaze {       // the map (maze_f64.hpp: LDS bytes up to kMzLdsCells cells), shared with the float64 queries
     long long checks;
-    double* stack;              // LDS, 4 x 48 doubles: the bisection's explicit stack (ONE lane of the wave walks a segment at a time;
+    double* stack;              // LDS, 4 x 48 doubles: the float32 bisection's explicit stack (ONE lane of the wave walks a segment at a time;
                                 // as private arrays indexed at run time it lived in scratch memory, a global round trip per push / pop)
 };
 
@@ -54,12 +51,11 @@ __device__ __forceinline__ void maze_ctx_init(MazeCtx& m, const double* map, int
     m.w = w;
     m.checks = 0;
     m.occ = nullptr;
-    if (w * w <= kMazeLdsCells) {
-        for (int i = lane; i < w * w; i += 64) lds[i] = map[i] == 0.0 ? 0 : 1;
+    if (w * w <= kMzLdsCells) {
+        mz_stage(map, w, lds, lane, 64);
         m.occ = lds;
     }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-    __builtin_amdgcn_wave_barrier();
+    wave_sync();
 }
 
 __device__ __forceinline__ int maze_cell(float x, int w) {        // ((x + 1.0) * w / 2.0).astype(int), clipped at w-1
@@ -108,64 +104,57 @@ __device__ __forceinline__ bool maze_edge_fp(MazeCtx& m, float ax, float ay, flo
 // ---- 3-DoF maze (MazeEnv(dim=3)): a stick of length 0.2 at (x, y), orientation coordinate z in [-0.4, 0.4]
 // (environment/maze_env.py:254-302,330-347).  The reference's numpy dtype flow is part of the behaviour: node rows are
 // float32, the stick ends come out float64 (float32 coordinate / float64 limit), so the 2-D point / segment queries of
-// the ends run in float64, while the interpolation along an edge runs in float32.
-__device__ __forceinline__ int maze_cell64(double x, int w) {
-    int c = (int)((x + 1.0) * (double)w / 2.0);
-    return c > w - 1 ? w - 1 : c;
-}
-__device__ __forceinline__ bool maze_valid64(double x, double y) { return x >= -1.0 && x <= 1.0 && y >= -1.0 && y <= 1.0; }
-__device__ __forceinline__ bool maze_point_fp64(MazeCtx& m, double x, double y) {
-    if (!maze_valid64(x, y)) return false;
-    m.checks += 1;
-    const int idx = maze_cell64(x, m.w) * m.w + maze_cell64(y, m.w);
-    return m.occ ? m.occ[idx] == 0 : m.map[idx] == 0.0;
-}
-__device__ bool maze_segment_fp64(MazeCtx& m, double ax, double ay, double bx, double by) {
-    double* sx0 = m.stack, *sy0 = sx0 + 48, *sx1 = sx0 + 96, *sy1 = sx0 + 144;
-    int sp = 1;
-    sx0[0] = ax; sy0[0] = ay; sx1[0] = bx; sy1[0] = by;
-    while (sp > 0) {
-        --sp;
-        const double lx = sx0[sp], ly = sy0[sp], rx = sx1[sp], ry = sy1[sp];
-        const int dc = abs(maze_cell64(lx, m.w) - maze_cell64(rx, m.w)) + abs(maze_cell64(ly, m.w) - maze_cell64(ry, m.w));
-        const double l1 = fabs(lx - rx) + fabs(ly - ry);
-        if (dc > 1 && l1 > 0.05) {
-            const double mx = (lx + rx) / 2.0, my = (ly + ry) / 2.0;
-            if (!maze_point_fp64(m, mx, my)) return false;
-            if (sp + 2 > 48) return false;
-            sx0[sp] = mx; sy0[sp] = my; sx1[sp] = rx; sy1[sp] = ry; ++sp;
-            sx0[sp] = lx; sy0[sp] = ly; sx1[sp] = mx; sy1[sp] = my; ++sp;
-        }
-    }
-    return true;
-}
+// the ends run in float64 -- maze_f64.hpp's, on the exactly widened row -- while the interpolation along an edge runs in
+// float32, here.  The header counts into an int; the callers add it to their long long totals.
 __device__ __forceinline__ bool maze_valid3(float x, float y, float z) {
     return maze_valid(x, y) && (double)z >= -0.4 && (double)z <= 0.4;
 }
 // stick ends: theta = z / LIMITS[2] * pi (float64), end = center -+ (STICK_LENGTH / 2) * (cos, sin)
 __device__ __forceinline__ void stick_ends(float x, float y, float z, double& ax, double& ay, double& bx, double& by) {
-    const double theta = (double)z / 0.4 * 3.141592653589793;
-    const double ox = 0.1 * cos(theta), oy = 0.1 * sin(theta);
-    ax = (double)x - ox; ay = (double)y - oy;
-    bx = (double)x + ox; by = (double)y + oy;
+    mz_ends((double)x, (double)y, (double)z, ax, ay, bx, by);
 }
-// the same for a float64 configuration (the raw draws of the sampler: nothing passes through float32)
-__device__ __forceinline__ void stick_ends(double x, double y, double z, double& ax, double& ay, double& bx, double& by) {
-    const double theta = z / 0.4 * 3.141592653589793;
-    const double ox = 0.1 * cos(theta), oy = 0.1 * sin(theta);
-    ax = x - ox; ay = y - oy;
-    bx = x + ox; by = y + oy;
+// The bisection between the two ends of a stick.  The stick is 0.2 long, so its ends are at most 0.2 * sqrt(2) = 0.283 apart
+// in L1; a segment splits only while that exceeds RRT_EPS = 0.05 and it halves per level (0.141, 0.071, 0.035): a fourth
+// level never opens, at any map width.  So the walk is three fixed levels in registers, midpoints in the recursion's order
+// M, L, LL, LR, R, RL, RR up to the first blocked one: mz_segment's answer and count without its loop, which took the
+// sampler twice and the steering 1.1 times as long (profiles/maze_f64_ab.txt).
+__device__ __forceinline__ bool seg_splits(int w, double lx, double ly, double rx, double ry) {
+    const int dc = abs(mz_cell(lx, w) - mz_cell(rx, w)) + abs(mz_cell(ly, w) - mz_cell(ry, w));
+    const double l1 = fabs(lx - rx) + fabs(ly - ry);
+    return dc > 1 && l1 > 0.05;
 }
-__device__ bool stick_state_fp(MazeCtx& m, float x, float y, float z) {        // _stick_in_free_space
-    if (!maze_valid3(x, y, z)) return false;
+// level 2 (a quarter of the stick): its halves are shorter than RRT_EPS and never split
+__device__ __forceinline__ bool stick_seg2(const MzMaze& m, double lx, double ly, double rx, double ry, int& cnt) {
+    if (!seg_splits(m.w, lx, ly, rx, ry)) return true;
+    return mz_point(m, (lx + rx) / 2.0, (ly + ry) / 2.0, cnt);
+}
+__device__ __forceinline__ bool stick_seg1(const MzMaze& m, double lx, double ly, double rx, double ry, int& cnt) {
+    if (!seg_splits(m.w, lx, ly, rx, ry)) return true;
+    const double mx = (lx + rx) / 2.0, my = (ly + ry) / 2.0;
+    if (!mz_point(m, mx, my, cnt)) return false;
+    return stick_seg2(m, lx, ly, mx, my, cnt) && stick_seg2(m, mx, my, rx, ry, cnt);
+}
+__device__ __forceinline__ bool stick_segment(const MzMaze& m, double ax, double ay, double bx, double by, int& cnt) {
+    if (!seg_splits(m.w, ax, ay, bx, by)) return true;
+    const double mx = (ax + bx) / 2.0, my = (ay + by) / 2.0;
+    if (!mz_point(m, mx, my, cnt)) return false;
+    return stick_seg1(m, ax, ay, mx, my, cnt) && stick_seg1(m, mx, my, bx, by, cnt);
+}
+// _stick_in_free_space of a float64 configuration (mz_stick with the fixed-depth walk): 0 .. 9 checks
+__device__ __forceinline__ bool stick_fp64(const MzMaze& m, double x, double y, double z, int& cnt) {
+    if (!mz_valid3(x, y, z)) return false;
     double ax, ay, bx, by;
-    stick_ends(x, y, z, ax, ay, bx, by);
-    if (!maze_point_fp64(m, ax, ay) || !maze_point_fp64(m, bx, by)) return false;
-    return maze_segment_fp64(m, ax, ay, bx, by);
+    mz_ends(x, y, z, ax, ay, bx, by);
+    if (!mz_point(m, ax, ay, cnt) || !mz_point(m, bx, by, cnt)) return false;
+    return stick_segment(m, ax, ay, bx, by, cnt);
 }
-__device__ bool stick_edge_fp(MazeCtx& m, const float* s, const float* t) {      // _edge_fp, state.size == 3
-    if (!maze_valid3(s[0], s[1], s[2]) || !maze_valid3(t[0], t[1], t[2])) return false;
-    if (!stick_state_fp(m, s[0], s[1], s[2]) || !stick_state_fp(m, t[0], t[1], t[2])) return false;
+__device__ __forceinline__ bool stick_state_fp(const MzMaze& m, const float* c, int& cnt) {      // the same of a float32 row
+    return stick_fp64(m, (double)c[0], (double)c[1], (double)c[2], cnt);
+}
+// The interior of _edge_fp(s, t), state.size == 3, on float32 rows: configurations s + k * 1. / K * disp, k = 1 .. K - 1, each
+// the 2-D _edge_fp of its stick's ends (mz_stick_steps / mz_stick_step are the same on float64 rows)
+struct StickSteps { float d0, d1, d2; int K; };
+__device__ __forceinline__ StickSteps stick_steps(const float* s, const float* t) {
     const float d0 = f_sub(t[0], s[0]), d1 = f_sub(t[1], s[1]);
     float d2 = f_sub(t[2], s[2]);
     if (fabs((double)d2) > 0.4) d2 = (float)(d2 > 0.f ? (double)d2 - 0.8 : (double)d2 + 0.8);
@@ -175,104 +164,54 @@ __device__ bool stick_edge_fp(MazeCtx& m, const float* s, const float* t) {     
     const double w2 = fabs((double)a2r - 0.8);
     const float a2 = (float)((double)a2r < w2 ? (double)a2r : w2);
     const float dist = f_sqrt(f_add(f_add(f_mul(a0, a0), f_mul(a1, a1)), f_mul(a2, a2)));
-    const int K = (int)f_div(dist, 0.015f);
-    for (int k = 1; k < K; ++k) {
-        const float r = (float)((double)k * 1.0 / (double)K);
-        const float cx = f_add(s[0], f_mul(r, d0)), cy = f_add(s[1], f_mul(r, d1)), cz = f_add(s[2], f_mul(r, d2));
-        double ax, ay, bx, by;
-        stick_ends(cx, cy, cz, ax, ay, bx, by);
-        // the 2-D _edge_fp of the two ends
-        if (!maze_valid64(ax, ay) || !maze_valid64(bx, by)) return false;
-        if (!maze_point_fp64(m, ax, ay) || !maze_point_fp64(m, bx, by)) return false;
-        if (!maze_segment_fp64(m, ax, ay, bx, by)) return false;
-    }
-    return true;
+    return {d0, d1, d2, (int)f_div(dist, 0.015f)};
 }
-
-// ---- the same stick queries for a whole wave (steering of the 3-DoF maze).  An edge query interpolates up to ~190
-// sticks (K = int(d / 0.015)), each a float64 cos / sin and a short bisection: the interior configurations k = 1 .. K - 1
-// go to the lanes, 64 per pass.  Every lane counts its own checks and stops at its own first blocked query; the first
-// failing k decides the edge, and the edge's count is what the sequential loop would have spent: all of the k below it plus
-// the failing k's own.  Passes after a failing pass are not run.  The bisection stack is per lane: a stick is 0.2 long, its
-// ends at most 0.283 apart in L1, so only segments of levels 0 .. 2 split (0.283 / 8 < RRT_EPS) and the depth-first walk
-// never holds more than four segments; the stack has one slot to spare.  LDS layout [component][slot][lane]: conflict-free.
-constexpr int kLaneStackSlots = 5;
-
-__device__ __forceinline__ bool lane_point_fp64(const MazeCtx& m, double x, double y, int& cnt) {
-    if (!maze_valid64(x, y)) return false;
-    cnt += 1;
-    const int idx = maze_cell64(x, m.w) * m.w + maze_cell64(y, m.w);
-    return m.occ ? m.occ[idx] == 0 : m.map[idx] == 0.0;
-}
-// stk: this lane's column of the LDS stack
-__device__ __forceinline__ bool lane_segment_fp64(const MazeCtx& m, double* stk, double ax, double ay, double bx, double by,
-                                                  int& cnt) {
-#define LANE_STK(c, s) stk[((c) * kLaneStackSlots + (s)) * 64]
-    int sp = 1;
-    LANE_STK(0, 0) = ax; LANE_STK(1, 0) = ay; LANE_STK(2, 0) = bx; LANE_STK(3, 0) = by;
-    while (sp > 0) {
-        --sp;
-        const double lx = LANE_STK(0, sp), ly = LANE_STK(1, sp), rx = LANE_STK(2, sp), ry = LANE_STK(3, sp);
-        const int dc = abs(maze_cell64(lx, m.w) - maze_cell64(rx, m.w)) + abs(maze_cell64(ly, m.w) - maze_cell64(ry, m.w));
-        const double l1 = fabs(lx - rx) + fabs(ly - ry);
-        if (dc > 1 && l1 > 0.05) {
-            const double mx = (lx + rx) / 2.0, my = (ly + ry) / 2.0;
-            if (!lane_point_fp64(m, mx, my, cnt)) return false;
-            if (sp + 2 > kLaneStackSlots) return false;          // cannot happen: see the depth bound above
-            LANE_STK(0, sp) = mx; LANE_STK(1, sp) = my; LANE_STK(2, sp) = rx; LANE_STK(3, sp) = ry; ++sp;
-            LANE_STK(0, sp) = lx; LANE_STK(1, sp) = ly; LANE_STK(2, sp) = mx; LANE_STK(3, sp) = my; ++sp;
-        }
-    }
-    return true;
-#undef LANE_STK
-}
-__device__ __forceinline__ bool lane_stick_state_fp(const MazeCtx& m, double* stk, const float (&c)[3], int& cnt) {
-    if (!maze_valid3(c[0], c[1], c[2])) return false;
+__device__ __forceinline__ bool stick_step(const MzMaze& m, const float* s, const StickSteps& e, int k, int& cnt) {
+    const float r = (float)((double)k * 1.0 / (double)e.K);
     double ax, ay, bx, by;
-    stick_ends(c[0], c[1], c[2], ax, ay, bx, by);
-    if (!lane_point_fp64(m, ax, ay, cnt) || !lane_point_fp64(m, bx, by, cnt)) return false;
-    return lane_segment_fp64(m, stk, ax, ay, bx, by, cnt);
+    stick_ends(f_add(s[0], f_mul(r, e.d0)), f_add(s[1], f_mul(r, e.d1)), f_add(s[2], f_mul(r, e.d2)), ax, ay, bx, by);
+    // the 2-D _edge_fp of the two ends (mz_edge2 with the fixed-depth walk)
+    if (!mz_valid2(ax, ay) || !mz_valid2(bx, by)) return false;
+    if (!mz_point(m, ax, ay, cnt) || !mz_point(m, bx, by, cnt)) return false;
+    return stick_segment(m, ax, ay, bx, by, cnt);
 }
+// _edge_fp, state.size == 3, by one lane: both end sticks, then the interior k in order up to the first blocked one
+__device__ bool stick_edge_fp(MazeCtx& m, const float* s, const float* t) {
+    if (!maze_valid3(s[0], s[1], s[2]) || !maze_valid3(t[0], t[1], t[2])) return false;
+    int cnt = 0;
+    bool ok = stick_state_fp(m, s, cnt) && stick_state_fp(m, t, cnt);
+    if (ok) {
+        const StickSteps e = stick_steps(s, t);
+        for (int k = 1; k < e.K && ok; ++k) ok = stick_step(m, s, e, k, cnt);
+    }
+    m.checks += cnt;
+    return ok;
+}
+
+// ---- the same edge query for a whole wave (steering of the 3-DoF maze).  An edge query interpolates up to ~190 sticks
+// (K = int(d / 0.015)), each a float64 cos / sin and a short bisection: the interior configurations k = 1 .. K - 1 go to the
+// lanes, 64 per pass.  Every lane counts its own checks and stops at its own first blocked query; the first failing k decides
+// the edge, and the edge's count is what the sequential loop would have spent: all of the k below it plus the failing k's
+// own.  Passes after a failing pass are not run.
 __device__ __forceinline__ bool wave_uniform(bool x) { return __builtin_amdgcn_readfirstlane(x ? 1 : 0) != 0; }
 
-// _edge_fp(s, t), state.size == 3, by all 64 lanes of the wave; s and t are the same in every lane, and so are the
-// result and `checks`.  The two end configurations are checked by every lane alike (the reference's order, one count).
-__device__ __forceinline__ bool stick_edge_wave(const MazeCtx& m, double* stk, int lane, const float (&s)[3], const float (&t)[3],
-                                long long& checks) {
+// s and t are the same in every lane, and so are the result and `checks`.  The two end configurations are checked by every
+// lane alike (the reference's order, one count).
+__device__ __forceinline__ bool stick_edge_wave(const MzMaze& m, int lane, const float (&s)[3], const float (&t)[3], long long& checks) {
     if (!maze_valid3(s[0], s[1], s[2]) || !maze_valid3(t[0], t[1], t[2])) return false;
     int c_ends = 0;
-    const bool ends_ok = wave_uniform(lane_stick_state_fp(m, stk, s, c_ends) && lane_stick_state_fp(m, stk, t, c_ends));
+    const bool ends_ok = wave_uniform(stick_state_fp(m, s, c_ends) && stick_state_fp(m, t, c_ends));
     checks += __builtin_amdgcn_readfirstlane(c_ends);
     if (!ends_ok) return false;
-    const float d0 = f_sub(t[0], s[0]), d1 = f_sub(t[1], s[1]);
-    float d2 = f_sub(t[2], s[2]);
-    if (fabs((double)d2) > 0.4) d2 = (float)(d2 > 0.f ? (double)d2 - 0.8 : (double)d2 + 0.8);
-    const float a0 = fabsf(f_sub(t[0], s[0])), a1 = fabsf(f_sub(t[1], s[1]));
-    const float a2r = fabsf(f_sub(t[2], s[2]));
-    const double w2 = fabs((double)a2r - 0.8);
-    const float a2 = (float)((double)a2r < w2 ? (double)a2r : w2);
-    const float dist = f_sqrt(f_add(f_add(f_mul(a0, a0), f_mul(a1, a1)), f_mul(a2, a2)));
-    const int K = __builtin_amdgcn_readfirstlane((int)f_div(dist, 0.015f));
-    for (int base = 1; base < K; base += 64) {
+    StickSteps e = stick_steps(s, t);
+    e.K = __builtin_amdgcn_readfirstlane(e.K);
+    for (int base = 1; base < e.K; base += 64) {
         const int k = base + lane;
         int cnt = 0;
-        bool good = true;
-        if (k < K) {
-            const float r = (float)((double)k * 1.0 / (double)K);
-            const float cx = f_add(s[0], f_mul(r, d0)), cy = f_add(s[1], f_mul(r, d1)), cz = f_add(s[2], f_mul(r, d2));
-            double ax, ay, bx, by;
-            stick_ends(cx, cy, cz, ax, ay, bx, by);
-            // the 2-D _edge_fp of the two ends
-            good = maze_valid64(ax, ay) && maze_valid64(bx, by) &&
-                   lane_point_fp64(m, ax, ay, cnt) && lane_point_fp64(m, bx, by, cnt) &&
-                   lane_segment_fp64(m, stk, ax, ay, bx, by, cnt);
-        }
+        const bool good = k < e.K ? stick_step(m, s, e, k, cnt) : true;
         const unsigned long long bad = __builtin_amdgcn_ballot_w64(!good);
         const int first = bad ? __builtin_ctzll(bad) : 63;
-        int sum = lane <= first ? cnt : 0;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off, 64);
-        checks += __builtin_amdgcn_readfirstlane(sum);
+        checks += __builtin_amdgcn_readfirstlane(wave_sum(lane <= first ? cnt : 0));
         if (bad) return false;
     }
     return true;
@@ -299,7 +238,7 @@ __device__ __forceinline__ unsigned long long dpp_u64(unsigned long long k) {
     const int hi = __builtin_amdgcn_update_dpp(0, (int)(unsigned)(k >> 32), CTRL, 0xf, 0xf, true);
     return ((unsigned long long)(unsigned)hi << 32) | (unsigned)lo;
 }
-__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long k) {
+__device__ __forceinline__ unsigned long long wave_max_u64_dpp(unsigned long long k) {
     unsigned long long o;
     o = dpp_u64<0xB1>(k); k = o > k ? o : k;                   // quad_perm [1, 0, 3, 2]
     o = dpp_u64<0x4E>(k); k = o > k ? o : k;                   // quad_perm [2, 3, 0, 1]
@@ -449,7 +388,7 @@ __device__ __forceinline__ void maze_explore_body(const MazeParams& p, const Maz
                 if (key > best) { best = key; bq = q; }                    // value desc, column asc
             }
         }
-        const unsigned long long w = wave_max_u64(best);
+        const unsigned long long w = wave_max_u64_dpp(best);
         int be = -1, bb = 0x7fffffff;
         if (w) {
             const int wl = __builtin_ctzll(__ballot(best == w));
@@ -474,7 +413,7 @@ __device__ __forceinline__ void maze_explore_body(const MazeParams& p, const Maz
             const unsigned long long key = ((unsigned long long)k << 32) | (0xffffffffu - (unsigned)i);
             if (k && key > best) best = key;
         }
-        const unsigned long long w = wave_max_u64(best);
+        const unsigned long long w = wave_max_u64_dpp(best);
         if (!w) break;                                                     // nothing left on the frontier
         const int bp = (int)(0xffffffffu - (unsigned)w);
         const int a = explored[bp], nb = rb_src[bp], be = rb_eid[bp];
@@ -503,7 +442,11 @@ __device__ __forceinline__ void maze_explore_body(const MazeParams& p, const Maz
                     const double wz = fabs(dz - 0.8);
                     dz = dz < wz ? dz : wz;
                     const double d = sqrt((dx * dx + dy * dy) + dz * dz);
-                    if (d < 0.05) goal_hit = stick_state_fp(m, v[3 * nb], v[3 * nb + 1], v[3 * nb + 2]) ? 1 : 0;
+                    if (d < 0.05) {
+                        int n = 0;
+                        goal_hit = stick_state_fp(m, v + 3 * nb, n) ? 1 : 0;
+                        m.checks += n;
+                    }
                 }
             } else {
                 rec[be].x = nb | kDead;                                    // cell (a, nb)
@@ -578,7 +521,7 @@ __global__ __launch_bounds__(256) void maze_explore_kernel(MazeParams p) {
     __shared__ int s_rb_src[kMazeLdsNodes], s_rb_eid[kMazeLdsNodes];
     __shared__ unsigned s_rb_key[kMazeLdsNodes];
     __shared__ float s_v[kMazeLdsNodes * DIM];
-    __shared__ unsigned char occ_lds[kMazeLdsCells];
+    __shared__ unsigned char occ_lds[kMzLdsCells];
     const MazeShared sh{s_in_ptr, s_pos, s_explored, s_rb_src, s_rb_eid, s_rb_key, s_v, occ_lds};
     const int N = p.node_ptr[blockIdx.x + 1] - p.node_ptr[blockIdx.x];
     if (N <= kMazeLdsNodes) maze_explore_body<DIM, true>(p, sh);
@@ -643,7 +586,7 @@ __global__ __launch_bounds__(64) void maze_steer_kernel(MazeSteerParams p) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off, 64));
     const int K = (int)ceilf(mx);
-    __shared__ unsigned char occ_lds[kMazeLdsCells];
+    __shared__ unsigned char occ_lds[kMzLdsCells];
     MazeCtx m;
     maze_ctx_init(m, p.maps + (size_t)b * p.w * p.w, p.w, occ_lds, lane);      // includes the fence + barrier
     if constexpr (DIM == 2) {
@@ -677,8 +620,6 @@ __global__ __launch_bounds__(64) void maze_steer_kernel(MazeSteerParams p) {
         }
         p.checks[b] += m.checks;
     } else {
-        __shared__ double s_lane_stack[4 * kLaneStackSlots * 64];
-        double* stk = s_lane_stack + lane;
         long long checks = 0;
         bool tripped = false;
         const int rounds = P < 3 ? 0 : __builtin_amdgcn_readfirstlane(K);
@@ -711,7 +652,7 @@ __global__ __launch_bounds__(64) void maze_steer_kernel(MazeSteerParams p) {
 #pragma nounroll
                 for (int e = 0; e < 2 && ok; ++e) {
                     const float from[3] = {e ? right[0] : left[0], e ? right[1] : left[1], e ? right[2] : left[2]};
-                    ok = stick_edge_wave(m, stk, lane, from, cand, checks);
+                    ok = stick_edge_wave(m, lane, from, cand, checks);
                 }
                 if (ok) diff = f_add(diff, maze_norm3(f_sub(cand[0], tgt[0]), f_sub(cand[1], tgt[1]), f_sub(cand[2], tgt[2])));
 #pragma unroll
@@ -749,19 +690,19 @@ __global__ __launch_bounds__(64) void maze_steer_kernel(MazeSteerParams p) {
 // flags gives every draw its rank; ~1300 draws per problem at the published setting = two steps, ~3 us.
 // ---------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(1024) void maze_sample_kernel(MazeSampleParams p) {
-    __shared__ unsigned char occ[kMazeLdsCells];
+    __shared__ unsigned char occ[kMzLdsCells];
     __shared__ int wsum[16];
     __shared__ int s_tstar, s_fail;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const long long cur0 = *p.cursor;
     long long cur = cur0;
     int node0 = 0;
-    const bool in_lds = p.w * p.w <= kMazeLdsCells;
+    const bool in_lds = p.w * p.w <= kMzLdsCells;
     if (tid == 0) { p.node_ptr[0] = 0; s_fail = 0; }
     for (int b = 0; b < p.B; ++b) {
         const double* map = p.maps + (size_t)b * p.w * p.w;
         __syncthreads();                                        // the previous problem's map is no longer in use
-        if (in_lds)
+        if (in_lds)                                             // (mz_stage written out: see stick_sample_kernel)
             for (int i = tid; i < p.w * p.w; i += 1024) occ[i] = map[i] == 0.0 ? 0 : 1;
         if (tid == 0) s_tstar = -1;
         __syncthreads();
@@ -773,7 +714,7 @@ __global__ __launch_bounds__(1024) void maze_sample_kernel(MazeSampleParams p) {
             if (in) { x = p.attempts[2 * idx]; y = p.attempts[2 * idx + 1]; }
             bool isfree = false;
             if (in) {
-                const int c = maze_cell64(x, p.w) * p.w + maze_cell64(y, p.w);
+                const int c = mz_cell(x, p.w) * p.w + mz_cell(y, p.w);
                 isfree = in_lds ? occ[c] == 0 : map[c] == 0.0;
             }
             // inclusive block scan of the free flags: ballot + popcount inside a wave, the sixteen wave totals through LDS
@@ -835,60 +776,31 @@ __global__ __launch_bounds__(1024) void maze_sample_kernel(MazeSampleParams p) {
 // ---------------------------------------------------------------------------------------------------------------------
 // The same for the 3-DoF stick robot (MazeEnv(dim=3)): a draw is a configuration (x, y, z) of [-1, 1)^2 x [-0.4, 0.4) and its
 // classification is _stick_in_free_space on the float64 draw (maze_env.py:279-291): end a, end b, then the bisection between
-// them, every in-bounds point query one collision check, evaluation stopping at the first blocked query.  The stick is 0.2
-// long, so its ends are at most 0.2 * sqrt(2) = 0.283 apart in L1; a segment splits only while that exceeds RRT_EPS = 0.05 and
-// it halves per level (0.141, 0.071, 0.035): a fourth level never opens, at any map width.  The walk is therefore three fixed
-// levels in registers -- midpoints in the order M, L, LL, LR, R, RL, RR, at most 2 + 7 = 9 checks per draw -- with no stack.
+// them, every in-bounds point query one collision check, evaluation stopping at the first blocked query (stick_fp64 above: at most
+// 2 + 7 = 9 checks per draw).
 // The structure is maze_sample_kernel's; the scan carries one more quantity, the check counts, because a problem's count is
 // the sum over the draws it CONSUMED (up to and including its n-th free one), not over the 1024-draw step they sat in.
 // ---------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ bool seg_splits(int w, double lx, double ly, double rx, double ry) {
-    const int dc = abs(maze_cell64(lx, w) - maze_cell64(rx, w)) + abs(maze_cell64(ly, w) - maze_cell64(ry, w));
-    const double l1 = fabs(lx - rx) + fabs(ly - ry);
-    return dc > 1 && l1 > 0.05;
-}
-// level 2 (a quarter of the stick): its halves are shorter than RRT_EPS and never split
-__device__ __forceinline__ bool stick_seg2(const MazeCtx& m, double lx, double ly, double rx, double ry, int& cnt) {
-    if (!seg_splits(m.w, lx, ly, rx, ry)) return true;
-    return lane_point_fp64(m, (lx + rx) / 2.0, (ly + ry) / 2.0, cnt);
-}
-__device__ __forceinline__ bool stick_seg1(const MazeCtx& m, double lx, double ly, double rx, double ry, int& cnt) {
-    if (!seg_splits(m.w, lx, ly, rx, ry)) return true;
-    const double mx = (lx + rx) / 2.0, my = (ly + ry) / 2.0;
-    if (!lane_point_fp64(m, mx, my, cnt)) return false;
-    return stick_seg2(m, lx, ly, mx, my, cnt) && stick_seg2(m, mx, my, rx, ry, cnt);
-}
-// _stick_in_free_space of a float64 configuration; cnt receives the collision checks it spends (0 .. 9)
-__device__ __forceinline__ bool stick_draw_fp64(const MazeCtx& m, double x, double y, double z, int& cnt) {
-    if (!maze_valid64(x, y) || !(z >= -0.4 && z <= 0.4)) return false;
-    double ax, ay, bx, by;
-    stick_ends(x, y, z, ax, ay, bx, by);
-    if (!lane_point_fp64(m, ax, ay, cnt) || !lane_point_fp64(m, bx, by, cnt)) return false;
-    if (!seg_splits(m.w, ax, ay, bx, by)) return true;
-    const double mx = (ax + bx) / 2.0, my = (ay + by) / 2.0;
-    if (!lane_point_fp64(m, mx, my, cnt)) return false;
-    return stick_seg1(m, ax, ay, mx, my, cnt) && stick_seg1(m, mx, my, bx, by, cnt);
-}
-
 __global__ __launch_bounds__(1024) void stick_sample_kernel(MazeSampleParams p) {
-    __shared__ unsigned char occ[kMazeLdsCells];
+    __shared__ unsigned char occ[kMzLdsCells];
     __shared__ int wsum[16], csum[16];
     __shared__ int s_tstar, s_cstar;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const long long cur0 = *p.cursor;
     long long cur = cur0;
     int node0 = 0;
-    const bool in_lds = p.w * p.w <= kMazeLdsCells;
+    const bool in_lds = p.w * p.w <= kMzLdsCells;
     if (tid == 0) p.node_ptr[0] = 0;
     for (int b = 0; b < p.B; ++b) {
         const double* map = p.maps + (size_t)b * p.w * p.w;
         __syncthreads();                                        // the previous problem's map is no longer in use
+        // mz_stage's loop written out: as a call inside the loop over the problems the compiler lays the kernel out
+        // differently and it takes 3 % longer (profiles/maze_f64_ab.txt)
         if (in_lds)
             for (int i = tid; i < p.w * p.w; i += 1024) occ[i] = map[i] == 0.0 ? 0 : 1;
         if (tid == 0) s_tstar = -1;
         __syncthreads();
-        MazeCtx m;
-        m.map = map; m.occ = in_lds ? occ : nullptr; m.w = p.w; m.checks = 0; m.stack = nullptr;
+        const MzMaze m{in_lds ? occ : nullptr, map, p.w};
         int free_before = 0, rej_before = 0, rej_total = 0, used = 0;
         long long checks = 0;
         for (long long off = 0;; off += 1024) {
@@ -899,7 +811,7 @@ __global__ __launch_bounds__(1024) void stick_sample_kernel(MazeSampleParams p) 
             bool isfree = false;
             if (in) {
                 x = p.attempts[3 * idx]; y = p.attempts[3 * idx + 1]; z = p.attempts[3 * idx + 2];
-                isfree = stick_draw_fp64(m, x, y, z, cnt);
+                isfree = stick_fp64(m, x, y, z, cnt);
             }
             // inclusive block scans of the free flags (ballot + popcount) and of the check counts (shuffles) inside a wave,
             // the sixteen wave totals of each through LDS
@@ -1019,7 +931,7 @@ constexpr int kStreamCachedSteps = 32;      // free flags of the first 32 x 1024
 // and stores the rows.
 template <int DIM>
 __global__ __launch_bounds__(1024) void maze_sample_streams_kernel(MazeStreamsParams p) {
-    __shared__ unsigned char occ[kMazeLdsCells];
+    __shared__ unsigned char occ[kMzLdsCells];
     __shared__ unsigned long long s_bal[kStreamCachedSteps * 16];
     __shared__ int wsum[16], csum[16];
     __shared__ int s_tstar, s_cstar;
@@ -1034,24 +946,22 @@ __global__ __launch_bounds__(1024) void maze_sample_streams_kernel(MazeStreamsPa
         if (tid == 0) { p.status[b] = 2; p.used[b] = 0; p.checks[b] = 0; }
         return;
     }
-    const bool in_lds = p.w * p.w <= kMazeLdsCells;
+    const bool in_lds = p.w * p.w <= kMzLdsCells;
     const double* map = p.maps + (size_t)b * p.w * p.w;
-    if (in_lds)
-        for (int i = tid; i < p.w * p.w; i += 1024) occ[i] = map[i] == 0.0 ? 0 : 1;
+    if (in_lds) mz_stage(map, p.w, occ, tid, 1024);
     if (tid == 0) s_tstar = -1;
     __syncthreads();
-    MazeCtx m;
-    m.map = map; m.occ = in_lds ? occ : nullptr; m.w = p.w; m.checks = 0; m.stack = nullptr;
+    const MzMaze m{in_lds ? occ : nullptr, map, p.w};
     const double* att = p.attempts + (size_t)a0 * DIM;
     auto classify = [&](long long idx, int& cnt) {
         if constexpr (DIM == 2) {
             const double x = att[2 * idx], y = att[2 * idx + 1];
             cnt = 1;
-            if (!maze_valid64(x, y)) return false;               // (uniform(-1, 1) never is: keeps the lookup inside the map)
-            const int c = maze_cell64(x, p.w) * p.w + maze_cell64(y, p.w);
+            if (!mz_valid2(x, y)) return false;                  // (uniform(-1, 1) never is: keeps the lookup inside the map)
+            const int c = mz_cell(x, p.w) * p.w + mz_cell(y, p.w);
             return in_lds ? occ[c] == 0 : map[c] == 0.0;
         } else {
-            return stick_draw_fp64(m, att[3 * idx], att[3 * idx + 1], att[3 * idx + 2], cnt);
+            return stick_fp64(m, att[3 * idx], att[3 * idx + 1], att[3 * idx + 2], cnt);
         }
     };
     // ---- pass 1: where is the n-th free draw, and what do the draws up to it cost

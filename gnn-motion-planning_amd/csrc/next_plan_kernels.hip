@@ -119,7 +119,7 @@ __global__ __launch_bounds__(kNpThreads) void next_plan_kernel(NextPlanParams p)
         for (int i = tid; i < kLat * kCells; i += kNpThreads) S.pb[i] = pbg[i];
         for (int i = tid; i < kCells; i += kNpThreads) S.occ[i] = map[i] == 0.0 ? 0 : 1;
     }
-    const LspMaze m{S.occ, map, kW};
+    const MzMaze m{S.occ, map, kW};
     const RrtNodes<DIM> tree{S.x, S.y, S.z, S.c, S.f};
     double goal[3] = {0.0, 0.0, 0.0};
 #pragma unroll

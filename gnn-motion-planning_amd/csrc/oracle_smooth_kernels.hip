@@ -20,7 +20,7 @@
 //   * _edge_fp of size 3: both validity tests, both stick checks, then K = int(distance / 0.015) interpolated sticks
 //     c = state + k * 1. / K * disp (disp[2] wrapped by 0.8), each the 2-D _edge_fp of its ends, up to the first blocked
 //     one.  Two float32 ends take the float32 flow of maze_kernels.hip's stick_edge_fp, anything else the float64 flow of
-//     train_episode_kernels.hip's ep_edge_fp3 on exactly upcast values;
+//     maze_f64.hpp's mz_stick_edge on exactly upcast values;
 //   * np.linalg.norm of a 3-vector (no wrap) is sqrt(dot): float64 dot = fma(d2, d2, fma(d1, d1, d0 * d0)); float32 dot =
 //     the three float32-rounded squares summed left to right in double and rounded once to float32.
 // Parallel across lanes: the critical-index test and the all-pairs edge checks of create_graph (one ordered pair per lane),
@@ -29,6 +29,7 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include "kernels.hpp"
+#include "wave64.hpp"
 
 // numpy rounds every operation on its own; the one fused operation is the float64 dot's (below)
 #pragma clang fp contract(off)
@@ -226,15 +227,6 @@ __device__ __forceinline__ double os_lerp(double A, double B, bool f, int i, int
     return d + A;
 }
 
-__device__ __forceinline__ unsigned long long os_wave_min_u64(unsigned long long k) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const unsigned long long o = __shfl_xor(k, off, 64);
-        k = o < k ? o : k;
-    }
-    return k;
-}
-
 template <int D> struct OsPath {                // one path in LDS
     double x[kOsCap], y[kOsCap], z[D == 3 ? kOsCap : 1];
     unsigned char f[kOsCap], src[kOsCap];
@@ -389,7 +381,7 @@ template <int D> __global__ __launch_bounds__(64) void oracle_smooth_kernel(Orac
                         const unsigned long long k = (unsigned long long)__double_as_longlong(sh.dist[v]);   // dist >= 0
                         if (k < best) best = k;
                     }
-                    const unsigned long long w = os_wave_min_u64(best);
+                    const unsigned long long w = wave_min_u64(best);
                     if (w >= 0x7ff0000000000000ull) break;
                     unsigned long long cand = ~0ull;
                     for (int v = lane; v < mm; v += 64) {
@@ -397,7 +389,7 @@ template <int D> __global__ __launch_bounds__(64) void oracle_smooth_kernel(Orac
                         if (cand == ~0ull) cand = (unsigned long long)v;
                         ++ties;
                     }
-                    const int u = (int)os_wave_min_u64(cand);
+                    const int u = (int)wave_min_u64(cand);
                     ties += __shfl_xor(ties, 32, 64); ties += __shfl_xor(ties, 16, 64); ties += __shfl_xor(ties, 8, 64);
                     ties += __shfl_xor(ties, 4, 64); ties += __shfl_xor(ties, 2, 64); ties += __shfl_xor(ties, 1, 64);
                     if (ties > 1) status |= kStTie;

@@ -41,18 +41,18 @@ __device__ __forceinline__ double rrt_wrap(double z) {           // maze_env.py:
 // env.step(s, new_state = t) by all 64 lanes, s and t the same in every lane (t already clipped and wrapped): -> no_collision,
 // the same in every lane; `checks` grows by what the call counts, the goal test of a free edge included.
 template <int DIM>
-__device__ __forceinline__ bool rrt_step(const LspMaze& m, int lane, const double* s, const double* t, bool near_goal, long long& checks) {
+__device__ __forceinline__ bool rrt_step(const MzMaze& m, int lane, const double* s, const double* t, bool near_goal, long long& checks) {
     bool fr;
     if (DIM == 2) {
         int cnt = 0;
-        fr = lsp_edge2(m, s[0], s[1], t[0], t[1], cnt);
-        if (fr && near_goal) lsp_point(m, t[0], t[1], cnt);
+        fr = mz_edge2(m, s[0], s[1], t[0], t[1], cnt);
+        if (fr && near_goal) mz_point(m, t[0], t[1], cnt);
         checks += cnt;
     } else {
-        fr = lsp_stick_edge_wave(m, lane, s, t, checks);
+        fr = mz_stick_edge_wave(m, lane, s, t, checks);
         if (fr && near_goal) {
             int cnt = 0;
-            lsp_stick(m, t[0], t[1], t[2], cnt);
+            mz_stick(m, t[0], t[1], t[2], cnt);
             checks += cnt;
         }
     }
@@ -83,8 +83,8 @@ __device__ __forceinline__ int rrt_nearest(const RrtNodes<DIM>& t, int n, int la
         const unsigned long long k = (unsigned long long)__double_as_longlong(rrt_dist<DIM>(q, smp));      // d >= 0: bit order
         if (k < best) { best = k; bi = j; }                      // ascending ids: the first strict minimum
     }
-    const unsigned long long wmin = lsp_wave_min_u64(best);
-    const int ni = (int)lsp_wave_min_u64(best == wmin ? (unsigned long long)(unsigned)bi : ~0ull);
+    const unsigned long long wmin = wave_min_u64(best);
+    const int ni = (int)wave_min_u64(best == wmin ? (unsigned long long)(unsigned)bi : ~0ull);
     dmin = __longlong_as_double((long long)wmin);
     return ni;
 }
@@ -118,7 +118,7 @@ __device__ __forceinline__ void rrt_clip(double* nw) {
 // independent, their counts add up), stick robot one candidate at a time over the lanes.  Lane 0 stores the new node's cost
 // and rewired parent; `plen` follows set_cost (search_tree.py:56-63).
 template <int DIM>
-__device__ __forceinline__ void rrt_rewire(const LspMaze& m, int lane, const RrtNodes<DIM>& t, int* rewired, int n, int ni, const double* near,
+__device__ __forceinline__ void rrt_rewire(const MzMaze& m, int lane, const RrtNodes<DIM>& t, int* rewired, int n, int ni, const double* near,
                                            const double* nw, bool near_goal, bool done, double& plen, long long& checks) {
     double* nc = t.c;
     // ---- pass 1: the cheapest free neighbour with a free edge becomes the parent
@@ -158,11 +158,11 @@ __device__ __forceinline__ void rrt_rewire(const LspMaze& m, int lane, const Rrt
         if (DIM == 2) {
             int cnt = 0;
             if (cand) {
-                const bool ok = lsp_edge2(m, q[0], q[1], nw[0], nw[1], cnt);
-                if (ok && near_goal) lsp_point(m, nw[0], nw[1], cnt);
+                const bool ok = mz_edge2(m, q[0], q[1], nw[0], nw[1], cnt);
+                if (ok && near_goal) mz_point(m, nw[0], nw[1], cnt);
                 if (ok) { nc[j] = cost_new; rewired[j] = n; }
             }
-            checks += lsp_wave_sum(cnt);
+            checks += wave_sum(cnt);
         } else {
             unsigned long long todo = __builtin_amdgcn_ballot_w64(cand);
             while (todo) {

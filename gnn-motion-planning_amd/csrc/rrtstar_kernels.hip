@@ -20,7 +20,7 @@
 //              a time over the lanes.  A node that improves gets its cost and rewired parent; descendants keep their costs.
 // Node state (coordinates, cost, flags: 8 DIM + 9 bytes a node) lives in LDS up to kRrtLdsNodes nodes and in the caller's
 // workspace beyond it.  Loop bounds: t_max iterations; ceil(n / 64) groups of at most 64 candidates per pass; the bisection
-// walk has at most 2^level nodes per level with level <= kLspMaxLevel (maze_f64.hpp); K = int(d / 0.015) <= 190 because both
+// walk has at most 2^level nodes per level with level <= kMzMaxLevel (maze_f64.hpp); K = int(d / 0.015) <= 190 because both
 // ends passed _valid_state (d <= sqrt(4 + 4 + 0.16)); the path walk stops after n nodes (status bit 2).
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -53,7 +53,7 @@ __device__ __forceinline__ void rrt_body(const RrtParams& p, double* s_x, double
     double* plen_out = p.path_lengths + row;
     long long* cum = p.cum_checks + row;
     const double* draws = p.draws + (size_t)b * p.draw_len;
-    const LspMaze m = lsp_maze(p.maps + (size_t)b * p.w * p.w, p.w, occ, lane);
+    const MzMaze m = mz_maze(p.maps + (size_t)b * p.w * p.w, p.w, occ, lane);
     double goal[3] = {0.0, 0.0, 0.0};
 #pragma unroll
     for (int c = 0; c < DIM; ++c) goal[c] = p.goal_states[(size_t)b * DIM + c];
@@ -65,7 +65,7 @@ __device__ __forceinline__ void rrt_body(const RrtParams& p, double* s_x, double
         nf[0] = kRrtFree;
         parents[0] = -1; rewired[0] = -1; plen_out[0] = -1.0; cum[0] = 0;
     }
-    lsp_sync();
+    wave_sync();
     const RrtNodes<DIM> tree{nx, ny, nz, nc, nf};
     int n = 1, status = 0, last_i = -1;
     long long checks = 0, pos = 0;
@@ -108,7 +108,7 @@ __device__ __forceinline__ void rrt_body(const RrtParams& p, double* s_x, double
         if (lane == 0) { plen_out[n] = plen; cum[n] = checks; }
         ++n;
         last_i = it;
-        lsp_sync();
+        wave_sync();
         if (success && p.stop) break;
     }
     // ---- the tree comes out; search_tree.path(): from the last node along rewired_parents to the root
@@ -141,7 +141,7 @@ __global__ __launch_bounds__(64) void rrtstar_plan_kernel(RrtParams p) {
     constexpr int kNodes = LDS ? kRrtLdsNodes : 1;
     __shared__ double s_x[kNodes], s_y[kNodes], s_z[DIM == 3 ? kNodes : 1], s_c[kNodes];
     __shared__ unsigned char s_f[kNodes];
-    __shared__ unsigned char occ[kLspLdsCells];
+    __shared__ unsigned char occ[kMzLdsCells];
     rrt_body<LDS, DIM>(p, s_x, s_y, s_z, s_c, s_f, occ);
 }
 

@@ -12,158 +12,41 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include "kernels.hpp"
+#include "maze_f64.hpp"
 
-// numpy rounds every float64 operation on its own; the one fused operation is the one numpy's BLAS dot uses (below)
+// numpy rounds every float64 operation on its own; the one fused operation is the one numpy's BLAS dot uses (mz_cost)
 #pragma clang fp contract(off)
 
 namespace gnnmp {
 
 namespace {
 
-constexpr int kEpLdsCells = 4096;       // maps up to 64 x 64 are staged into LDS as bytes
 constexpr int kEpLdsNodes = 1024;       // problems up to this many nodes keep their per-node state in LDS
-constexpr int kEpStack = 16;            // bisection stack entries per lane (depth <= 7 for L1 lengths <= 4 and RRT_EPS = 0.05)
 
-// ---- (a) MazeEnv's checker on float64 states, one lane per edge.  Every lane walks its own bisection stack in LDS
-// ([4][kEpStack][64] doubles per 64-lane block).  The free / blocked answer does not depend on the order in which the
-// midpoints are visited (it is the AND of all of them), only on which midpoints exist, which is the reference's rule.
-struct EpMaze {
-    const unsigned char* occ;           // LDS copy (1 = obstacle) or nullptr
-    const double* map;                  // [w, w] row-major map[x][y]
-    int w;
-    double* stk;                        // this block's stack base; entry (k, sp) of lane l at stk[(k * kEpStack + sp) * 64 + l]
-    int lane;
-};
-
-__device__ __forceinline__ int ep_cell(double x, int w) {       // ((x + 1.0) * w / 2.0).astype(int), clipped at w - 1
-    const int c = (int)((x + 1.0) * (double)w / 2.0);
-    return c > w - 1 ? w - 1 : c;
-}
-__device__ __forceinline__ bool ep_valid2(double x, double y) { return x >= -1.0 && x <= 1.0 && y >= -1.0 && y <= 1.0; }
-__device__ __forceinline__ bool ep_point_fp(const EpMaze& m, double x, double y) {    // _point_in_free_space
-    if (!ep_valid2(x, y)) return false;
-    const int idx = ep_cell(x, m.w) * m.w + ep_cell(y, m.w);
-    return m.occ ? m.occ[idx] == 0 : m.map[idx] == 0.0;
-}
-__device__ bool ep_segment_fp(const EpMaze& m, double ax, double ay, double bx, double by) {      // _iterative_check_segment
-    double* s = m.stk + m.lane;
-    auto at = [&](int k, int sp) -> double& { return s[(k * kEpStack + sp) * 64]; };
-    int sp = 1;
-    at(0, 0) = ax; at(1, 0) = ay; at(2, 0) = bx; at(3, 0) = by;
-    while (sp > 0) {
-        --sp;
-        const double lx = at(0, sp), ly = at(1, sp), rx = at(2, sp), ry = at(3, sp);
-        const int dc = abs(ep_cell(lx, m.w) - ep_cell(rx, m.w)) + abs(ep_cell(ly, m.w) - ep_cell(ry, m.w));
-        const double l1 = fabs(lx - rx) + fabs(ly - ry);
-        if (dc > 1 && l1 > 0.05) {
-            const double mx = (lx + rx) / 2.0, my = (ly + ry) / 2.0;
-            if (!ep_point_fp(m, mx, my)) return false;
-            if (sp + 2 > kEpStack) return false;             // cannot happen (depth <= 7), never writes past the stack
-            at(0, sp) = mx; at(1, sp) = my; at(2, sp) = rx; at(3, sp) = ry; ++sp;
-            at(0, sp) = lx; at(1, sp) = ly; at(2, sp) = mx; at(3, sp) = my; ++sp;
-        }
-    }
-    return true;
-}
-__device__ bool ep_edge_fp2(const EpMaze& m, double ax, double ay, double bx, double by) {       // _edge_fp, size 2
-    if (!ep_valid2(ax, ay) || !ep_valid2(bx, by)) return false;
-    if (!ep_point_fp(m, ax, ay) || !ep_point_fp(m, bx, by)) return false;
-    return ep_segment_fp(m, ax, ay, bx, by);
-}
-// stick robot (maze_env.py:245-302): theta = z / LIMITS[2] * pi, ends = center -+ (STICK_LENGTH / 2.) * (cos, sin)
-__device__ __forceinline__ bool ep_valid3(const double* s) {
-    return ep_valid2(s[0], s[1]) && s[2] >= -0.4 && s[2] <= 0.4;
-}
-__device__ __forceinline__ void ep_ends(double x, double y, double z, double& ax, double& ay, double& bx, double& by) {
-    const double theta = z / 0.4 * 3.141592653589793;
-    const double ox = 0.1 * cos(theta), oy = 0.1 * sin(theta);
-    ax = x - ox; ay = y - oy;
-    bx = x + ox; by = y + oy;
-}
-__device__ bool ep_stick_fp(const EpMaze& m, const double* s) {                                   // _stick_in_free_space
-    if (!ep_valid3(s)) return false;
-    double ax, ay, bx, by;
-    ep_ends(s[0], s[1], s[2], ax, ay, bx, by);
-    if (!ep_point_fp(m, ax, ay) || !ep_point_fp(m, bx, by)) return false;
-    return ep_segment_fp(m, ax, ay, bx, by);
-}
-__device__ bool ep_edge_fp3(const EpMaze& m, const double* s, const double* t) {                // _edge_fp, size 3
-    if (!ep_valid3(s) || !ep_valid3(t)) return false;
-    if (!ep_stick_fp(m, s) || !ep_stick_fp(m, t)) return false;
-    const double d0 = t[0] - s[0], d1 = t[1] - s[1];
-    double d2 = t[2] - s[2];
-    if (fabs(d2) > 0.4) d2 = d2 > 0.0 ? d2 - 0.8 : d2 + 0.8;
-    // distance(): |t - s|, third coordinate min(|d|, ||d| - 0.8|), sqrt of the left-to-right sum of squares
-    const double a0 = fabs(t[0] - s[0]), a1 = fabs(t[1] - s[1]);
-    double a2 = fabs(t[2] - s[2]);
-    const double w2 = fabs(a2 - 0.8);
-    a2 = w2 < a2 ? w2 : a2;
-    const double d = sqrt((a0 * a0 + a1 * a1) + a2 * a2);
-    const int K = (int)(d / 0.015);
-    for (int k = 1; k < K; ++k) {
-        const double r = (double)k / (double)K;                 // k * 1. / K
-        const double cx = s[0] + r * d0, cy = s[1] + r * d1, cz = s[2] + r * d2;
-        double ax, ay, bx, by;
-        ep_ends(cx, cy, cz, ax, ay, bx, by);
-        if (!ep_edge_fp2(m, ax, ay, bx, by)) return false;
-    }
-    return true;
-}
-
-// ---- wave reductions (all 64 lanes active)
-__device__ __forceinline__ unsigned long long ep_wave_max_u64(unsigned long long k) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const unsigned long long o = __shfl_xor(k, off, 64);
-        k = o > k ? o : k;
-    }
-    return k;
-}
-__device__ __forceinline__ unsigned long long ep_wave_min_u64(unsigned long long k) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const unsigned long long o = __shfl_xor(k, off, 64);
-        k = o < k ? o : k;
-    }
-    return k;
-}
 __device__ __forceinline__ unsigned ep_ord(float x) {          // order-preserving float -> unsigned, never 0 for a non-NaN
     const unsigned u = __float_as_uint(x);
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ void ep_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-}
-
-// first slot q in [lo, hi) with key[q] >= x (key sorted ascending), hi when none
-__device__ __forceinline__ int ep_lower_bound(const long long* key, int lo, int hi, long long x) {
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (key[mid] < x) lo = mid + 1; else hi = mid;
-    }
-    return lo;
 }
 
 // all lanes: out-block starts of the problem's nodes (row_beg [N + 1], problem-local slots) and, when rev != nullptr, the
 // reverse of every edge (problem-local id, -1 when the edge set is not symmetric).  Returns (wave-uniform) whether every
 // edge has its reverse.
 __device__ bool ep_blocks(const long long* src, const long long* dst, int N, int E, int* row_beg, int* rev, int lane) {
-    for (int u = lane; u <= N; u += 64) row_beg[u] = ep_lower_bound(src, 0, E, (long long)u);
-    ep_sync();
+    for (int u = lane; u <= N; u += 64) row_beg[u] = lower_bound(src, 0, E, (long long)u);
+    wave_sync();
     bool ok = true;
     if (rev) {
         for (int e = lane; e < E; e += 64) {
             const long long s = src[e], t = dst[e];
             int r = -1;
             if (t >= 0 && t < N) {
-                const int q = ep_lower_bound(dst, row_beg[t], row_beg[t + 1], s);
+                const int q = lower_bound(dst, row_beg[t], row_beg[t + 1], s);
                 if (q < row_beg[t + 1] && dst[q] == s) r = q;
             }
             rev[e] = r;
             ok = ok && r >= 0;
         }
-        ep_sync();
+        wave_sync();
     }
     return __all(ok);
 }
@@ -176,32 +59,19 @@ __device__ bool ep_blocks(const long long* src, const long long* dst, int N, int
 constexpr int kEpLabelBlocks = 8;
 
 __global__ __launch_bounds__(64) void ep_label_kernel(EpLabelParams p) {
-    __shared__ unsigned char occ[kEpLdsCells];
-    __shared__ double stk[4 * kEpStack * 64];
+    __shared__ unsigned char occ[kMzLdsCells];
     const int b = blockIdx.y, lane = threadIdx.x;
     const int n0 = p.node_ptr[b], e0 = p.edge_ptr[b], E = p.edge_ptr[b + 1] - e0;
-    const double* map = p.maps + (size_t)b * p.w * p.w;
-    EpMaze m{nullptr, map, p.w, stk, lane};
-    if (p.w * p.w <= kEpLdsCells) {
-        for (int i = lane; i < p.w * p.w; i += 64) occ[i] = map[i] == 0.0 ? 0 : 1;
-        m.occ = occ;
-    }
-    __syncthreads();
+    const MzMaze m = mz_maze(p.maps + (size_t)b * p.w * p.w, p.w, occ, lane);
     const long long* src = p.edge_index + e0;
     const long long* dst = p.edge_index + p.total_edges + e0;
     for (int e = blockIdx.x * 64 + lane; e < E; e += kEpLabelBlocks * 64) {
         const double* s = p.points + (size_t)(n0 + src[e]) * p.dim;
         const double* t = p.points + (size_t)(n0 + dst[e]) * p.dim;
-        const bool fr = p.dim == 2 ? ep_edge_fp2(m, s[0], s[1], t[0], t[1]) : ep_edge_fp3(m, s, t);
+        int cnt = 0;                                                         // (the labels carry no check count)
+        const bool fr = p.dim == 2 ? mz_edge2(m, s[0], s[1], t[0], t[1], cnt) : mz_stick_edge(m, s, t, cnt);
         double cost = INFINITY;
-        if (fr) {
-            // np.linalg.norm(t - s) = sqrt(dot(d, d)); numpy's BLAS dot accumulates left to right with fused multiply-adds
-            const double d0 = t[0] - s[0], d1 = t[1] - s[1];
-            double acc = d0 * d0;
-            acc = __builtin_fma(d1, d1, acc);
-            if (p.dim == 3) { const double d2 = t[2] - s[2]; acc = __builtin_fma(d2, d2, acc); }
-            cost = sqrt(acc);
-        }
+        if (fr) cost = p.dim == 2 ? mz_cost<2>(s, t) : mz_cost<3>(s, t);
         p.edge_free[e0 + e] = fr ? 1 : 0;
         p.edge_cost[e0 + e] = cost;
     }
@@ -230,14 +100,14 @@ __device__ __forceinline__ void ep_paths_body(const EpPathsParams& p, double* s_
     const int goal = p.goal_index[b];
     for (int i = lane; i < N; i += 64) { dist[i] = INFINITY; done[i] = 0; prev[i] = -1; }
     const bool sym = ep_blocks(src, dst, N, E, rb, nullptr, lane);
-    ep_sync();
+    wave_sync();
     if (goal < 0 || goal >= N) {                                            // nothing to do: every node unreachable
         if (LDS) for (int i = lane; i < N; i += 64) p.dist[n0 + i] = INFINITY;
         if (lane == 0) p.n_valid[b] = 0;
         return;
     }
     if (lane == 0) { dist[goal] = 0.0; prev[goal] = goal; }
-    ep_sync();
+    wave_sync();
     bool sym_ok = sym;
     while (true) {
         unsigned long long best = ~0ull;
@@ -247,20 +117,20 @@ __device__ __forceinline__ void ep_paths_body(const EpPathsParams& p, double* s_
             const unsigned long long k = (unsigned long long)__double_as_longlong(dist[i]);    // dist >= 0: bits order = value order
             if (k < best) { best = k; bi = i; }                              // ascending ids: the first strict minimum
         }
-        const unsigned long long w = ep_wave_min_u64(best);
+        const unsigned long long w = wave_min_u64(best);
         if (w >= 0x7ff0000000000000ull) break;                               // +inf (or nothing left)
         const unsigned long long cand = best == w ? (unsigned long long)(unsigned)bi : ~0ull;
-        const int u = (int)ep_wave_min_u64(cand);
+        const int u = (int)wave_min_u64(cand);
         const double du = __longlong_as_double((long long)w);
         if (lane == 0) done[u] = 1;
         for (int q = rb[u] + lane; q < rb[u + 1]; q += 64) {                 // v = dst[q]; cost(v -> u) is the reverse edge's
             const int v = (int)dst[q];
-            const int r = ep_lower_bound(dst, rb[v], rb[v + 1], (long long)u);
+            const int r = lower_bound(dst, rb[v], rb[v + 1], (long long)u);
             if (r >= rb[v + 1] || dst[r] != u) { sym_ok = false; continue; }
             const double alt = du + cost[r];
             if (alt < dist[v]) { dist[v] = alt; prev[v] = u; }
         }
-        ep_sync();
+        wave_sync();
     }
     int cnt = 0;
     for (int i = lane; i < N; i += 64) {
@@ -268,8 +138,7 @@ __device__ __forceinline__ void ep_paths_body(const EpPathsParams& p, double* s_
         cnt += d != INFINITY ? 1 : 0;
         if (LDS) p.dist[n0 + i] = d;
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off, 64);
+    cnt = wave_sum(cnt);
     sym_ok = __all(sym_ok);
     if (lane == 0) p.n_valid[b] = sym_ok ? cnt : -1;
 }
@@ -360,7 +229,7 @@ __device__ __forceinline__ void ep_episode_body(const EpEpisodeParams& p, const 
                 if (k > best) { best = k; bq = q; }                          // value desc, column asc
             }
         }
-        const unsigned long long w = ep_wave_max_u64(best);
+        const unsigned long long w = wave_max_u64(best);
         int wq = -1;
         if (w) wq = __builtin_amdgcn_readlane(bq, __builtin_ctzll(__ballot(best == w)));
         if (lane == 0) {
@@ -371,9 +240,9 @@ __device__ __forceinline__ void ep_episode_body(const EpEpisodeParams& p, const 
     };
 
     if (lane == 0) explored[0] = start;
-    ep_sync();
+    wave_sync();
     rescan(0);
-    ep_sync();
+    wave_sync();
     int n_expl = 1, step_i = -1;
     bool emptied = false;
     for (int it = 0; it < steps_in; ++it) {
@@ -384,7 +253,7 @@ __device__ __forceinline__ void ep_episode_body(const EpEpisodeParams& p, const 
             const unsigned long long kk = ((unsigned long long)k << 32) | (0xffffffffu - (unsigned)i);
             if (k && kk > best) best = kk;                                   // value desc, position asc
         }
-        const unsigned long long w = ep_wave_max_u64(best);
+        const unsigned long long w = wave_max_u64(best);
         if (!w) { emptied = true; break; }                                   // argmax of an empty tensor raises
         const int bp = (int)(0xffffffffu - (unsigned)w);
         const int a = explored[bp], c = key_col[bp], q = key_slot[bp];
@@ -397,7 +266,7 @@ __device__ __forceinline__ void ep_episode_body(const EpEpisodeParams& p, const 
         } else if (lane == 0) {
             dead[q] = 1; dead[r] = 1;                                        // cells (a, c) and (c, a)
         }
-        ep_sync();
+        wave_sync();
         // rows whose cached best cell died: column c (free) or the cells (a, c) / (c, a) (blocked); then the new row
         const int old_n = fr ? n_expl - 1 : n_expl;
         for (int base = 0; base < old_n; base += 64) {
@@ -414,7 +283,7 @@ __device__ __forceinline__ void ep_episode_body(const EpEpisodeParams& p, const 
             }
         }
         if (fr) rescan(n_expl - 1);
-        ep_sync();
+        wave_sync();
     }
 
     if (!replay) {
@@ -433,11 +302,11 @@ __device__ __forceinline__ void ep_episode_body(const EpEpisodeParams& p, const 
         const unsigned long long k = (unsigned long long)__double_as_longlong(dist[explored[i]]);
         if (k < bd) bd = k;                                                  // first minimum per lane (positions ascend)
     }
-    const unsigned long long wd = ep_wave_min_u64(bd);
+    const unsigned long long wd = wave_min_u64(bd);
     unsigned long long cpos = ~0ull;
     for (int i = lane; i < n_expl; i += 64)
         if ((unsigned long long)__double_as_longlong(dist[explored[i]]) == wd) { cpos = (unsigned long long)i; break; }
-    const int npos = (int)ep_wave_min_u64(cpos);
+    const int npos = (int)wave_min_u64(cpos);
     const int nn = explored[npos];
     const int pn = p.prev[n0 + nn];
     const float fr0 = (float)nn, fr1 = pn >= 0 ? (float)pn : INFINITY;
@@ -470,7 +339,7 @@ __device__ __forceinline__ void ep_episode_body(const EpEpisodeParams& p, const 
             len += __builtin_popcountll(bal);
         }
     }
-    const unsigned long long wl = ep_wave_min_u64(lbest);
+    const unsigned long long wl = wave_min_u64(lbest);
     if (lane == 0) {
         p.frontier_len[b] = len;
         p.label[b] = len ? (pn >= 0 ? (int)(unsigned)wl : 0) : -1;          // an infinite prev: every norm is inf, argmin 0

@@ -164,6 +164,63 @@ def test_random_maze3_batch_matches_restatement():
     assert int((status == 0).sum()) >= 4
 
 
+def _midpoints(l, r, w, level=0, half=None):
+    """(level, half of the whole segment: 'L' / 'R' / None for its own midpoint, point) of every midpoint the bisection
+    of l -> r visits on a map without obstacles."""
+    dc = abs(H._cell(l[0], w) - H._cell(r[0], w)) + abs(H._cell(l[1], w) - H._cell(r[1], w))
+    if not (dc > 1 and abs(l[0] - r[0]) + abs(l[1] - r[1]) > H.RRT_EPS):
+        return []
+    mid = ((l[0] + r[0]) / 2.0, (l[1] + r[1]) / 2.0)
+    return ([(level, half, mid)] + _midpoints(l, mid, w, level + 1, half or 'L') + _midpoints(mid, r, w, level + 1, half or 'R'))
+
+
+def test_long_maze2_edges_bisect_beyond_five_levels():
+    """Edges of L1 length 3 on a 64 x 64 map split six times.  One is free; the other is blocked by a single obstacle cell
+    that only midpoints of level >= 5 in its right half land in, so the walk has to get through the whole left half and
+    down the right one to find it."""
+    w = 64
+    cell_of = lambda q: (H._cell(q[0], w), H._cell(q[1], w))
+    a, b, c, d = (-0.95, -0.52), (0.93, 0.61), (-0.9, 0.7), (0.95, -0.45)
+    mids = _midpoints(a, b, w)
+    assert max(lv for lv, _, _ in mids) >= 5
+    others = {cell_of(q) for q in (a, b, c, d)} | {cell_of(q) for _, _, q in _midpoints(c, d, w)}
+    shallow = {cell_of(q) for lv, half, q in mids if lv < 5 or half != 'R'}
+    cell = next(cell_of(q) for lv, half, q in mids if lv >= 5 and half == 'R' and cell_of(q) not in others | shallow)
+    m = np.zeros((w, w))
+    m[cell] = 1.0
+    pts = np.array([a, b, c, d])
+    ei = np.array([[0, 1, 2, 3], [1, 0, 3, 2]])
+    hf, hc = H.label_edges(pts, ei, m)
+    assert np.all(np.abs(pts[ei[0]] - pts[ei[1]]).sum(axis=1) > 2.9)
+    assert hf[0] == 0 and hf[2] == 1                                 # a blocked and a free long edge
+    g = graphs_of([{'points': pts, 'edge_index': ei, 'map': m}])
+    assert np.array_equal(g.edge_free.cpu().numpy(), hf) and np.array_equal(g.edge_cost.cpu().numpy(), hc)
+
+
+def _knn_edges(pts, k=5):
+    """A symmetric k-nearest-neighbour edge set, columns sorted by (source, target) like construct_graph's."""
+    dist = np.linalg.norm(pts[:, None, :] - pts[None, :, :], axis=-1)
+    np.fill_diagonal(dist, np.inf)
+    pairs = {(s, int(t)) for s in range(len(pts)) for t in np.argsort(dist[s])[:k]}
+    return np.array(sorted(pairs | {(t, s) for s, t in pairs}), dtype=np.int64).T
+
+
+@pytest.mark.parametrize('dim', [2, 3])
+def test_labels_on_maps_beyond_the_lds_copy(dim):
+    """Width 65 is 4225 cells, more than the 4096 bytes of the LDS copy: every query reads the map in global memory."""
+    rng = np.random.default_rng(20 + dim)
+    lim = np.array([1.0, 1.0, 0.4])[:dim]
+    cases = []
+    for _ in range(2):
+        pts = rng.uniform(-lim, lim, (20, dim))
+        cases.append({'points': pts, 'edge_index': _knn_edges(pts), 'map': (rng.random((65, 65)) < 0.02).astype(np.float64)})
+    host = [H.label_edges(c['points'], c['edge_index'], c['map']) for c in cases]
+    hf, hc = np.concatenate([h[0] for h in host]), np.concatenate([h[1] for h in host])
+    assert 0 < int(hf.sum()) < len(hf)                               # free and blocked edges
+    g = graphs_of(cases)
+    assert np.array_equal(g.edge_free.cpu().numpy(), hf) and np.array_equal(g.edge_cost.cpu().numpy(), hc)
+
+
 def test_loss_stays_finite_with_large_logits():
     """Masked slots of the ragged gather hold scores[0]; a logit far above the frontier's maximum must not reach exp()."""
     rng0 = np.random.default_rng(8)

@@ -182,6 +182,30 @@ def test_long_edges_on_own_maps_equal_the_host_steering():
         assert _steer([c])[0][0].tobytes() == g[0].tobytes() and _steer([c])[0][1:] == g[1:]
 
 
+def test_maps_beyond_the_lds_copy_equal_the_host_steering():
+    """Width 65 is 4225 cells, more than the 4096 bytes of the LDS copy: every query reads the map in global memory.  Two
+    paths of four waypoints on sparse maps of the test's own, against the host's smooth_step over Maze3D."""
+    rng = np.random.RandomState(23)
+    maps = (rng.rand(2, 65, 65) < 0.004).astype(np.float64)
+    env = Maze3D(maps, np.zeros((2, 3)), np.zeros((2, 3)))
+    want, batch = [], []
+    for mi in range(2):
+        old = np.concatenate([np.clip(rng.uniform(-0.4, 0.4, 2) + np.cumsum(rng.normal(0, 0.15, (4, 2)), axis=0), -0.85, 0.85),
+                              rng.uniform(-0.3, 0.3, (4, 1))], axis=1).astype(np.float32)
+        new = (old + rng.normal(0, 0.06, old.shape) * [[0], [1], [1], [0]]).astype(np.float32)
+        env.init_new_problem(mi)
+        env.collision_check_count = 0
+        out = planner.smooth_step([r.copy() for r in old], new.copy(), env)
+        want.append((np.array(out, dtype=np.float32).reshape(-1, 3), int(env.collision_check_count)))
+        batch.append({'old_path': old, 'new_path': new, 'map': maps[mi]})
+    # waypoints move on one path at least, and one edge at least is blocked (a fully accepted path ends on its proposal)
+    assert any(w[0].tobytes() != c['old_path'].tobytes() for w, c in zip(want, batch))
+    assert any(w[0].tobytes() != c['new_path'].tobytes() for w, c in zip(want, batch))
+    for mi, ((hp, hc), (path, checks, status)) in enumerate(zip(want, _steer(batch))):
+        print('\nmap %d: checks device %d host %d, status %d' % (mi, checks, hc, status))
+        assert status == 0 and path.tobytes() == hp.tobytes() and checks == hc and hc > 0, mi
+
+
 class _TrippingSmoother:
     """Stands in for the network: proposes the path itself, except one waypoint turned by more than 1.2."""
 
