@@ -114,7 +114,8 @@ __device__ __forceinline__ void gb_select(const GbParams& p, double (&dist)[T], 
 
 // Graphs beyond 2048 nodes, k <= 16: the candidates stream past once per pass; every lane keeps the 16 smallest
 // (distance, index) pairs of ITS candidates in registers (sorted insertion; candidates arrive in ascending index, so a strict
-// comparison keeps the lower index ahead on ties) -- the k nearest overall are among those 64 x 16 -- and the usual selection
+// comparison puts a newcomer behind the entries at its distance and a full list gives up its highest index there: pinned by
+// tests/test_graph_build_edges_gpu.py::test_streaming_trip) -- the k nearest overall are among those 64 x 16 -- and the usual selection
 // rounds then run over them.  (Recomputing all distances in every round, the general form below, was 225 ms for 32 graphs of
 // 5000 nodes at k = 16.)
 __device__ __forceinline__ void gb_knn_top16(const GbParams& p, const float* __restrict__ xi, int n0, int M, int k,
@@ -140,16 +141,22 @@ __device__ __forceinline__ void gb_knn_top16(const GbParams& p, const float* __r
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             const int c = c0 + u * 64 + lane;
-            double cd = c < M ? d[u] : (double)INFINITY;
-            int ci = c;
+            const double cd = c < M ? d[u] : (double)INFINITY;
+            // sorted insertion behind the entries at the same distance (strict comparison).  The list is ascending, so "cd <
+            // td[s]" is false up to the insertion point and true from there on: every slot from there takes its predecessor,
+            // the last entry leaves.  All sixteen comparisons are against the CANDIDATE: comparing a displaced entry again on
+            // its way down (as this loop once did) lets it pass the entries at its own distance, and a full list then drops
+            // its lowest index at that distance instead of its highest.
+            bool lt[16];
 #pragma unroll
-            for (int s = 0; s < 16; ++s) {                     // sorted insertion: the displaced entry moves on down the list
-                const bool lt = cd < td[s];
-                const double od = td[s];
-                const int oi = ti[s];
-                td[s] = lt ? cd : od; ti[s] = lt ? ci : oi;
-                cd = lt ? od : cd; ci = lt ? oi : ci;
+            for (int s = 0; s < 16; ++s) lt[s] = cd < td[s];
+#pragma unroll
+            for (int s = 15; s > 0; --s) {
+                td[s] = lt[s] ? (lt[s - 1] ? td[s - 1] : cd) : td[s];
+                ti[s] = lt[s] ? (lt[s - 1] ? ti[s - 1] : c) : ti[s];
             }
+            td[0] = lt[0] ? cd : td[0];
+            ti[0] = lt[0] ? c : ti[0];
         }
     }
     for (int r = 0; r < p.kmax; ++r) {
@@ -447,8 +454,13 @@ hipError_t launch_graph_build(const GbParams& p, hipStream_t st) {
     {
         int cap = 8 * p.kmax < 256 ? 256 : 8 * p.kmax;       // entries per wave held in LDS (typical bucket: <= 4 k1)
         if (cap > 3072) cap = 3072;
-        hipLaunchKernelGGL(gb_unique_kernel, dim3((p.total_nodes + 3) / 4), dim3(256), (size_t)4 * 2 * cap * sizeof(int), st,
-                           p, cap);
+        const size_t lds = (size_t)4 * 2 * cap * sizeof(int);
+        if (lds > 64 * 1024) {                               // k1_max >= 257: beyond the default dynamic-LDS limit (at most 96 KB)
+            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gb_unique_kernel),
+                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            if (e != hipSuccess) return e;
+        }
+        hipLaunchKernelGGL(gb_unique_kernel, dim3((p.total_nodes + 3) / 4), dim3(256), lds, st, p, cap);
     }
     LAUNCH_CHECK();
     // per-graph totals of unique edges, chained into edge_ptr, then final per-source offsets

@@ -14,6 +14,7 @@ import torch
 
 from conftest import env_of, golden_files, load_weights
 import gnnmp
+import knn_host as K
 from gnnmp.synth import ENVS, synth_graph
 from oracle import ref_cpu
 from parity_bar import assert_fp32_parity, explorer_oracle_pair
@@ -336,3 +337,118 @@ def test_large_graph_prep_paths():
     perm = torch.randperm(E, generator=torch.Generator().manual_seed(5)).to(DEV)
     shuffled = m.edge_scores(d['goal'], 2, d['v'], d['obstacles'], d['edge_index'][:, perm])
     assert torch.equal(shuffled, alone[perm])
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Goal node (model.py:132, knn(v, goal, 1)): the arg-min of the float32 squared distance, LOWEST index on equal distance
+# (goal_body; goal_partial combined by prep_scatter_kernel for graphs from 4096 nodes in the column-split build).  The goal
+# lies off every node and the nearest rows of v are exact copies of each other, so their distances are equal bit for bit;
+# the node is read with debug_tap(batch, 3) and compared with tests/knn_host.argmin_stable32.
+# ---------------------------------------------------------------------------------------------------------------------
+
+def _tied_goal_graph(n, copies, seed, k1=5, n_obs=20, edges=None):
+    """Random maze2 graph whose rows `copies` are one point, 1/256 from the goal and nearer to it than every other row."""
+    gen = torch.Generator().manual_seed(seed)
+    v = torch.rand(n, 2, generator=gen) * 2 - 1
+    goal = torch.tensor([0.28125, -0.4375])
+    far = (v - goal).norm(dim=1) < 0.02                        # nobody else near the goal
+    v[far] = v[far] + 0.25
+    v[list(copies)] = goal + torch.tensor([1.0 / 256, 0.0])
+    d = (v.double() - goal.double()).pow(2).sum(1)
+    assert int((d == d.min()).sum()) == len(copies) and K.argmin_stable32(v, goal) == min(copies)
+    if edges is None:
+        ei = K.build_edges_stable(v, n // 2, k1)
+    else:
+        ei = torch.randint(0, n, (2, edges), generator=gen)
+    return {'v': v, 'goal': goal, 'obstacles': torch.rand(n_obs, 2, generator=gen) - 0.5, 'edge_index': ei}
+
+
+def _goal_nodes(m, graphs, loop=2):
+    """Scores per graph and the goal node per graph of one batched forward."""
+    b = gnnmp.GraphBatch.from_graphs(graphs, 2, DEV)
+    parts = b.split_edges(m.forward_batch(b, loop))
+    return parts, [int(x) for x in m.debug_tap(b, 3).cpu().tolist()]
+
+
+def _pin_knn(monkeypatch, highest=False):
+    """The oracle's goal node pinned to the lowest (or, as the counter-check, the highest) index at the minimum float32 distance."""
+    def knn(x, y, k, input_dtype=False):
+        assert k == 1 and y.shape[0] == 1
+        xf = x.float()
+        i = x.shape[0] - 1 - K.argmin_stable32(xf.flip(0), y.float()) if highest else K.argmin_stable32(xf, y.float())
+        return torch.tensor([[0], [i]])
+    monkeypatch.setattr(ref_cpu, 'knn', knn)
+
+
+def _check_scores_need_the_right_node(s, g, loop, monkeypatch, what):
+    """Scores on the fp32 bar against the oracle with the lowest tied index; host-side condition: the oracle with the highest
+    tied index is at least 100 x the case's own fp32-vs-fp64 error away, so the wrong node cannot pass."""
+    w = load_weights('weights_maze')
+    with monkeypatch.context() as mp:
+        _pin_knn(mp)
+        ref32, ref64 = explorer_oracle_pair(w, g, loop)
+    with monkeypatch.context() as mp:
+        _pin_knn(mp, highest=True)
+        wrong32, _ = explorer_oracle_pair(w, g, loop)
+    own = (ref32.double() - ref64).abs().max().item()
+    moved = (wrong32 - ref32).abs().max().item()
+    print('\n%s: the highest tied index moves the scores by %.2e, own fp32-vs-fp64 error %.2e' % (what, moved, own))
+    assert moved >= 100 * own, (moved, own)
+    assert_fp32_parity(s, ref32, ref64, what)
+
+
+@pytest.mark.parametrize('n,copies', [(100, (3, 40)),                  # two lanes of one wave
+                                      (300, (10, 200)),                # two waves of the workgroup
+                                      (300, (7, 70, 263)),             # three copies: lanes and waves
+                                      (1100, (17, 1041)),              # one thread's first and second stride trip (i, i + 1024)
+                                      (2200, (1100, 2124, 76)),        # ... second and third trip, and the lowest in another thread
+                                      (130, (5, 127)), (400, (390, 12)), (700, (9, 350, 697))],      # slices of the sliced CSR build
+                         ids=lambda x: str(x).replace(' ', ''))
+def test_goal_node_among_identical_rows_single_graph(n, copies, monkeypatch):
+    g = _tied_goal_graph(n, copies, seed=n + len(copies))
+    m = make_model('maze2')
+    parts, nodes = _goal_nodes(m, [g])
+    assert nodes == [K.argmin_stable32(g['v'], g['goal'])] == [min(copies)]
+    d = to_dev(g)
+    assert torch.equal(parts[0], m.edge_scores(d['goal'], 2, d['v'], d['obstacles'], d['edge_index']))
+    _check_scores_need_the_right_node(parts[0].cpu(), g, 2, monkeypatch, 'copies at %s of %d' % (copies, n))
+
+
+def test_goal_node_among_identical_rows_column_split_build(monkeypatch):
+    """The shape of test_column_split_csr_build_ragged_batch (tests/test_explorer_fuzz_gpu.py; edge columns of a graph split
+    over several workgroups, the goal arg-min on the graph's last part) with tied goals in the large graphs, and a graph of
+    4200 nodes whose arg-min is split over the parts (goal_partial, from 4096 nodes) with the copies in different parts."""
+    from test_explorer_fuzz_gpu import random_graph
+    gen = torch.Generator().manual_seed(909)
+    m = make_model('maze2')
+    graphs = [_tied_goal_graph(2500, (2400, 31, 1055), 1, n_obs=30, edges=40000), random_graph(gen, 40, 0, 5),
+              random_graph(gen, 1, 3, 0), _tied_goal_graph(3000, (2999, 1500), 2, n_obs=90, edges=52000),
+              random_graph(gen, 150, 600, 116, hub=90), _tied_goal_graph(1800, (1700, 64), 3, n_obs=1, edges=25000)]
+    b = gnnmp.GraphBatch.from_graphs(graphs, 2, DEV)
+    assert b.total_edges // b.n_graphs > 2 * 8192
+    parts, nodes = _goal_nodes(m, graphs)
+    assert nodes == [K.argmin_stable32(g['v'], g['goal']) for g in graphs]
+    assert nodes[0] == 31 and nodes[3] == 1500 and nodes[5] == 64
+    _check_scores_need_the_right_node(parts[5].cpu(), graphs[5], 2, monkeypatch, 'column-split build')
+    big = _tied_goal_graph(4200, (4100, 3000, 600, 1624), 4, n_obs=5, edges=70000)       # 8 parts of 525 nodes
+    _, nodes = _goal_nodes(m, [big])
+    assert nodes == [600]
+    big['v'][600] += 0.5                                                                 # the lowest copy now in the fourth part
+    _, nodes = _goal_nodes(m, [big])
+    assert nodes == [K.argmin_stable32(big['v'], big['goal'])] == [1624]
+
+
+def test_goal_node_among_equidistant_lattice_nodes():
+    """Distinct nodes at the same distance: every point of a 14 x 14 lattice in a shuffled order, the goal on a cell centre
+    (four corners at 2 (1/16)^2, exact in float32)."""
+    v = K.lattice(196, 2, 0.125, 7, 0)
+    goal = torch.tensor([0.0625, -0.1875])
+    d = K.sqdist64(goal.view(1, 2), v)[0]
+    tied = np.flatnonzero(d == d.min())
+    assert tied.size == 4 and K.argmin_stable32(v, goal) == tied[0]
+    g = {'v': v, 'goal': goal, 'obstacles': torch.rand(9, 2, generator=torch.Generator().manual_seed(7)) - 0.5,
+         'edge_index': K.build_edges_stable(v, 98, 4)}
+    m = make_model('maze2')
+    for graphs in ([g], [g, synth_graph('maze2', 64, 4, seed=1), g]):
+        _, nodes = _goal_nodes(m, graphs)
+        assert nodes[0] == nodes[-1] == int(tied[0])

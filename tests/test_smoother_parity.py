@@ -9,6 +9,7 @@ import torch
 
 from conftest import golden_files, load_weights
 import gnnmp
+import knn_host as K
 from oracle import ref_cpu
 
 pytestmark = pytest.mark.gpu
@@ -156,6 +157,93 @@ def test_random_problems(seed):
         got = out[off:off + path.shape[0]]
         assert torch.allclose(got, ref, rtol=1e-5, atol=1e-5 * scale), (name, (got - ref).abs().max())
         off += path.shape[0]
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The kNN's tie rule (lower sample index on equal distance) and its sample counts up to the 2048 limit.
+# sm_graph_kernel<16> takes problems of up to 1024 samples, sm_graph_kernel<32> those beyond (slots 17 to 32 of a lane);
+# the two-launch form (sm_knn_kernel + sm_edges_kernel, GNNMP_SM_FUSED_GRAPH=0) is run once in a child process on the same
+# problems and must give the same bits, so the oracle comparisons below hold for it as well.
+# ---------------------------------------------------------------------------------------------------------------------
+TIE_NAME = 'smooth_2d_attv3'                     # scale 1: x / scale is exact
+
+
+def _knn_highest_index(monkeypatch):
+    """The oracle's float32 kNN with the OPPOSITE tie rule: samples flipped, stable sort, ids mapped back."""
+    orig = ref_cpu.knn
+
+    def knn(x, y, k, input_dtype=False):
+        e = orig(x.flip(0), y, k, True)
+        e[1] = x.shape[0] - 1 - e[1]
+        return e
+    monkeypatch.setattr(ref_cpu, 'knn', knn)
+
+
+def _gpu_forward(prob, loop):
+    path, free, coll, ei = prob
+    return make(TIE_NAME)(path=path.to(DEV), free=free.to(DEV), collided=coll.to(DEV), obstacles=None, edge_index=ei.to(DEV),
+                          loop=loop).cpu()
+
+
+@pytest.mark.parametrize('ns', K.SMOOTHER_SAMPLE_COUNTS)
+def test_knn_ties_pick_the_lower_sample_index(ns, monkeypatch):
+    """Lattice samples, waypoints on lattice points and cell centres: the tenth neighbour lies inside a shell of equidistant
+    samples (all distances exact in float32).  Reference: the oracle with the float32 kNN, which sorts stably.  Host-side
+    condition: the oracle with the opposite tie rule moves the result by more than 1e-3, a hundred times the bar -- except
+    with 9 samples, fewer than k = 10, where every sample is a neighbour under any rule and the two oracles must agree."""
+    prob = K.smoother_lattice_problem(ns)
+    w = load_weights(TIE_NAME)
+    ref = ref_cpu.smoother_forward(w, *prob, loop=1, knn_input_dtype=True)
+    with monkeypatch.context() as mp:
+        _knn_highest_index(mp)
+        other = ref_cpu.smoother_forward(w, *prob, loop=1, knn_input_dtype=True)
+    moved = (ref - other).abs().max().item()
+    print('\n%d samples: the opposite tie rule moves the oracle by %.2e' % (ns, moved))
+    assert moved > 1e-3 if ns > 10 else moved == 0.0
+    out = _gpu_forward(prob, 1)
+    assert torch.allclose(out, ref, rtol=1e-5, atol=1e-5), (out - ref).abs().max()
+
+
+@pytest.mark.parametrize('ns', K.SMOOTHER_SAMPLE_COUNTS)
+def test_sample_counts_up_to_the_limit_against_the_oracle(ns):
+    """The same sample counts on random inputs at loop = 2 against the default oracle (float64 kNN)."""
+    prob = K.smoother_random_problem(ns)
+    out = _gpu_forward(prob, 2)
+    ref = ref_cpu.smoother_forward(load_weights(TIE_NAME), *prob, loop=2)
+    assert torch.allclose(out, ref, rtol=1e-5, atol=1e-5), (out - ref).abs().max()
+
+
+_TWO_LAUNCH_CHILD = r'''
+import sys, torch
+sys.path.insert(0, %r); sys.path.insert(0, %r + '/tests')
+import gnnmp, knn_host as K
+from gnnmp.weights import load_weights
+m = gnnmp.ModelSmoother(workspace_size=3, config_size=2, embed_size=128, obs_size=6, scale=1.0).eval()
+m.load_state_dict(load_weights('smooth_2d_attv3'), strict=True)
+res = {}
+for ns in K.SMOOTHER_SAMPLE_COUNTS:
+    for kind, build, loop in (('tied', K.smoother_lattice_problem, 1), ('random', K.smoother_random_problem, 2)):
+        path, free, coll, ei = build(ns)
+        res['%%s%%d' %% (kind, ns)] = m(path=path.cuda(), free=free.cuda(), collided=coll.cuda(), obstacles=None,
+                                     edge_index=ei.cuda(), loop=loop).cpu()
+torch.save(res, sys.argv[1])
+'''
+
+
+def test_two_launch_form_same_bits_on_the_tie_and_limit_cases(tmp_path):
+    """sm_knn_kernel + sm_edges_kernel on every problem of the two tests above, in ONE child process (the switch is read once
+    per process): bit-equal to the one-launch form of this process, which those tests hold to the oracle."""
+    import subprocess
+    import sys
+    from conftest import REPO
+    out = str(tmp_path / 'two_launch.pt')
+    subprocess.run([sys.executable, '-c', _TWO_LAUNCH_CHILD % (REPO, REPO), out], check=True,
+                   env=dict(os.environ, GNNMP_SM_FUSED_GRAPH='0'), timeout=300)
+    res = torch.load(out)
+    assert len(res) == 2 * len(K.SMOOTHER_SAMPLE_COUNTS)
+    for ns in K.SMOOTHER_SAMPLE_COUNTS:
+        assert torch.equal(res['tied%d' % ns], _gpu_forward(K.smoother_lattice_problem(ns), 1)), ns
+        assert torch.equal(res['random%d' % ns], _gpu_forward(K.smoother_random_problem(ns), 2)), ns
 
 
 def test_limits_fail_loudly():
