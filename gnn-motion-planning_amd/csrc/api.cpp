@@ -2,6 +2,7 @@
 // carving and the kernel sequence of the explorer forward pass.
 #include <hip/hip_runtime.h>
 #include <cmath>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -1975,6 +1976,54 @@ extern "C" int gnnmp_next_state_forward(const gnnmp_next_states* d, void* hip_st
     p.states = d->states; p.problem_of_state = d->problem_of_state; p.pb_rep = d->pb_rep; p.weights = d->weights; p.y = d->y;
     p.status = d->status;
     HIP_TRY(launch_next_state_forward(p, static_cast<hipStream_t>(hip_stream)));
+    return GNNMP_OK;
+}
+
+// =============================================================================================
+// the NEXT planning network of the arm families (next3d_kernels.hip; next_model/model3D.py:87-213)
+// =============================================================================================
+static bool next3d_dims_ok(int32_t dim, int32_t point_dim) { return dim >= 1 && dim <= 15 && (point_dim == 3 || point_dim == 6); }
+
+extern "C" int gnnmp_next3d_weights_floats(int32_t dim, int32_t point_dim, size_t* n_floats) {
+    if (!n_floats) return GNNMP_ERR_NULL;
+    if (!next3d_dims_ok(dim, point_dim)) return GNNMP_ERR_DIMS;
+    *n_floats = next3d_weights_floats();
+    return GNNMP_OK;
+}
+
+extern "C" int gnnmp_next3d_workspace_bytes(int32_t n_problems, size_t* bytes) {
+    if (!bytes) return GNNMP_ERR_NULL;
+    if (n_problems < 0) return GNNMP_ERR_ARG;
+    *bytes = next3d_workspace_bytes(n_problems);
+    return GNNMP_OK;
+}
+
+extern "C" int gnnmp_next3d_pb_forward(const gnnmp_next3d_pb* d, void* hip_stream) {
+    if (!d) return GNNMP_ERR_NULL;
+    if (!next3d_dims_ok(d->dim, d->point_dim) || d->width != 15) return GNNMP_ERR_DIMS;
+    if (d->n_problems < 0 || d->iters < 0) return GNNMP_ERR_ARG;
+    if (d->workspace_bytes < next3d_workspace_bytes(d->n_problems) || reinterpret_cast<uintptr_t>(d->workspace) % 16) return GNNMP_ERR_ARG;
+    if (!d->maps || !d->goals || !d->weights || !d->pb_rep || !d->workspace) return GNNMP_ERR_NULL;
+    if (d->n_problems == 0) return GNNMP_OK;
+    Next3dPbParams p;
+    p.B = d->n_problems; p.dim = d->dim; p.pd = d->point_dim; p.iters = d->iters;
+    p.maps = d->maps; p.goals = d->goals; p.weights = d->weights; p.pb_rep = d->pb_rep;
+    p.workspace = static_cast<float*>(d->workspace);
+    HIP_TRY(launch_next3d_pb_forward(p, static_cast<hipStream_t>(hip_stream)));
+    return GNNMP_OK;
+}
+
+extern "C" int gnnmp_next3d_state_forward(const gnnmp_next3d_states* d, void* hip_stream) {
+    if (!d) return GNNMP_ERR_NULL;
+    if (!next3d_dims_ok(d->dim, d->point_dim) || d->width != 15) return GNNMP_ERR_DIMS;
+    if (d->n_states < 0 || d->n_problems < 0) return GNNMP_ERR_ARG;
+    if (!d->inputs || !d->problem_of_state || !d->pb_rep || !d->weights || !d->y || !d->status) return GNNMP_ERR_NULL;
+    if (d->n_states == 0) return GNNMP_OK;
+    Next3dStateParams p;
+    p.S = d->n_states; p.B = d->n_problems; p.dim = d->dim; p.pd = d->point_dim;
+    p.inputs = d->inputs; p.problem_of_state = d->problem_of_state; p.pb_rep = d->pb_rep; p.weights = d->weights; p.y = d->y;
+    p.status = d->status;
+    HIP_TRY(launch_next3d_state_forward(p, static_cast<hipStream_t>(hip_stream)));
     return GNNMP_OK;
 }
 

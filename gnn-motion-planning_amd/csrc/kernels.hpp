@@ -354,6 +354,28 @@ hipError_t launch_next_pb_forward(const NextPbParams& p, hipStream_t st);
 hipError_t launch_next_state_forward(const NextStateParams& p, hipStream_t st);
 size_t next_weights_floats();
 
+// ---- the NEXT planning network of the arm families (next3d_kernels.hip, next_model/model3D.py:87-213)
+struct Next3dPbParams {
+    int B, dim, pd, iters;                // problems, state size 1 .. 15, point size 3 / 6, LSTM rounds
+    const float *maps, *goals;            // [B, 15, 15, 15], [B, pd + dim]
+    const float* weights;                 // next3d_weights_floats() packed floats
+    float* pb_rep;                        // out [B, 64, 15, 15, 15]
+    float* workspace;                     // next3d_workspace_bytes(B) bytes, 16-byte aligned
+};
+struct Next3dStateParams {
+    int S, B, dim, pd;                    // states, problems
+    const float* inputs;                  // [S, pd + dim]
+    const int* problem_of_state;          // [S]
+    const float* pb_rep;                  // [B, 64, 15, 15, 15]
+    const float* weights;
+    float* y;                             // out [S, dim + 1]
+    int* status;                          // [2], accumulated: rows outside [0, B), last such row + 1
+};
+hipError_t launch_next3d_pb_forward(const Next3dPbParams& p, hipStream_t st);
+hipError_t launch_next3d_state_forward(const Next3dStateParams& p, hipStream_t st);
+size_t next3d_weights_floats();
+size_t next3d_workspace_bytes(int B);
+
 // ---- NEXT's guided tree loop on maze problems (next_plan_kernels.hip, algorithm/tsa.py:12-81, 141-220)
 struct NextPlanParams {
     RrtParams t;                          // the RRT* fields (the workspace pointers are unused: the node state lives in LDS)

@@ -20,6 +20,8 @@
  *       PPN.pb_forward / PPN.state_forward, batched           next_model/model2D.py:151-210 (calls model2D.py:244, 254)
  *   gnnmp_next_plan / gnnmp_next_plan_max_nodes                                       (ABI 9)
  *       NEXT_plan with a model, batched, one launch            algorithm/tsa.py:12-81, 141-220 (call eval_next.py:65)
+ *   gnnmp_next3d_weights_floats / gnnmp_next3d_workspace_bytes / gnnmp_next3d_pb_forward / gnnmp_next3d_state_forward
+ *       PPN.pb_forward / PPN.state_forward of the arm families, batched   next_model/model3D.py:154-213 (calls model3D.py:251, 265)
  *   gnnmp_graph_workspace_bytes / gnnmp_graph_build
  *       create_data's edge construction                       eval_gnn.py:159-164
  *   gnnmp_maze_sample
@@ -938,6 +940,62 @@ int gnnmp_next_weights_floats(int32_t dim, size_t* n_floats);
  * 2 / 3, width not 15), GNNMP_ERR_ARG (n_problems / n_states < 0, iters < 0), GNNMP_ERR_NULL (an array). */
 int gnnmp_next_pb_forward(const gnnmp_next_pb* desc, void* hip_stream);
 int gnnmp_next_state_forward(const gnnmp_next_states* desc, void* hip_stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The NEXT planning network of the arm families (additive to ABI 9) -- the PPN of next_model/model3D.py:87-213 behind Model3D
+ * (next_7, next_ur5, next_13: point_dim 3; next_14: point_dim 6) with env_width 15 (3375 voxels), cap = g = 8, latent 64.  A
+ * network input row is [point (point_dim), state (dim)]; no coordinate is scaled.  Batched over problems and over states:
+ *   gnnmp_next3d_pb_forward     pb_rep of B problems: the goal attention (1 x 1 x 1-conv MLP (point_dim + 3)-16-16-32-32-64-1 over
+ *                               the voxels, voxel (i, j, k) entering as [point, j, i, k]; softmax over the 3375 voxels, times
+ *                               softmax(dim-64-8 MLP of the state part), in double), hidden (3 x 3 x 3, 9 -> 64), h0 / c0
+ *                               (3 x 3 x 3, 64 -> 64) and `iters` rounds of { conv 3 x 3 x 3 64 -> 64 on h; LSTMCell(64, 64) per
+ *                               voxel }, in exact fp32 MFMA (hidden, h0, c0 and the first round, whose sums reach the hundreds,
+ *                               accumulate on the double-precision MFMA and store fp32).  One launch per stage and per round over (problem, tile of 128
+ *                               voxels); h (double-buffered), c, the hidden layer and the 9-channel input live in `workspace` as
+ *                               channel-last rows, gnnmp_next3d_workspace_bytes(B) bytes (about 3.7 MB a problem), 16-byte
+ *                               aligned, caller-owned, contents undefined before and after the call.
+ *   gnnmp_next3d_state_forward  y = [action mean, value] of S input rows, each read out of its problem's pb_rep through the state
+ *                               attention, the sum over voxels and cap (accumulated in double) and the policy MLP 8-128-64-(dim+1)
+ * Both calls run on hip_stream and do not synchronise or allocate; results are bit-identical from run to run and a problem's
+ * pb_rep does not depend on the batch it is in.
+ *
+ * Packed weights (gnnmp_next3d_weights_floats floats, the same count for every (dim, point_dim);
+ * gnnmp.next_model3d.pack_weights writes them): the attention's six shared layers as [out][in] weight then bias (the first layer's
+ * rows padded to 12 inputs, the last bias padded to 4 floats), its dim-64-8 MLP (first layer [64][16], columns >= dim zero), the
+ * policy MLP (last layer padded to [16][64] + 16), then hidden / h0 / c0 / conv as [27 taps x (cin padded to 16s) / 16][4 column
+ * tiles][64 lanes][4 steps] + 64 biases (tap = (di 3 + dj) 3 + dk) and the LSTM as [8][16][64][4] over K = [input 64 | hidden 64],
+ * N = the 256 gate rows, + 256 summed biases, element order as for gnnmp_next_weights_floats.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct {
+    int32_t n_problems, dim, point_dim, width;   /* B >= 0 (0: nothing is done); 1 <= dim <= 15; point_dim 3 / 6; width 15  */
+    int32_t iters;                       /* LSTM rounds >= 0; the reference runs 20; 0 returns h0                         */
+    const float* maps;                   /* [B, 15, 15, 15]  0 = free                                                      */
+    const float* goals;                  /* [B, point_dim + dim]                                                           */
+    const float* weights;                /* packed, see above                                                              */
+    float* pb_rep;                       /* out [B, 64, 15, 15, 15]: pb_forward(...) viewed as [B, g * cap, ...], c = 8 g + cap */
+    void* workspace;                     /* device memory, 16-byte aligned                                                 */
+    size_t workspace_bytes;              /* >= gnnmp_next3d_workspace_bytes(B)                                             */
+} gnnmp_next3d_pb;
+
+typedef struct {
+    int32_t n_states, n_problems, dim, point_dim, width;   /* S >= 0 (0: nothing is done), B >= 0                          */
+    const float* inputs;                 /* [S, point_dim + dim]                                                           */
+    const int32_t* problem_of_state;     /* [S]  any order, repeats allowed                                                */
+    const float* pb_rep;                 /* [B, 64, 15, 15, 15]                                                            */
+    const float* weights;                /* packed, see above                                                              */
+    float* y;                            /* out [S, dim + 1]: the action mean, then the value                              */
+    int32_t* status;                     /* [2] device-writable, ACCUMULATED (zero it first), as gnnmp_next_states.status  */
+} gnnmp_next3d_states;
+
+/* GNNMP_ERR_NULL (n_floats), GNNMP_ERR_DIMS (dim outside 1 .. 15, point_dim not 3 / 6). */
+int gnnmp_next3d_weights_floats(int32_t dim, int32_t point_dim, size_t* n_floats);
+/* GNNMP_ERR_NULL (bytes), GNNMP_ERR_ARG (n_problems < 0).  Monotone in n_problems. */
+int gnnmp_next3d_workspace_bytes(int32_t n_problems, size_t* bytes);
+/* All argument errors come back before anything is launched, in this order: GNNMP_ERR_NULL (the struct), GNNMP_ERR_DIMS (dim,
+ * point_dim, width not 15), GNNMP_ERR_ARG (n_problems / n_states < 0, iters < 0, workspace_bytes too small, a workspace that is
+ * not 16-byte aligned), GNNMP_ERR_NULL (an array, the workspace included). */
+int gnnmp_next3d_pb_forward(const gnnmp_next3d_pb* desc, void* hip_stream);
+int gnnmp_next3d_state_forward(const gnnmp_next3d_states* desc, void* hip_stream);
 
 /* ------------------------------------------------------------------------------------------
  * NEXT's guided planner on maze problems (ABI 9) -- eval_next.py's NEXT_plan(env, model, T=t_max, g_explore_eps=0.1,
