@@ -23,6 +23,15 @@ constexpr int oW1 = 0, oB1 = oW1 + 64, oW2 = oB1 + 16, oB2 = oW2 + 256, oW3 = oB
 
 __device__ __forceinline__ double relu(double v) { return v > 0. ? v : 0.; }
 
+// The ReLU of the policy MLP: a NaN stays a NaN, as in torch and numpy.  `v > 0 ? v : 0` alone turns it into 0, and a pb_rep
+// that is not finite then reads out as an ordinary value (the last layer's bias) that no status word reports.  Decided and
+// selected on the bits: the build does not honour NaNs in comparisons.  Every other input gives the bits of relu().
+__device__ __forceinline__ double relu_keep_nan(double v) {
+    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
+    const bool nan = (b & 0x7fffffffffffffffull) > 0x7ff0000000000000ull;
+    return __longlong_as_double((long long)((v > 0. || nan) ? b : 0ull));
+}
+
 // the shared 1 x 1-conv MLP of the attention for one cell: input [s0, s1, column, row] -> the logit.  In double: the logits
 // reach tens, so a float32 logit carries an absolute error of 1e-6 and more into exp(), which the 20 recurrent rounds amplify;
 // the MLP is 4 k multiply-adds a cell, nothing next to the convolutions.
@@ -153,7 +162,7 @@ __device__ __forceinline__ void next_state_readout(const float* __restrict__ W, 
     if (tid < 128) {
         double v = (double)W[oPB1 + tid];
         for (int i = 0; i < 8; ++i) v = fma((double)W[oP1 + tid * 8 + i], s.x[i], v);
-        s.h1[tid] = v > 0. ? v : 0.;
+        s.h1[tid] = relu_keep_nan(v);
     }
     __syncthreads();
     {
@@ -163,7 +172,7 @@ __device__ __forceinline__ void next_state_readout(const float* __restrict__ W, 
         v += __shfl_xor(v, 1);
         v += __shfl_xor(v, 2);
         v += (double)W[oPB2 + j];
-        if (part == 0) s.h2[j] = v > 0. ? v : 0.;
+        if (part == 0) s.h2[j] = relu_keep_nan(v);
     }
     __syncthreads();
     if (tid < nout) {

@@ -182,7 +182,6 @@ __global__ __launch_bounds__(kNpThreads) void next_plan_kernel(NextPlanParams p)
             }
             pos += mode == 0 ? 1 : 2 + DIM;
         } else {
-            pos += 2;
             // ---- select (tsa.py:141-165)
             double sc = -INFINITY;
             int id = 0x7fffffff;
@@ -244,6 +243,7 @@ __global__ __launch_bounds__(kNpThreads) void next_plan_kernel(NextPlanParams p)
             if (bad) { status |= 8; break; }
 #pragma unroll
             for (int c = 0; c < DIM; ++c) near[c] = par[c];
+            pos += 2;                                            // only now: an iteration given up with a status consumed nothing
             ++g;
         }
         // ---- env.step(parent, new state): wave 0, then everybody learns the outcome

@@ -1053,7 +1053,8 @@ typedef struct {                         /* all out; rows of a problem behind it
     int32_t* path_len;
     int32_t* status;                     /* [B]  0, or bits: 1 and 2 as gnnmp_rrtstar_tree; 4 = the eps block ended before a
                                           * guided iteration (the tree holds the iterations before it; nothing is read beyond
-                                          * the block); 8 = a score was not finite.  Any of 1, 4, 8 ends the problem        */
+                                          * the block); 8 = a score was not finite.  Any of 1, 4, 8 ends the problem: the
+                                          * tree, `used` and `guided` are those of the iterations before it                 */
     int8_t* expanded_by_rrt;             /* [B, t_max + 1]  1 = goal or RRT step, 0 = guided step, -1 for the root       */
     float* state_values;                 /* [B, t_max + 1]  the network's value of every node                            */
     double* w;                           /* [B, t_max + 1]                                                               */

@@ -195,6 +195,19 @@ def test_two_runs_are_bit_identical(fam):
     fam.net.check_status()
 
 
+def test_the_cached_pb_forward_workspace_carries_nothing_over(fam):
+    """The workspace (h, c and the hidden layer) grows for B = 3 and is then reused by smaller calls with other round counts."""
+    net = nm.NextNet3D(fam.dim, fam.pd).load_state_dict(fam.w)
+    net.pb_forward(_t(fam.maps4[[3, 2, 1]]), _t(fam.goals4[[3, 2, 1]]), iters=2)
+    ws = net._ws[str(torch.device(DEV))]
+    net.pb_forward(_t(fam.maps4[:1]), _t(fam.goals4[:1]), iters=1)
+    used = net.pb_forward(_t(fam.maps4[:1]), _t(fam.goals4[:1]), iters=2)
+    assert net._ws[str(torch.device(DEV))] is ws and ws.numel() >= nm.workspace_bytes(3) > nm.workspace_bytes(1)      # the same buffer
+    fresh = nm.NextNet3D(fam.dim, fam.pd).load_state_dict(fam.w).pb_forward(_t(fam.maps4[:1]), _t(fam.goals4[:1]), iters=2)
+    assert torch.equal(used, fresh)
+    _within(used, fam.pb4_64[:1], fam.own_pb2, 'kuka%d pb_rep iters 2 through a used workspace' % fam.dim)
+
+
 class StubEnv:
     """get_robot_points as a fixed numpy function of the state (the real one is PyBullet's forward kinematics)."""
     RRT_EPS = 0.5

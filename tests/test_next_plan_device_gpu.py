@@ -54,34 +54,43 @@ def _model(dim):
     return _MODELS[dim]
 
 
-def _eps(names, t_max):
+def _eps(names, t_max, k=K, seeds=None):
     dim = int(_load(names[0])['dim'])
-    return next_plan.default_eps([int(_load(n)['seed']) for n in names], t_max, K, dim)
+    return next_plan.default_eps([int(_load(n)['seed']) for n in names] if seeds is None else seeds, t_max, k, dim)
 
 
-def host_run(name, t_max, stop, eps=None):
-    """``plan_host`` on the device model with the noise block the device loop gets (cached for the default block)."""
-    key = (name, t_max, stop)
-    if eps is None and key in _HOST:
+def host_run(name, t_max, stop, eps=None, g_explore_eps=next_plan.G_EXPLORE_EPS, c=1.0, k=K, seed=None, pb_edit=None):
+    """``plan_host`` on the device model with the noise block the device loop gets (cached for the default block).  ``seed``:
+    another ``RandomState`` stream than the recorded one; ``pb_edit``: a function applied to the model's ``pb_rep`` after
+    ``set_problem`` (never cached)."""
+    key = (name, t_max, stop, g_explore_eps, c, k, seed)
+    cached = eps is None and pb_edit is None
+    if cached and key in _HOST:
         return _HOST[key]
     rec = _load(name)
+    seed = int(rec['seed']) if seed is None else int(seed)
     model = _model(int(rec['dim']))
     model.set_problem(_problem(rec))
-    noise = _eps([name], t_max)[0] if eps is None else eps
-    out = next_plan.plan_host(_problem(rec), int(rec['seed']), next_plan.NoiseModel(model, noise), t_max=t_max, stop_when_success=stop, k=K)
+    if pb_edit is not None:
+        model.pb_rep = pb_edit(model.pb_rep)
+    noise = _eps([name], t_max, k, [seed])[0] if eps is None else eps
+    out = next_plan.plan_host(_problem(rec), seed, next_plan.NoiseModel(model, noise), t_max=t_max, g_explore_eps=g_explore_eps,
+                              stop_when_success=stop, c=c, k=k)
     model.check_status()
-    if eps is None:
+    if cached:
         _HOST[key] = out
     return out
 
 
-def device_run(names, t_max, stop, draws='host', cache=True, **kw):
-    key = (tuple(names), t_max, stop, draws)
+def device_run(names, t_max, stop, draws='host', cache=True, g_explore_eps=next_plan.G_EXPLORE_EPS, c=1.0, k=K, seeds=None, **kw):
+    key = (tuple(names), t_max, stop, draws, g_explore_eps, c, k, None if seeds is None else tuple(seeds))
     if cache and not kw and key in _DEVICE:
         return _DEVICE[key]
     recs = [_load(n) for n in names]
-    res = next_plan.plan_maze_batch([_problem(r) for r in recs], DEV, [int(r['seed']) for r in recs], _model(int(recs[0]['dim'])).net,
-                                    t_max=t_max, stop_when_success=stop, draws=draws, eps=kw.pop('eps', _eps(names, t_max)), k=K, **kw)
+    seeds = [int(r['seed']) for r in recs] if seeds is None else [int(s) for s in seeds]
+    eps = kw.pop('eps') if 'eps' in kw else _eps(names, t_max, k, seeds)
+    res = next_plan.plan_maze_batch([_problem(r) for r in recs], DEV, seeds, _model(int(recs[0]['dim'])).net, t_max=t_max,
+                                    stop_when_success=stop, draws=draws, eps=eps, g_explore_eps=g_explore_eps, c=c, k=k, **kw)
     if cache and not kw:
         _DEVICE[key] = res
     return res
