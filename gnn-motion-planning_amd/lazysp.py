@@ -73,18 +73,45 @@ def _bounds(env):
 
 
 def graph_edges(points, k1):
-    """``construct_graph``'s edge set (lazy_sp.py:125-129): [E, 2] (source, target) rows sorted by (source, target)."""
+    """``construct_graph``'s edge set (lazy_sp.py:125-129): [E, 2] (source, target) rows sorted by (source, target).  The k1
+    nearest of a node (itself included) in ascending (squared distance, id) order -- squared distances accumulated coordinate
+    by coordinate in float64 from the float32 coordinates, a stable sort -- so that among equidistant candidates the LOWER id
+    is taken, the rule of the device's graph builder (csrc/graph_kernels.hip gb_knn); ``topk`` leaves that order open."""
     import torch
-    from .graph_build import coalesce, knn_graph
-    e = knn_graph(torch.from_numpy(np.asarray(points, dtype=np.float64).astype(np.float32)), k1)
-    return coalesce(torch.cat((e, e.flip(0)), dim=1), len(points)).numpy().T
+    from .graph_build import coalesce
+    x = np.asarray(points, dtype=np.float64).astype(np.float32).astype(np.float64)
+    n = x.shape[0]
+    d = np.zeros((n, n))
+    for c in range(x.shape[1]):
+        df = x[:, c].reshape(-1, 1) - x[:, c].reshape(1, -1)
+        d = d + df * df
+    nb = np.argsort(d, axis=1, kind='stable')[:, :min(int(k1), n)]
+    centre = np.broadcast_to(np.arange(n).reshape(-1, 1), nb.shape)
+    e = torch.from_numpy(np.stack((nb.reshape(-1), centre.reshape(-1)))).long()
+    return coalesce(torch.cat((e, e.flip(0)), dim=1), n).numpy().T
 
 
-def _dijkstra(cost, early_exit):
+def extract_index(key):
+    """``min_dist(q, dist)`` (dijkstra.py:34-46) on the keys of the unvisited nodes: the first strict minimum as the reference
+    walks its set ``q`` -- ascending ids, as CPython iterates a set of the ints 0 .. n - 1 that were all added before any was
+    removed (each hashes to its own slot) -- so the LOWEST id among equal keys; ``np.argmin``'s first minimum.  (Module level,
+    like the test below, so that a test can swap in another rule.)"""
+    return int(np.argmin(key))
+
+
+def relax_improves(alt, dist):
+    """The relaxation test ``alt < dist[v]`` (dijkstra.py:71), STRICT: of two equally short ways to v the one found first --
+    from the node extracted first -- stays in ``prev``."""
+    return alt < dist
+
+
+def _dijkstra(cost, early_exit, stats=None):
     """``dijkstra(nodes, neighbors, edge_cost, 0)`` on the dense cost matrix (inf = no edge): extraction by (distance, lowest
     id), strict improvement.  With ``early_exit`` the run stops once node 1 is extracted, or at the first infinite minimum
     (nodes at infinite distance relax nothing): extraction keys never decrease under non-negative costs, so neither dist[1] nor
-    prev along node 1's chain can change afterwards."""
+    prev along node 1's chain can change afterwards.  ``stats`` (a dict) counts exact ties: ``extract_ties`` extractions
+    whose finite key more than one unvisited node holds, ``relax_ties`` relaxations of another node with a finite
+    ``alt == dist[v]``."""
     n = cost.shape[0]
     dist = np.full(n, INF)
     prev = np.full(n, -1, dtype=np.int64)
@@ -92,23 +119,29 @@ def _dijkstra(cost, early_exit):
     prev[0] = 0
     key = dist.copy()                      # dist of the unvisited, inf for the visited
     for _ in range(n):
-        u = int(np.argmin(key))            # first minimum = lowest id
+        u = extract_index(key)
         du = key[u]
         if du == INF:
             break
+        if stats is not None:
+            stats['extract_ties'] += int(np.count_nonzero(key == du) > 1)
         key[u] = INF
         if early_exit and u == 1:
             break
         alt = du + cost[u]
-        better = alt < dist
+        better = relax_improves(alt, dist)
+        better[u] = False                  # (the loop edge: alt = du, never below dist[u])
+        if stats is not None:
+            ties = (alt == dist) & (alt < INF)
+            ties[u] = False
+            stats['relax_ties'] += int(ties.sum())
         dist[better] = alt[better]
         prev[better] = u
-        better[u] = False
         key[better] = alt[better]          # an improved node was never visited: alt >= du >= every visited distance
     return dist, prev
 
 
-def plan_host(problem, seed, batch=50, t_max=1000, k=10, early_exit=True):
+def plan_host(problem, seed, batch=50, t_max=1000, k=10, early_exit=True, attempts=None):
     """``np.random.seed(seed); LazySP(env, batch_size=batch, T=t_max, k=k).plan()`` for one maze problem (a dict with ``map``,
     ``init_state``, ``goal_state``; 2 coordinates = point robot, 3 = stick robot), on a private ``RandomState``.  Returns a dict:
     ``samples`` [N, dim] float64; ``checks`` (sampling included); ``path_ids`` (start -> goal, empty when unsolved) and ``path``
@@ -116,15 +149,31 @@ def plan_host(problem, seed, batch=50, t_max=1000, k=10, early_exit=True):
     ``dijkstra_runs``; ``invalid_order`` [m, 2]: the blocked edges (n1, n2) in the order they were found; ``rounds`` [R, 4]:
     N, cumulative checks, unordered valid pairs, unordered invalid pairs after every round.  Two more, for tests that aim at
     a shape: ``walk_edges`` (edges of the path of every Dijkstra run that reached the start) and ``blocked_at`` (position of
-    the blocked edge on the path of every run that found one)."""
+    the blocked edge on the path of every run that found one).  ``checked_order`` [m, 3]: every checked edge (n1, n2, 1 = free / 2 = blocked) in
+    the order of the checks -- the device's pair list.  ``extract_ties`` / ``relax_ties``: the exact ties of all
+    Dijkstra runs, as :func:`_dijkstra` counts them; ``draws``: the draws taken, rejected ones included.  ``attempts``: an ``[n, dim]`` array of raw doubles in [0, 1), one row
+    per draw (``low + row * ranges``), instead of ``RandomState(seed).random_sample(dim)``; ``seed`` is not used then and
+    running out of rows raises."""
     env = _problem_env(problem)
     dim = env.config_dim
     rs = np.random.RandomState(int(seed) & 0xffffffff)
     low, ranges = _bounds(env)
     samples = [np.asarray(env.goal_state, dtype=np.float64).reshape(dim), np.asarray(env.init_state, dtype=np.float64).reshape(dim)]
-    valid, invalid, invalid_order, rounds = set(), set(), [], []
+    valid, invalid, invalid_order, rounds, checked = set(), set(), [], [], []
     runs, T, path = 0, 0, []
     walk_edges, blocked_at = [], []        # per Dijkstra run that reached the start: edges of its path, position of the blocked one
+    ties = dict(extract_ties=0, relax_ties=0, draws=0)
+    if attempts is not None:
+        rows = iter(np.asarray(attempts, dtype=np.float64).reshape(-1, dim))
+
+    def draw():
+        ties['draws'] += 1
+        if attempts is None:
+            return rs.random_sample(dim)
+        row = next(rows, None)
+        if row is None:
+            raise ValueError('lazysp.plan_host: the attempts ran out')
+        return row
 
     def result():
         pts = np.array(samples).reshape(-1, dim)
@@ -133,12 +182,13 @@ def plan_host(problem, seed, batch=50, t_max=1000, k=10, early_exit=True):
                 'path': pts[np.array(path, dtype=np.int64)], 'T': T, 'valid_edges': un(valid), 'invalid_edges': un(invalid),
                 'dijkstra_runs': runs, 'invalid_order': np.array(invalid_order, dtype=np.int64).reshape(-1, 2),
                 'rounds': np.array(rounds, dtype=np.int64).reshape(-1, 4),
-                'walk_edges': np.array(walk_edges, dtype=np.int64), 'blocked_at': np.array(blocked_at, dtype=np.int64)}
+                'walk_edges': np.array(walk_edges, dtype=np.int64), 'blocked_at': np.array(blocked_at, dtype=np.int64),
+                'checked_order': np.array(checked, dtype=np.int64).reshape(-1, 3), **ties}
 
     while T < t_max:
         got = 0
         while got < batch:
-            p = low + rs.random_sample(dim) * ranges
+            p = low + draw() * ranges
             if env._state_fp(p):
                 samples.append(p)
                 got += 1
@@ -150,13 +200,15 @@ def plan_host(problem, seed, batch=50, t_max=1000, k=10, early_exit=True):
             if (int(s), int(t)) not in invalid:
                 cost[t, s] = np.linalg.norm(pts[t] - pts[s])
         while True:
-            dist, prev = _dijkstra(cost, early_exit)
+            dist, prev = _dijkstra(cost, early_exit, ties)
             runs += 1
             if dist[1] == INF:
                 break
             walk = [1]
             while walk[-1] != 0:
                 walk.append(int(prev[walk[-1]]))
+                if len(walk) > n:
+                    raise RuntimeError('lazysp.plan_host: prev holds a cycle (the reference would not return)')
             feasible = True
             walk_edges.append(len(walk) - 1)
             for pos, (n1, n2) in enumerate(zip(walk[:-1], walk[1:])):
@@ -164,9 +216,11 @@ def plan_host(problem, seed, batch=50, t_max=1000, k=10, early_exit=True):
                     continue
                 if env._edge_fp(pts[n1], pts[n2]):
                     valid.update(((n1, n2), (n2, n1)))
+                    checked.append((n1, n2, 1))
                 else:
                     invalid.update(((n1, n2), (n2, n1)))
                     invalid_order.append((n1, n2))
+                    checked.append((n1, n2, 2))
                     cost[n1, n2] = cost[n2, n1] = INF
                     blocked_at.append(pos)
                     feasible = False

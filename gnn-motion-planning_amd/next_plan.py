@@ -28,8 +28,8 @@ of standard normal draws ``eps`` that replaces the global torch generator (:clas
 import numpy as np
 
 from . import maze2d
-from .rrtstar import (MODEL_EPS, RRT_EPS, _problem_env, distances, draws_per_problem, new_stats, next_sample, rewire_last,
-                      sample_bounds)
+from .rrtstar import (MODEL_EPS, RRT_EPS, _problem_env, distances, draws_per_problem, nearest_index, new_stats, next_sample,
+                      rewire_last, sample_bounds, tied_minimum)
 
 G_EXPLORE_EPS = 0.1                    # eval_next.py:62 explore_eps
 POLICY_STD = RRT_EPS * 0.3             # next_model/model2D.py: Model2D's std
@@ -120,17 +120,22 @@ class NoiseModel:
         return [a for a in actions], [None] * k
 
 
-def plan_host(problem, seed, model, t_max=1000, g_explore_eps=G_EXPLORE_EPS, model_eps=MODEL_EPS, stop_when_success=True, c=1.0, k=10):
+def plan_host(problem, seed, model, t_max=1000, g_explore_eps=G_EXPLORE_EPS, model_eps=MODEL_EPS, stop_when_success=True, c=1.0, k=10,
+              raw=None):
     """One maze problem (a dict with ``map``, ``init_state``, ``goal_state``).  Returns the tree fields of
     :func:`gnnmp.rrtstar.plan_host` plus ``expanded_by_rrt`` (int8: 1 / 0, -1 for the root's None), ``state_values`` (float32),
     ``w``, ``w_sum``, ``visits`` and in ``stats`` also ``guided`` (guided iterations), ``guided_collided`` (those whose step
     collided), ``guided_success`` (those that reached the goal region), ``wraps`` (candidate steps that wrapped the angle) and
     ``min_margin`` (the smallest gap between the best and the second-best score over all ``select`` and ``expand`` arg-maxes:
-    how far the run came to a tie that a last-bit difference in ``w`` could flip; inf when no arg-max had two entries)."""
+    how far the run came to a tie that a last-bit difference in ``w`` could flip; inf when no arg-max had two entries).
+    ``raw``: the problem's block of raw doubles instead of ``RandomState(seed).random_sample(...)``, as
+    :func:`gnnmp.rrtstar.plan_host` takes it; the RRT branch counts the same exact ties."""
     env = _problem_env(problem)
     dim = env.config_dim
     low, ranges = sample_bounds(dim)
-    raw = np.random.RandomState(int(seed) & 0xffffffff).random_sample(draws_per_problem(t_max, dim))
+    if raw is None:
+        raw = np.random.RandomState(int(seed) & 0xffffffff).random_sample(draws_per_problem(t_max, dim))
+    raw = np.asarray(raw, dtype=np.float64).reshape(-1)
     goal = np.asarray(env.goal_state, dtype=np.float64).reshape(dim)
     # SearchTree.__init__ with a model (search_tree.py:5-28)
     states = [np.asarray(env.init_state, dtype=np.float64).reshape(dim).copy()]
@@ -180,8 +185,11 @@ def plan_host(problem, seed, model, t_max=1000, g_explore_eps=G_EXPLORE_EPS, mod
             # global_explore (tsa.py:121-139)
             idx = np.array(non_terminal)
             d = distances(np.array(states)[idx], sample, dim)
-            j = int(np.argmin(d))
+            j = nearest_index(d)
             parent = int(idx[j])
+            tied, far = tied_minimum(d, idx)
+            stats['nearest_ties'] += tied
+            stats['nearest_ties_far'] += far
             if d[j] < RRT_EPS:
                 new_state = sample
                 stats['direct_steer'] += 1

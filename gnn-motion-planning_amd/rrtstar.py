@@ -83,6 +83,31 @@ def distances(states, to_state, dim):
     return np.sqrt(np.sum(gap ** 2, axis=-1))
 
 
+def nearest_index(d):
+    """``np.argmin(dists)`` of ``global_explore`` (tsa.py:129): the FIRST minimum, so among equidistant non-terminal nodes the
+    lowest id.  (Module level, like the two tests below, so that a test can swap in another rule.)"""
+    return int(np.argmin(d))
+
+
+def parent_improves(cost_new, min_cost):
+    """Pass 1 of ``RRTS_rewire_last`` (tsa.py:256): a STRICT ``cost_new < min_cost`` against the running minimum -- of two
+    equally cheap parents the earlier one stays, and the later one's edge is not even checked."""
+    return cost_new < min_cost
+
+
+def neighbor_improves(cost_new, cost_j):
+    """Pass 2 of ``RRTS_rewire_last`` (tsa.py:271): a STRICT ``cost_new < costs[j]`` -- a neighbour the new node would reach at
+    exactly its present cost keeps its parent, unchecked."""
+    return cost_new < cost_j
+
+
+def tied_minimum(d, ids):
+    """(tied, far) for the distances ``d`` of the nodes ``ids`` (ascending): more than one node holds the minimum; two of
+    them have ids 64 or more apart (they belong to different strides of a 64-lane scan)."""
+    tied = np.asarray(ids)[np.asarray(d) == np.min(d)]
+    return len(tied) > 1, bool(len(tied) > 1 and tied[-1] - tied[0] >= 64)
+
+
 def rewire_last(env, goal, states, rewired, freesp, in_goal, costs, path_lengths, nearest, stats):
     """``RRTS_rewire_last`` (tsa.py:222-281) on the tree lists, whose last entries are the node just inserted from ``nearest``:
     sets its cost (and ``path_lengths[-1]`` when it is in the goal region), rewires it and then its neighbours, in place.
@@ -109,19 +134,27 @@ def rewire_last(env, goal, states, rewired, freesp, in_goal, costs, path_lengths
     if len(near) > 64:
         stats['max_near_collided'] = max(stats['max_near_collided'], n_coll)
     min_cost, min_j = dists[nearest] + costs[nearest], nearest
+    first_group = None                       # the group of 64 ids that held the first improvement
     for j in near:
         if not freesp[j]:
             continue
         cost_new = dists[j] + costs[j]
-        if cost_new < min_cost and rewire_step(j):
+        if cost_new == min_cost and j != min_j:
+            stats['parent_ties'] += 1
+            stats['parent_ties_late'] += first_group is not None and j // 64 > first_group
+        if parent_improves(cost_new, min_cost) and rewire_step(j):
             min_cost, min_j = cost_new, int(j)
+            if first_group is None:
+                first_group = j // 64
     rewired[-1] = min_j
     costs[-1] = float(min_cost)
     if in_goal[-1] and (path_lengths[-1] < 0 or path_lengths[-1] > min_cost):      # set_cost (search_tree.py:56-63)
         path_lengths[-1] = float(min_cost)
     for j in near:
         cost_new = min_cost + dists[j]
-        if cost_new < costs[j]:
+        if cost_new == costs[j]:
+            stats['rewire_ties'] += 1
+        if neighbor_improves(cost_new, costs[j]):
             if not freesp[j]:
                 stats['collided_second_pass'] += 1
             if rewire_step(j):
@@ -131,10 +164,11 @@ def rewire_last(env, goal, states, rewired, freesp, in_goal, costs, path_lengths
 
 
 def new_stats():
-    return dict(direct_steer=0, collided_second_pass=0, goal_rechecks=0, rewired=0, max_near=0, max_near_collided=0, max_rewire_k=0)
+    return dict(direct_steer=0, collided_second_pass=0, goal_rechecks=0, rewired=0, max_near=0, max_near_collided=0, max_rewire_k=0,
+                nearest_ties=0, nearest_ties_far=0, parent_ties=0, parent_ties_late=0, rewire_ties=0)
 
 
-def plan_host(problem, seed, t_max=1000, stop_when_success=True):
+def plan_host(problem, seed, t_max=1000, stop_when_success=True, raw=None):
     """``np.random.seed(seed); NEXT_plan(env, model=None, T=t_max, g_explore_eps=1., stop_when_success=...)`` for one maze
     problem (a dict with ``map``, ``init_state``, ``goal_state``; 2 coordinates = point robot, 3 = stick robot) on a private
     ``RandomState``.  Returns the whole search tree as a dict: ``states`` [n, dim] float64 (n = iterations run + 1: collided new
@@ -145,11 +179,23 @@ def plan_host(problem, seed, t_max=1000, stop_when_success=True):
     counts what tests aim at: ``direct_steer`` iterations whose sample was within RRT_EPS of the tree, ``collided_second_pass``
     second-pass checks on collided neighbours, ``goal_rechecks`` goal tests inside rewiring that counted a ``_state_fp``,
     ``rewired`` nodes whose parent was changed, ``max_near`` / ``max_near_collided`` neighbours (collided ones) of one
-    iteration and ``max_rewire_k`` interpolated sticks of one rewiring check."""
+    iteration and ``max_rewire_k`` interpolated sticks of one rewiring check.  Exact ties, which random doubles never give and
+    a lattice of draws gives all the time: ``nearest_ties`` iterations whose least distance is held by more than one
+    non-terminal node (``nearest_ties_far``: by nodes with ids 64 or more apart), ``parent_ties`` free near nodes other than
+    the present best parent with ``cost_new == min_cost`` in pass 1 (``parent_ties_late``: those in a later group of 64 ids than
+    the call's first improvement, where a running minimum and one frozen at the start of the group differ), ``rewire_ties`` near nodes with ``cost_new == costs[j]``
+    in pass 2.  ``raw``: the problem's block of raw doubles (``draws_per_problem`` of them) instead of
+    ``RandomState(seed).random_sample(...)``; ``seed`` is not used then."""
     env = _problem_env(problem)
     dim = env.config_dim
     low, ranges = sample_bounds(dim)
-    raw = np.random.RandomState(int(seed) & 0xffffffff).random_sample(draws_per_problem(t_max, dim))
+    if raw is None:
+        raw = np.random.RandomState(int(seed) & 0xffffffff).random_sample(draws_per_problem(t_max, dim))
+    else:
+        raw = np.asarray(raw, dtype=np.float64).reshape(-1)
+        if raw.shape[0] < draws_per_problem(t_max, dim):
+            raise ValueError('rrtstar.plan_host: raw holds %d doubles, %d iterations can draw %d'
+                             % (raw.shape[0], t_max, draws_per_problem(t_max, dim)))
     goal = np.asarray(env.goal_state, dtype=np.float64).reshape(dim)
     # search_tree.py:5-19
     states = [np.asarray(env.init_state, dtype=np.float64).reshape(dim).copy()]
@@ -162,8 +208,11 @@ def plan_host(problem, seed, t_max=1000, stop_when_success=True):
         # global_explore (tsa.py:121-139)
         idx = np.flatnonzero(np.array(freesp) & ~np.array(in_goal))
         d = distances(np.array(states)[idx], sample, dim)
-        k = int(np.argmin(d))
+        k = nearest_index(d)
         nearest = int(idx[k])
+        tied, far = tied_minimum(d, idx)
+        stats['nearest_ties'] += tied
+        stats['nearest_ties_far'] += far
         if d[k] < RRT_EPS:                   # RRT_steer (tsa.py:97-101)
             new_state = sample
             stats['direct_steer'] += 1

@@ -58,9 +58,10 @@ def test_plan_maze_batch_equals_reference(group, draws):
         assert_same_plan(got, rec, '%s (%s draws)' % (name, draws))
 
 
-def run_abi(rec, pair_cap=None, spare_slot=False):
+def run_abi(rec, pair_cap=None, spare_slot=False, attempts=None):
     """The rounds of one recorded problem through the C entry points with an explicit host loop (slot 0 of the store; with
-    ``spare_slot`` a second slot that no call touches, its arrays filled with a sentinel).  Returns (result dict, store)."""
+    ``spare_slot`` a second slot that no call touches, its arrays filled with a sentinel).  ``attempts``: [n, dim] raw doubles
+    that take the place of the seed's stream, one row a draw (``low + row * ranges``).  Returns (result dict, store)."""
     dim, batch, t_max, k = settings_of(rec)
     B = 2 if spare_slot else 1
     R = lazysp.n_rounds(batch, t_max)
@@ -80,18 +81,20 @@ def run_abi(rec, pair_cap=None, spare_slot=False):
     active = torch.tensor([1] + [0] * (B - 1), dtype=torch.uint8, device=DEV)
     slot_of = torch.zeros(1, dtype=torch.int32, device=DEV)
     rs, buf = np.random.RandomState(int(rec['seed'])), np.zeros((0, dim))
-    rounds = 0
+    if attempts is not None:
+        rs, buf = None, -limits + np.asarray(attempts, dtype=np.float64) * (limits - (-limits))
+    rounds, rows = 0, []
     for r in range(1, R + 1):
         want = 64
         while True:
-            if buf.shape[0] < want:
+            if rs is not None and buf.shape[0] < want:
                 buf = np.concatenate((buf, rs.uniform(-limits, limits, (want - buf.shape[0], dim))))
             att_ptr = np.array([0] + [buf.shape[0]] * B, dtype=np.int64)
             used, _, status = lazysp.lazysp_sample(store, torch.from_numpy(buf).to(DEV), att_ptr, maps, init64, goal64, batch, active=active)
             if int(status[0]) == 0:
                 buf = buf[int(used[0]):]
                 break
-            assert int(status[0]) == 1 and int(used[0]) == 0
+            assert int(status[0]) == 1 and int(used[0]) == 0 and rs is not None
             want *= 2
         g = lazysp.lazysp_gather(store, slot_of, k1_table, 2 + r * batch)
         assert g['node_ptr'].tolist() == [0, 2 + r * batch] and g['n_free'].tolist() == [2 + r * batch]
@@ -101,6 +104,8 @@ def run_abi(rec, pair_cap=None, spare_slot=False):
         lazysp.lazysp_round(store, None, ei, edge_ptr, maps)
         torch.cuda.synchronize()
         rounds = r
+        state = store.pair_state[0, :int(store.n_pairs[0])]
+        rows.append((int(store.n_nodes[0]), int(store.checks[0]), int((state == 1).sum()), int((state == 2).sum())))
         if int(store.solved[0]) or int(store.status[0]):
             break
     n, npairs, plen = int(store.n_nodes[0]), int(store.n_pairs[0]), int(store.path_len[0])
@@ -110,7 +115,8 @@ def run_abi(rec, pair_cap=None, spare_slot=False):
     return {'samples': pts, 'checks': int(store.checks[0]), 'path_ids': ids, 'path': pts[ids], 'T': rounds * batch,
             'valid_edges': lazysp._unordered(pairs[st == 1]), 'invalid_edges': lazysp._unordered(pairs[st == 2]),
             'dijkstra_runs': int(store.dijkstra_runs[0]), 'invalid_order': pairs[st == 2].astype(np.int64).reshape(-1, 2),
-            'status': int(store.status[0]), 'n_pairs': npairs, 'pairs': pairs}, store
+            'status': int(store.status[0]), 'n_pairs': npairs, 'pairs': pairs, 'pair_state': st,
+            'rounds': np.array(rows, dtype=np.int64).reshape(-1, 4)}, store
 
 
 @pytest.mark.parametrize('name', ['maze2_b20_t100_i3', 'maze3_round1_i6', 'maze2_firstinf_i0', 'maze2_b1_t6_i1'])

@@ -11,7 +11,9 @@ from gnnmp import rrtstar
 from gnnmp.maze2d import Maze2D, Maze3D
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
-CASES = sorted(os.path.basename(p)[len('rrtstar_'):-len('.npz')] for p in glob.glob(os.path.join(GOLDEN, 'rrtstar_*.npz')))
+# (the rrtstar_lattice_* fixtures hold crafted draw blocks, no seed: tests/test_rrtstar_ties_host.py)
+CASES = sorted(os.path.basename(p)[len('rrtstar_'):-len('.npz')] for p in glob.glob(os.path.join(GOLDEN, 'rrtstar_*.npz'))
+               if not os.path.basename(p).startswith('rrtstar_lattice_'))
 _HOST = {}
 
 

@@ -11,6 +11,12 @@ cumulated_collision_checks), success, the returned i, the node ids of search_tre
 (np.random.rand and env.uniform_sample wrapped at run time).  Printed per case, and stored: iterations that took the
 direct-steer branch, second-pass checks on collided neighbours, goal tests inside rewiring that counted a _state_fp, nodes
 whose rewired parent differs from the parent they were grown from.
+
+rrtstar_lattice_*.npz: the same reference on a crafted block of raw doubles instead of a seed's -- multiples of 1/64, fed through
+the same two wrappers -- so that x and y are multiples of 1/32, below RRT_EPS: samples next to the tree are taken as they are,
+the tree grows on the lattice, and equal distances and equal costs are equal bit for bit.  These files hold the block
+(``raw``) and, from gnnmp.rrtstar.plan_host on the same block once its tree equals the reference's in every field, the tie
+counters (nearest_ties, nearest_ties_far, parent_ties, parent_ties_late, rewire_ties).  They cannot be redrawn from a seed.
 """
 import os
 import sys
@@ -27,14 +33,16 @@ import numpy as np  # noqa: E402
 os.chdir(REF)
 import algorithm.tsa as tsa  # noqa: E402
 from environment import MazeEnv  # noqa: E402
+from environment.maze_env import LIMITS  # noqa: E402
 
 OUT = os.path.join(REPO, 'tests', 'golden')
 
 
-def run(env, idx, seed, t_max, stop=True):
+def run(env, idx, seed, t_max, stop=True, raw=None):
     np.random.seed(seed)
     env.init_new_problem(idx)
     dim = env.dim
+    fed = [0]                                # doubles of ``raw`` handed out
     count = dict(draws=0, direct=0, collided2=0, goal_rechecks=0, rewired=0)
     state = dict(in_rewire=False, tree=None)
     real_rand, real_uniform, real_steer, real_rewire = np.random.rand, env.uniform_sample, tsa.RRT_steer, tsa.RRTS_rewire_last
@@ -42,10 +50,19 @@ def run(env, idx, seed, t_max, stop=True):
 
     def rand(*a):
         count['draws'] += 1
+        if raw is not None:
+            assert not a
+            fed[0] += 1
+            return float(raw[fed[0] - 1])
         return real_rand(*a)
 
     def uniform(*a, **kw):
         count['draws'] += dim
+        if raw is not None:                  # np.random.uniform(-LIMITS, LIMITS) = low + (high - low) * d on the block's doubles
+            assert not a and not kw
+            lim = np.asarray(LIMITS[:dim], dtype=np.float64)
+            fed[0] += dim
+            return -lim + (lim - (-lim)) * raw[fed[0] - dim:fed[0]]
         return real_uniform(*a, **kw)
 
     def steer(env_, sample_state, nearest, dist):
@@ -117,7 +134,99 @@ def record(name, dim, rec):
                                     rec['goal_rechecks'], rec['rewired'], rec['second_pass_rewires'], os.path.getsize(path) / 1024))
 
 
+class CraftedEnv:
+    """A one-problem MazeEnv look-alike over the reference's own checker: a crafted map with start and goal."""
+
+    def __new__(cls, dim, grid, start, goal):
+        env = MazeEnv(dim=dim, map_file='maze_files/mazes_hard.npz' if dim == 2 else 'maze_files/mazes_hard_3.npz')
+        env.maps = np.asarray(grid, dtype=env.maps.dtype)[None]
+        env.init_states = np.asarray(start, dtype=np.float64)[None]
+        env.goal_states = np.asarray(goal, dtype=np.float64)[None]
+        env.size, env.order, env.episode_i = 1, [0], 0
+        return env
+
+
+Z_STEPS = (0, 1, 2, 3, 61, 62, 63)           # z = -0.4 + 0.8 * s / 64: four values up from -0.4, three down from +0.4 (the wrap)
+
+
+def lattice_block(t_max, dim, h, seed):
+    """[t_max, 2 + dim] raw doubles, all multiples of 1/64: the two rand() of an iteration are 0.5 (no goal sample), x and y
+    uniform over the (2h + 1)^2 lattice points round (0, 0), the stick's angle over Z_STEPS.
+    t_max = 70, a tree too small for two equidistant nodes 64 ids apart to turn up by chance, has them placed (lattice
+    units, angle -0.4): iterations 0 .. 3 grow nodes 1 .. 4 at (-1, 0) .. (-4, 0), the random ones in between stay at x >= 0,
+    iteration 67 grows node 68 at (-3, 1) from node 3, and the sample (-4, 1) of iteration 68 is 1 away from node 4 and from
+    node 68 and sqrt(2) from the next ones."""
+    rs = np.random.RandomState(seed)
+    raw = np.full((t_max, 2 + dim), 0.5)
+    xy = rs.randint(-h, h + 1, (t_max, 2))
+    z = rs.choice(Z_STEPS, t_max)
+    if t_max == 70:
+        xy[:, 0] = np.abs(xy[:, 0])
+        placed = {0: (-1, 0), 1: (-2, 0), 2: (-3, 0), 3: (-4, 0), 67: (-3, 1), 68: (-4, 1)}
+        for i, p in placed.items():
+            xy[i], z[i] = p, 0
+    raw[:, 2:4] = (32 + xy) / 64.0
+    if dim == 3:
+        raw[:, 4] = z / 64.0
+    return raw.reshape(-1)
+
+
+def lattice_cases():
+    """(name, dim, map, t_max, half-width of the window): start (0, 0[, -0.4]), goal at the window's corner of the small trees.
+    ``pocket``: four cells blocked diagonally off the start inside the window, so collided nodes pile up next to free ones."""
+    lds = rrtstar_lds_nodes()
+    free, pocket = np.zeros((15, 15)), np.zeros((15, 15))
+    pocket[8, 8] = pocket[6, 6] = pocket[8, 6] = pocket[6, 8] = 1
+    for dim in (2, 3):
+        for t_max, h in ((70, 4), (300, 6), (lds - 2, 10), (lds, 10)):
+            yield 'maze%d_t%d' % (dim, t_max), dim, free, t_max, h
+        yield 'maze%d_pocket_t300' % dim, dim, pocket, 300, 8
+
+
+def rrtstar_lds_nodes():
+    """gnnmp.rrtstar.lds_nodes() without the library: kRrtLdsNodes of csrc/rrtstar_kernels.hip."""
+    import re
+    with open(os.path.join(REPO, 'gnn-motion-planning_amd', 'csrc', 'rrtstar_kernels.hip')) as f:
+        return int(re.search(r'constexpr int kRrtLdsNodes = (\d+);', f.read()).group(1))
+
+
+def lattice_main():
+    sys.path.insert(0, REPO)
+    from gnnmp import rrtstar
+    fields = rrtstar.TREE_FIELDS
+    for name, dim, grid, t_max, h in lattice_cases():
+        start = (0.0, 0.0) if dim == 2 else (0.0, 0.0, -0.4)
+        goal = (0.25, 0.25) if dim == 2 else (0.25, 0.25, -0.4)
+        env = CraftedEnv(dim, grid, start, goal)
+        problem = dict(map=np.asarray(grid, dtype=np.float64), init_state=np.array(start), goal_state=np.array(goal))
+        raw = lattice_block(t_max, dim, h, 100 * dim + t_max)
+        host = rrtstar.plan_host(problem, 0, t_max=t_max, stop_when_success=False, raw=raw)
+        rec = run(env, 0, 0, t_max, stop=False, raw=raw)
+        for key in fields:                   # the counters below are the host's: only where it IS the reference's run
+            a, b = np.asarray(host[key]), np.asarray(rec[key])
+            assert a.shape == b.shape and np.array_equal(a, b), '%s: plan_host differs from the reference in %s' % (name, key)
+        st = host['stats']
+        assert st['direct_steer'] == rec['direct_steer'] and st['rewired'] == rec['second_pass_rewires']
+        ties = {k: int(st[k]) for k in ('nearest_ties', 'nearest_ties_far', 'parent_ties', 'parent_ties_late', 'rewire_ties')}
+        assert all(v > 0 for k, v in ties.items() if k != 'parent_ties_late' or (t_max >= 300 and 'pocket' not in name)), (name, ties)
+        on_lattice = float(np.mean(np.all(rec['states'][:, :2] * 32 == np.round(rec['states'][:, :2] * 32), axis=1)))
+        z = rec['states'][:, 2] if dim == 3 else np.zeros(len(rec['states']))
+        wrap_edges = int(np.sum(np.abs(z[1:] - z[rec['parents'][1:]]) > 0.4))
+        rec.pop('first_rand')
+        rec.update(raw=raw, lattice=True, window=h, max_near=int(st['max_near']), wrap_edges=wrap_edges, **ties)
+        path = os.path.join(OUT, 'rrtstar_lattice_%s.npz' % name)
+        np.savez_compressed(path, dim=dim, **rec)
+        print('lattice_%-20s n=%4d checks=%6d success=%d direct_steer=%4d collided_2nd_pass=%3d goal_rechecks=%3d rewired=%3d max_near=%3d '
+              'on_lattice=%.2f wrap_edges=%3d %s  %5.1f KB' % (name, rec['states'].shape[0], rec['cumulated_collision_checks'][-1],
+                                                             rec['success'], rec['direct_steer'], rec['collided_second_pass'],
+                                                             rec['goal_rechecks'], rec['rewired'], st['max_near'], on_lattice, wrap_edges,
+                                                             ' '.join('%s=%d' % kv for kv in ties.items()), os.path.getsize(path) / 1024),
+              flush=True)
+
+
 def main():
+    if sys.argv[1:] == ['lattice']:          # only the crafted cases (the seed-driven ones below take minutes)
+        return lattice_main()
     envs = {2: MazeEnv(dim=2, map_file='maze_files/mazes_hard.npz'), 3: MazeEnv(dim=3, map_file='maze_files/mazes_hard_3.npz')}
 
     def first(dim, t_max, want, what, start=0, stop=True, seed_of=lambda idx: 1000 + idx, n=1):      # noqa: E731
@@ -154,6 +263,7 @@ def main():
     # the very first rand() is below model_eps: the first sample is the goal state
     seed = next(s for s in range(1000, 3000) if np.random.RandomState(s).random_sample() < 0.05)
     record('maze2_t100_firstgoal_s%d' % seed, 2, run(envs[2], 1, seed, 100))
+    lattice_main()
 
 
 if __name__ == '__main__':
