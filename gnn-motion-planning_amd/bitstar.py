@@ -39,9 +39,11 @@ import math
 
 import numpy as np
 
-from . import maze2d
+from .streams_batch import (AttemptBlocks, StageClock, bounds, check_stream_args, eval_chunks, maze_class, maze_streams_batch,
+                            problem_env, problem_tensors, stream_ptr)
 
 INF = float('inf')
+_maze_class = maze_class               # the name a test reaches for: the shared definition, not a copy
 ETA = 1.1                              # bit_star.py:51
 # scipy.special.gamma(dim / 2 + 1) at dim 2 and 3, the values radius_init divides by (math.gamma(2.5) is one ulp above)
 UNIT_BALL_GAMMA = {2: 1.0, 3: 1.329340388179137}
@@ -55,27 +57,6 @@ DEFAULT_EDGE_CAP_PER_NODE = 2
 
 FIELDS = ('points', 'vertices', 'parents', 'g', 'samples_left', 'checks', 'g_goal', 'T', 'path_ids', 'draws')
 STATS = ('vertex_expansions', 'edge_pops', 'edge_checks', 'rewired', 'filtered', 'max_edge_queue', 'ties_at_pop')
-
-
-def _maze_class(dim):
-    if dim == 2:
-        return maze2d.Maze2D
-    if dim == 3:
-        return maze2d.Maze3D
-    raise ValueError('bitstar: maze problems have 2 (point robot) or 3 (stick robot) coordinates')
-
-
-def _problem_env(problem):
-    init = np.asarray(problem['init_state'], dtype=np.float64).reshape(-1)
-    env = _maze_class(init.shape[0])(np.asarray(problem['map'])[None], init[None],
-                                     np.asarray(problem['goal_state'], dtype=np.float64).reshape(1, -1))
-    env.init_new_problem(0)
-    return env
-
-
-def _bounds(bound):
-    b = np.array(bound, dtype=np.float64).reshape((2, -1)).T               # bit_star.py:32-34
-    return b[:, 0].copy(), b[:, 1] - b[:, 0]
 
 
 def n_batches(batch, t_max):
@@ -97,7 +78,7 @@ def radius_of(dim, ranges, n_free, n_collision, q):
 def radius_by_batch(dim, batch, used_by_batch):
     """``r`` after every batch from the cumulative attempts of the sampling: after batch k (1-based) ``n_free_points`` is
     ``2 + k * batch``, ``n_collision_points`` the rejected draws so far and ``q`` the same ``2 + k * batch``."""
-    _, ranges = _bounds(_maze_class(dim)(np.zeros((1, 1, 1)), np.zeros((1, dim)), np.zeros((1, dim))).bound)
+    _, ranges = bounds(maze_class(dim, 'bitstar')(np.zeros((1, 1, 1)), np.zeros((1, dim)), np.zeros((1, dim))).bound)
     out = np.zeros(len(used_by_batch), dtype=np.float64)
     for k, used in enumerate(used_by_batch, start=1):
         free = 2 + k * int(batch)
@@ -119,10 +100,10 @@ def plan_host(problem, seed, batch=50, t_max=1000, pool=None):
 
     ``pool=(points_per_batch, r_by_batch)`` replaces the sampling: batch k appends ``points_per_batch[k]`` unchecked and uses
     ``r_by_batch[k]``.  Raises where the reference would leave the first-solution search (refinement) or could not run."""
-    env = _problem_env(problem)
+    env = problem_env(problem, 'bitstar')
     dim = env.config_dim
     batch, t_max = int(batch), int(t_max)
-    low, ranges = _bounds(env.bound)
+    low, ranges = bounds(env.bound)                  # bit_star.py:32-34
     rs = np.random.RandomState(int(seed) & 0xffffffff)
     start, goal = tuple(np.asarray(env.init_state, dtype=np.float64).reshape(dim)), tuple(np.asarray(env.goal_state, dtype=np.float64).reshape(dim))
     if start == goal:
@@ -272,11 +253,6 @@ def default_edge_cap(n_nodes):
     return max(min(DEFAULT_EDGE_CAP_PER_NODE * n, n * (n - 1)), 1)
 
 
-def _stream(dev):
-    import torch
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
 def bitstar_sample(attempts, att_ptr_host, maps, init64, goal64, batch, nb, pool, used, checks, status, active=None):
     """``gnnmp_bitstar_sample``: the ``nb * batch`` free draws of every active problem from its own block ``[att_ptr[b],
     att_ptr[b + 1])`` of ``attempts`` (float64 ``[M, dim]``, device) into ``pool`` ``[B, rows, dim]`` behind start and goal,
@@ -286,15 +262,10 @@ def bitstar_sample(attempts, att_ptr_host, maps, init64, goal64, batch, nb, pool
     import torch
     from . import _lib
     dev = pool.device
-    att_ptr_host = np.ascontiguousarray(att_ptr_host, dtype=np.int64)
-    att_ptr = torch.from_numpy(att_ptr_host).to(dev)
-    attempts = attempts.contiguous()
-    sb = _lib.MazeStreamsBatch(int(pool.shape[0]), int(maps.shape[1]), int(batch), int(pool.shape[1]), int(attempts.shape[0]),
-                               attempts.data_ptr(), att_ptr.data_ptr(), att_ptr_host.ctypes.data, maps.data_ptr(), init64.data_ptr(),
-                               goal64.data_ptr(), active.data_ptr() if active is not None else None)
+    sb, keep = maze_streams_batch(pool.shape[0], maps.shape[1], batch, pool.shape[1], attempts, att_ptr_host, maps, init64, goal64, active)
     with torch.cuda.device(dev):
         _lib.check(_lib.lib().gnnmp_bitstar_sample(ctypes.byref(sb), int(pool.shape[2]), int(nb), pool.data_ptr(), used.data_ptr(),
-                                                   checks.data_ptr(), status.data_ptr(), _stream(dev)), 'gnnmp_bitstar_sample')
+                                                   checks.data_ptr(), status.data_ptr(), stream_ptr(dev)), 'gnnmp_bitstar_sample')
 
 
 def bitstar_plan(maps, pool, r_by_batch, checks_by_batch, batch, nb, edge_cap=None, flags=0):
@@ -321,7 +292,7 @@ def bitstar_plan(maps, pool, r_by_batch, checks_by_batch, batch, nb, edge_cap=No
     result = _lib.BITStarResult(*(out[k].data_ptr() for k in ('g', 'parents', 'vertices', 'path')),
                                 *(out['small'][r].data_ptr() for r in range(5)), out['counters'].data_ptr())
     with torch.cuda.device(dev):
-        _lib.check(L.gnnmp_bitstar_plan(ctypes.byref(batch_s), ctypes.byref(result), ws.data_ptr(), ws.numel(), _stream(dev)),
+        _lib.check(L.gnnmp_bitstar_plan(ctypes.byref(batch_s), ctypes.byref(result), ws.data_ptr(), ws.numel(), stream_ptr(dev)),
                    'gnnmp_bitstar_plan')
     out['workspace'] = ws
     return out
@@ -360,81 +331,38 @@ def plan_maze_batch(problems, device, seeds, batch=50, t_max=1000, draws='host',
     that fills it is run again, alone, with the provable bound ``N (N - 1)`` -- the same computation, it has its own stream.
     Returns one dict per problem with :func:`plan_host`'s fields plus ``success`` and ``status`` (0 = fine; a loop bound or a
     bad table raises)."""
-    import time
     import torch
-
-    def mark(name, t_prev):
-        if timings is None:
-            return t_prev
-        torch.cuda.current_stream().synchronize()
-        now = time.perf_counter()
-        timings[name] = timings.get(name, 0.) + now - t_prev
-        return now
+    who = 'bitstar.plan_maze_batch'
     B, batch, t_max = len(problems), int(batch), int(t_max)
     if B == 0:
         return []
-    if len(seeds) != B:
-        raise ValueError('bitstar.plan_maze_batch: one seed per problem')
+    check_stream_args(B, seeds, draws, who)
     if batch < 1 or t_max < 1:
         raise ValueError('bitstar.plan_maze_batch: batch >= 1 and t_max >= 1')
-    if draws not in ('host', 'device'):
-        raise ValueError("bitstar.plan_maze_batch: draws is 'host' or 'device'")
     dev = torch.device(device)
-    dims = {int(np.asarray(pr['init_state']).reshape(-1).shape[0]) for pr in problems}
-    if len(dims) != 1:
-        raise ValueError('bitstar.plan_maze_batch: point-robot and stick-robot problems in one batch')
-    dim = dims.pop()
-    limits = np.asarray(_maze_class(dim).SAMPLE_LIMITS, dtype=np.float64)
     nb = n_batches(batch, t_max)
     total, rows = nb * batch, 2 + nb * batch
-    f64 = lambda key: torch.from_numpy(np.ascontiguousarray(np.asarray(        # noqa: E731
-        [np.asarray(pr[key], dtype=np.float64).reshape(-1) if key != 'map' else np.asarray(pr[key], dtype=np.float64) for pr in problems]))).to(dev)
-    tm = time.perf_counter()
+    clock = StageClock(timings)
     with torch.cuda.device(dev):
-        maps, init64, goal64 = f64('map'), f64('init_state'), f64('goal_state')
+        dim, maps, init64, goal64 = problem_tensors(problems, dev, who)
+        _, ranges = bounds(maze_class(dim, 'bitstar')(np.zeros((1, 1, 1)), np.zeros((1, dim)), np.zeros((1, dim))).bound)
         pool = torch.zeros(B, rows, dim, dtype=torch.float64, device=dev)
         used_d = torch.zeros(B, nb, dtype=torch.int64, device=dev)
         schecks_d = torch.zeros(B, nb, dtype=torch.int64, device=dev)
         status_d = torch.zeros(B, dtype=torch.int32, device=dev)
-        if draws == 'device':
-            from .rng import MTStreams
-            streams = MTStreams(seeds, dev)
-        else:
-            gens = [np.random.RandomState(int(s) & 0xffffffff) for s in seeds]
-            bufs = [np.zeros((0, dim))] * B
-        # ---- sampling: a block per problem from its own generator, longer for whoever ran out
-        pending, want = np.arange(B), int(total * _DRAWS_PER_FREE[dim - 2] * 1.25) + 64
-        while pending.size:
-            mask = np.zeros(B, dtype=np.uint8)
-            mask[pending] = 1
-            mask_d = torch.from_numpy(mask).to(dev)
-            counts = np.zeros(B, dtype=np.int64)
-            counts[pending] = want
-            att_ptr = np.zeros(B + 1, dtype=np.int64)
-            att_ptr[1:] = np.cumsum(counts)
-            if draws == 'device':
-                att, gstat = streams.uniform(counts, -limits, limits, out_ptr=att_ptr, active=mask_d)      # not committed
-            else:
-                for i in pending:
-                    bufs[i] = np.concatenate((bufs[i], gens[i].uniform(-limits, limits, (want - bufs[i].shape[0], dim))))
-                att = torch.from_numpy(np.concatenate([bufs[i] for i in pending])).to(dev)
+        blocks = AttemptBlocks(seeds, dim, dev, draws, _DRAWS_PER_FREE)
+
+        def sample(att, att_ptr, mask_d):
             bitstar_sample(att, att_ptr, maps, init64, goal64, batch, nb, pool, used_d, schecks_d, status_d, active=mask_d)
-            if draws == 'device':
-                status_h, gstat_h = torch.stack((status_d, gstat)).cpu().numpy()
-                if gstat_h[pending].any():
-                    raise RuntimeError('gnnmp_mt19937_uniform: status for problem(s) %s' % pending[gstat_h[pending] != 0].tolist())
-            else:
-                status_h = status_d.cpu().numpy()
-            if (status_h[pending] > 1).any():
-                raise RuntimeError('gnnmp_bitstar_sample: attempt block outside the buffer for problem(s) %s'
-                                   % pending[status_h[pending] > 1].tolist())
-            pending = pending[status_h[pending] == 1]
-            want *= 2
+            return (status_d,)
+        # ---- sampling: a block per problem from its own generator, longer for whoever ran out.  The sampler starts over on a
+        # longer block, so nothing is committed here: the streams move below, by what each problem's search reached
+        blocks.run(np.arange(B), total, sample, commit=False,
+                   no_room='gnnmp_bitstar_sample: attempt block outside the buffer for problem(s) %s')
         used, schecks = torch.stack((used_d, schecks_d)).cpu().numpy()     # the one readback between the two launches
-        _DRAWS_PER_FREE[dim - 2] = max(1.5, 0.5 * _DRAWS_PER_FREE[dim - 2] + 0.5 * float(used[:, -1].mean()) / total)
-        tm = mark('sampling', tm)
+        blocks.update_estimate(float(used[:, -1].mean()), total)
+        clock.mark('sampling')
         cache, r_tab = {}, np.zeros((B, nb), dtype=np.float64)
-        _, ranges = _bounds(_maze_class(dim)(np.zeros((1, 1, 1)), np.zeros((1, dim)), np.zeros((1, dim))).bound)
         for b in range(B):
             for k in range(1, nb + 1):
                 key = (k, int(used[b, k - 1]))
@@ -443,9 +371,9 @@ def plan_maze_batch(problems, device, seeds, batch=50, t_max=1000, draws='host',
                     cache[key] = radius_of(dim, ranges, free, key[1] - k * batch, free)
                 r_tab[b, k - 1] = cache[key]
         r_tab_d = torch.from_numpy(r_tab).to(dev)
-        tm = mark('radius', tm)
+        clock.mark('radius')
         out = bitstar_plan(maps, pool, r_tab_d, schecks_d, batch, nb, edge_cap=edge_cap)
-        tm = mark('plan', tm)
+        clock.mark('plan')
         small, counters = out['small'].cpu().numpy(), out['counters'].cpu().numpy()
         host = {k: out[k].cpu().numpy() for k in ('g', 'parents', 'vertices', 'path')}
         pool_h = pool.cpu().numpy()
@@ -460,10 +388,10 @@ def plan_maze_batch(problems, device, seeds, batch=50, t_max=1000, draws='host',
     if draws == 'device':
         with torch.cuda.device(dev):
             reached = np.array([int(used[b, res[b]['T'] // batch - 1]) for b in range(B)], dtype=np.int32)
-            streams.advance(reached, dim)                        # by the attempts of the batches each problem reached
+            blocks.streams.advance(reached, dim)                        # by the attempts of the batches each problem reached
         if streams_out is not None:
-            streams_out.append(streams)
-    mark('results', tm)
+            streams_out.append(blocks.streams)
+    clock.mark('results')
     return res
 
 
@@ -481,18 +409,13 @@ def eval_bit_device(env, indexes, seed=1234, seeds=None, batch=50, t_max=1000, d
     """The tuple of the reference's ``eval_bit.eval_bit`` without its wall-clock entries, from :func:`plan_maze_batch`, ``chunk``
     problems per launch: ``(n_success, collision, solution_cost, paths)`` -- see :func:`eval_aggregate`; ``paths`` are the
     float64 states of ``get_best_path()``.  Problem ``indexes[i]`` draws from ``np.random.RandomState(seeds[i])``; default
-    :func:`gnnmp.planner.stream_seeds`.  The numbers DIFFER from ``eval_bit``'s, which walks ONE global stream problem after
+    :func:`gnnmp.streams_batch.stream_seeds`.  The numbers DIFFER from ``eval_bit``'s, which walks ONE global stream problem after
     problem -- other samples of the same distribution -- and in exchange they do not depend on the order of ``indexes`` or on
     ``chunk``.  ``rows_out``: a list that receives per problem (success, checks, g_goal, vertices, N, T).  The global numpy
     generator is left alone."""
-    from .planner import stream_seeds
-    indexes = list(indexes)
-    seeds = stream_seeds(seed, indexes) if seeds is None else list(seeds)
     results = []
-    for c0 in range(0, len(indexes), max(int(chunk), 1)):
-        part = indexes[c0:c0 + max(int(chunk), 1)]
-        pr = [dict(map=env.maps[i], init_state=env.init_states[i], goal_state=env.goal_states[i]) for i in part]
-        results.extend(plan_maze_batch(pr, device, seeds[c0:c0 + len(part)], batch=batch, t_max=t_max, draws=draws, timings=timings))
+    for pr, chunk_seeds in eval_chunks(env, indexes, seed, seeds, chunk):
+        results.extend(plan_maze_batch(pr, device, chunk_seeds, batch=batch, t_max=t_max, draws=draws, timings=timings))
     if rows_out is not None:
         rows_out.extend((int(r['success']), r['checks'], r['g_goal'], len(r['vertices']), r['points'].shape[0], r['T']) for r in results)
     return eval_aggregate(results) + ([r['path'] for r in results],)

@@ -22,9 +22,15 @@ problems, on their order or on how a batch is cut.
 """
 import numpy as np
 
-from . import maze2d
+from .streams_batch import (AttemptBlocks, StageClock, bounds, check_stream_args, eval_chunks, maze_streams_batch, maze_class,
+                            problem_env, problem_tensors, stream_ptr)
 
 INF = float('inf')
+_maze_class = maze_class               # names the tests reach for: the shared definitions, not copies
+
+
+def _bounds(env):
+    return bounds(env.bound)
 
 # status bits of a device slot (include/gnnmp.h, gnnmp_lazysp_round)
 STATUS_PAIR_OVERFLOW, STATUS_LOOP_BOUND, STATUS_BAD_INPUT = 1, 2, 4
@@ -49,27 +55,6 @@ def rounds_pair_cap(batch, t_max, k):
         n = 2 + r * batch
         cap += min(min(k1_of(k, n), n) * n, n * (n - 1) // 2)
     return max(cap, 1)
-
-
-def _maze_class(dim):
-    if dim == 2:
-        return maze2d.Maze2D
-    if dim == 3:
-        return maze2d.Maze3D
-    raise ValueError('lazysp: maze problems have 2 (point robot) or 3 (stick robot) coordinates')
-
-
-def _problem_env(problem):
-    init = np.asarray(problem['init_state'], dtype=np.float64).reshape(-1)
-    env = _maze_class(init.shape[0])(np.asarray(problem['map'])[None], init[None],
-                                     np.asarray(problem['goal_state'], dtype=np.float64).reshape(1, -1))
-    env.init_new_problem(0)
-    return env
-
-
-def _bounds(env):
-    b = np.array(env.bound, dtype=np.float64).reshape((2, -1)).T          # lazy_sp.py:37-39
-    return b[:, 0].copy(), b[:, 1] - b[:, 0]
 
 
 def graph_edges(points, k1):
@@ -154,10 +139,10 @@ def plan_host(problem, seed, batch=50, t_max=1000, k=10, early_exit=True, attemp
     Dijkstra runs, as :func:`_dijkstra` counts them; ``draws``: the draws taken, rejected ones included.  ``attempts``: an ``[n, dim]`` array of raw doubles in [0, 1), one row
     per draw (``low + row * ranges``), instead of ``RandomState(seed).random_sample(dim)``; ``seed`` is not used then and
     running out of rows raises."""
-    env = _problem_env(problem)
+    env = problem_env(problem, 'lazysp')
     dim = env.config_dim
     rs = np.random.RandomState(int(seed) & 0xffffffff)
-    low, ranges = _bounds(env)
+    low, ranges = bounds(env.bound)                  # lazy_sp.py:37-39
     samples = [np.asarray(env.goal_state, dtype=np.float64).reshape(dim), np.asarray(env.init_state, dtype=np.float64).reshape(dim)]
     valid, invalid, invalid_order, rounds, checked = set(), set(), [], [], []
     runs, T, path = 0, 0, []
@@ -266,11 +251,6 @@ class LazySPStore:
             self.path, self.solved, self.status)))
 
 
-def _stream(dev):
-    import torch
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
 def lazysp_sample(store, attempts, att_ptr_host, maps, init64, goal64, n, active=None):
     """``gnnmp_lazysp_sample``: append ``n`` free draws to every active problem's float64 pool from its own block
     ``[att_ptr[b], att_ptr[b + 1])`` of ``attempts`` (float64 ``[M, dim]``, device).  One launch; returns device tensors
@@ -279,18 +259,13 @@ def lazysp_sample(store, attempts, att_ptr_host, maps, init64, goal64, n, active
     import torch
     from . import _lib
     dev = store.device
-    att_ptr_host = np.ascontiguousarray(att_ptr_host, dtype=np.int64)
-    att_ptr = torch.from_numpy(att_ptr_host).to(dev)
+    sb, keep = maze_streams_batch(store.B, maps.shape[1], n, store.cap, attempts, att_ptr_host, maps, init64, goal64, active)
     used = torch.zeros(store.B, dtype=torch.int32, device=dev)
     checks = torch.zeros(store.B, dtype=torch.int64, device=dev)
     status = torch.zeros(store.B, dtype=torch.int32, device=dev)
-    attempts = attempts.contiguous()
-    sb = _lib.MazeStreamsBatch(store.B, int(maps.shape[1]), int(n), store.cap, int(attempts.shape[0]), attempts.data_ptr(),
-                               att_ptr.data_ptr(), att_ptr_host.ctypes.data, maps.data_ptr(), init64.data_ptr(), goal64.data_ptr(),
-                               active.data_ptr() if active is not None else None)
     with torch.cuda.device(dev):
         _lib.check(_lib.lib().gnnmp_lazysp_sample(ctypes.byref(sb), store.dim, ctypes.byref(store.struct), used.data_ptr(),
-                                                  checks.data_ptr(), status.data_ptr(), _stream(dev)), 'gnnmp_lazysp_sample')
+                                                  checks.data_ptr(), status.data_ptr(), stream_ptr(dev)), 'gnnmp_lazysp_sample')
     return used, checks, status
 
 
@@ -308,7 +283,7 @@ def lazysp_gather(store, slot_of, k1_table, v_rows):
     with torch.cuda.device(dev):
         _lib.check(_lib.lib().gnnmp_lazysp_gather(ctypes.byref(store.struct), store.dim, A, slot_of.data_ptr(), k1_table.data_ptr(),
                                                   int(v_rows), out['v'].data_ptr(), out['node_ptr'].data_ptr(),
-                                                  out['n_free'].data_ptr(), out['k1'].data_ptr(), _stream(dev)), 'gnnmp_lazysp_gather')
+                                                  out['n_free'].data_ptr(), out['k1'].data_ptr(), stream_ptr(dev)), 'gnnmp_lazysp_gather')
     return out
 
 
@@ -329,7 +304,7 @@ def lazysp_round(store, slot_of, ei, edge_ptr, maps):
     with torch.cuda.device(dev):
         _lib.check(L.gnnmp_lazysp_round(ctypes.byref(store.struct), store.dim, A, slot_of.data_ptr() if slot_of is not None else None,
                                         ei.data_ptr(), total, edge_ptr.data_ptr(), maps.data_ptr(), int(maps.shape[1]), ws.data_ptr(),
-                                        ws.numel(), _stream(dev)), 'gnnmp_lazysp_round')
+                                        ws.numel(), stream_ptr(dev)), 'gnnmp_lazysp_round')
     return ws
 
 
@@ -353,107 +328,50 @@ def plan_maze_batch(problems, device, seeds, batch=50, t_max=1000, k=10, draws='
 
     Returns one dict per problem with :func:`plan_host`'s fields plus ``success`` and ``status`` (the slot's status bits,
     0 = fine; with ``raise_on_status`` a non-zero one raises).  ``pair_cap``: override the derived pair-list capacity."""
-    import time
     import torch
     from .graph_build import build_edges_gpu
-
-    def mark(name, t_prev):
-        if timings is None:
-            return t_prev
-        torch.cuda.current_stream().synchronize()
-        now = time.perf_counter()
-        timings[name] = timings.get(name, 0.) + now - t_prev
-        return now
+    who = 'lazysp.plan_maze_batch'
     B, n, t_max = len(problems), int(batch), int(t_max)
     if B == 0:
         return []
-    if len(seeds) != B:
-        raise ValueError('lazysp.plan_maze_batch: one seed per problem')
+    check_stream_args(B, seeds, draws, who)
     if n < 1 or t_max < 1:
         raise ValueError('lazysp.plan_maze_batch: batch >= 1 and t_max >= 1')
-    if draws not in ('host', 'device'):
-        raise ValueError("lazysp.plan_maze_batch: draws is 'host' or 'device'")
     dev = torch.device(device)
-    dims = {int(np.asarray(pr['init_state']).reshape(-1).shape[0]) for pr in problems}
-    if len(dims) != 1:
-        raise ValueError('lazysp.plan_maze_batch: point-robot and stick-robot problems in one batch')
-    dim = dims.pop()
-    limits = np.asarray(_maze_class(dim).SAMPLE_LIMITS, dtype=np.float64)
+    dim, maps, init64, goal64 = problem_tensors(problems, dev, who)
+    maze_class(dim, 'lazysp')
     R = n_rounds(n, t_max)
     cap = R * n
     store = LazySPStore(B, cap, rounds_pair_cap(n, t_max, k) if pair_cap is None else pair_cap, dim, dev)
-    f64 = lambda key: torch.from_numpy(np.ascontiguousarray(np.asarray(        # noqa: E731
-        [np.asarray(pr[key], dtype=np.float64).reshape(-1) if key != 'map' else np.asarray(pr[key], dtype=np.float64) for pr in problems]))).to(dev)
-    maps, init64, goal64 = f64('map'), f64('init_state'), f64('goal_state')
     k1_np = np.ones(cap + 3, dtype=np.int32)
     k1_np[2:] = [k1_of(k, q) for q in range(2, cap + 3)]
     k1_table = torch.from_numpy(k1_np).to(dev)
-    if draws == 'device':
-        from .rng import MTStreams
-        streams = MTStreams(seeds, dev)
-    else:
-        gens = [np.random.RandomState(int(s) & 0xffffffff) for s in seeds]
-        bufs = [np.zeros((0, dim))] * B                                  # drawn, not yet consumed
+    blocks = AttemptBlocks(seeds, dim, dev, draws, _DRAWS_PER_FREE)
+
+    def sample(att, att_ptr, mask_d):
+        used, _, status = lazysp_sample(store, att, att_ptr, maps, init64, goal64, n, active=mask_d)
+        return status, used
     act = np.arange(B)
     rounds_done = np.zeros(B, dtype=np.int64)
     snaps = []
-    tm = time.perf_counter()
+    clock = StageClock(timings)
     with torch.cuda.device(dev):
         for r in range(1, R + 1):
             # ---- sampling: a block per active problem from its own generator, longer for whoever ran out
-            pending, want = act, int(n * _DRAWS_PER_FREE[dim - 2] * 1.25) + 64
-            drawn = consumed = 0
-            while pending.size:
-                mask = np.zeros(B, dtype=np.uint8)
-                mask[pending] = 1
-                mask_d = torch.from_numpy(mask).to(dev)
-                counts = np.zeros(B, dtype=np.int64)
-                if draws == 'device':
-                    counts[pending] = want
-                else:
-                    for i in pending:
-                        short = want - bufs[i].shape[0]
-                        if short > 0:
-                            bufs[i] = np.concatenate((bufs[i], gens[i].uniform(-limits, limits, (short, dim))))
-                        counts[i] = bufs[i].shape[0]
-                att_ptr = np.zeros(B + 1, dtype=np.int64)
-                att_ptr[1:] = np.cumsum(counts)
-                if draws == 'device':
-                    att, gstat = streams.uniform(counts, -limits, limits, out_ptr=att_ptr, active=mask_d)      # not committed
-                else:
-                    att = torch.from_numpy(np.concatenate([bufs[i] for i in pending])).to(dev)
-                used, _, status = lazysp_sample(store, att, att_ptr, maps, init64, goal64, n, active=mask_d)
-                if draws == 'device':
-                    streams.advance(used, dim, active=mask_d)            # used is 0 for whoever ran out: those stay put
-                    status_h, used_h, gstat_h = torch.stack((status, used, gstat)).cpu().numpy()
-                    if gstat_h[pending].any():
-                        raise RuntimeError('gnnmp_mt19937_uniform: status for problem(s) %s' % pending[gstat_h[pending] != 0].tolist())
-                else:
-                    status_h, used_h = torch.stack((status, used)).cpu().numpy()
-                if (status_h[pending] > 1).any():
-                    raise RuntimeError('gnnmp_lazysp_sample: no room in the pool of problem(s) %s' % pending[status_h[pending] > 1].tolist())
-                fin = pending[status_h[pending] == 0]
-                if draws == 'host':
-                    for i in fin:
-                        bufs[i] = bufs[i][used_h[i]:]
-                drawn += n * int(fin.size)
-                consumed += int(used_h[fin].sum())
-                pending = pending[status_h[pending] == 1]
-                want *= 2
-            _DRAWS_PER_FREE[dim - 2] = max(1.5, 0.5 * _DRAWS_PER_FREE[dim - 2] + 0.5 * consumed / max(drawn, 1))
-            tm = mark('sampling', tm)
+            blocks.run(act, n, sample, no_room='gnnmp_lazysp_sample: no room in the pool of problem(s) %s')
+            clock.mark('sampling')
             # ---- this round's graphs
             A, N = int(act.size), 2 + r * n
             slot_of = torch.from_numpy(act.astype(np.int32)).to(dev)
             g = lazysp_gather(store, slot_of, k1_table, A * N)
-            tm = mark('gather', tm)
+            clock.mark('gather')
             ei, edge_ptr = build_edges_gpu(g['v'], g['node_ptr'], g['n_free'], g['k1'])
-            tm = mark('graph_build', tm)
+            clock.mark('graph_build')
             ws = lazysp_round(store, slot_of, ei, edge_ptr, maps)
             snaps.append(torch.stack((store.n_nodes.to(torch.int64), store.checks, store.n_pairs.to(torch.int64))))
             solved_h, status_h = torch.stack((store.solved, store.status)).cpu().numpy()      # the read that decides who continues
             del ws
-            tm = mark('lazy_round', tm)
+            clock.mark('lazy_round')
             rounds_done[act] = r
             if raise_on_status and status_h[act].any():
                 bad = act[status_h[act] != 0]
@@ -485,7 +403,7 @@ def plan_maze_batch(problems, device, seeds, batch=50, t_max=1000, k=10, draws='
                     'valid_edges': _unordered(pr_[st_ == 1]), 'invalid_edges': _unordered(pr_[st_ == 2]),
                     'dijkstra_runs': int(runs[b]), 'invalid_order': pr_[st_ == 2].astype(np.int64).reshape(-1, 2),
                     'rounds': np.array(rows, dtype=np.int64).reshape(-1, 4), 'success': bool(solved[b]), 'status': int(status[b])})
-    mark('results', tm)
+    clock.mark('results')
     return out
 
 
@@ -495,17 +413,13 @@ def eval_lazysp_device(env, indexes, seed=1234, seeds=None, batch=50, t_max=1000
     problems per batch: ``n_success``, ``collision`` (mean collision checks, sampling included), ``solution_cost`` (mean
     :func:`gnnmp.planner.path_cost` of the solved problems' float64 paths), ``paths`` and per-problem ``rows`` (success, checks,
     path cost, path nodes, N, dijkstra runs, T).  Problem ``indexes[i]`` draws from ``np.random.RandomState(seeds[i])``; default
-    :func:`gnnmp.planner.stream_seeds`.  The numbers DIFFER from ``eval_lazysp``'s, which walks ONE global stream problem after
+    :func:`gnnmp.streams_batch.stream_seeds`.  The numbers DIFFER from ``eval_lazysp``'s, which walks ONE global stream problem after
     problem -- other samples of the same distribution -- and in exchange they do not depend on the order of ``indexes`` or on
     ``chunk``.  The global numpy generator is left alone."""
-    from .planner import path_cost, stream_seeds
-    indexes = list(indexes)
-    seeds = stream_seeds(seed, indexes) if seeds is None else list(seeds)
+    from .planner import path_cost
     rows, paths = [], []
-    for c0 in range(0, len(indexes), max(int(chunk), 1)):
-        part = indexes[c0:c0 + max(int(chunk), 1)]
-        pr = [dict(map=env.maps[i], init_state=env.init_states[i], goal_state=env.goal_states[i]) for i in part]
-        for res in plan_maze_batch(pr, device, seeds[c0:c0 + len(part)], batch=batch, t_max=t_max, k=k, draws=draws, timings=timings):
+    for pr, chunk_seeds in eval_chunks(env, indexes, seed, seeds, chunk):
+        for res in plan_maze_batch(pr, device, chunk_seeds, batch=batch, t_max=t_max, k=k, draws=draws, timings=timings):
             paths.append(res['path'])
             rows.append((int(res['success']), res['checks'], path_cost(res['path']) if res['success'] else 0.0, len(res['path_ids']),
                          res['samples'].shape[0], res['dijkstra_runs'], res['T']))

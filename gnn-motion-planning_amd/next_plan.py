@@ -28,8 +28,9 @@ of standard normal draws ``eps`` that replaces the global torch generator (:clas
 import numpy as np
 
 from . import maze2d
-from .rrtstar import (MODEL_EPS, RRT_EPS, _problem_env, distances, draws_per_problem, nearest_index, new_stats, next_sample,
-                      rewire_last, sample_bounds, tied_minimum)
+from .rrtstar import (MODEL_EPS, RRT_EPS, TREE_TENSORS, distances, draws_per_problem, eval_aggregate, nearest_index, new_stats,
+                      next_sample, rewire_last, sample_bounds, tied_minimum, tree_results)
+from .streams_batch import RawDoubles, StageClock, check_stream_args, eval_chunks, problem_env, problem_tensors
 
 G_EXPLORE_EPS = 0.1                    # eval_next.py:62 explore_eps
 POLICY_STD = RRT_EPS * 0.3             # next_model/model2D.py: Model2D's std
@@ -130,7 +131,7 @@ def plan_host(problem, seed, model, t_max=1000, g_explore_eps=G_EXPLORE_EPS, mod
     how far the run came to a tie that a last-bit difference in ``w`` could flip; inf when no arg-max had two entries).
     ``raw``: the problem's block of raw doubles instead of ``RandomState(seed).random_sample(...)``, as
     :func:`gnnmp.rrtstar.plan_host` takes it; the RRT branch counts the same exact ties."""
-    env = _problem_env(problem)
+    env = problem_env(problem, 'rrtstar')
     dim = env.config_dim
     low, ranges = sample_bounds(dim)
     if raw is None:
@@ -289,9 +290,7 @@ def next_plan_device(maps, init64, goal64, draws, pb_rep, weights, eps, t_max, s
     batch = _lib.NextPlanBatch(B, dim, int(maps.shape[1]), int(t_max), 1 if stop_when_success else 0, int(draws.shape[1]),
                                maps.data_ptr(), init64.data_ptr(), goal64.data_ptr(), draws.data_ptr(), float(g_explore_eps), float(c), k,
                                int(eps.shape[1]), float(scale), pb_rep.data_ptr(), weights.data_ptr(), eps.data_ptr() or None)
-    tree = _lib.NextPlanTree(*(out[key].data_ptr() for key in ('states', 'parents', 'rewired_parents', 'flags', 'costs', 'path_lengths',
-                                                               'cumulated_checks', 'path')),
-                             *(out['small'][r].data_ptr() for r in range(6)),
+    tree = _lib.NextPlanTree(*(out[key].data_ptr() for key in TREE_TENSORS), *(out['small'][r].data_ptr() for r in range(6)),
                              *(out[key].data_ptr() for key in ('expanded_by_rrt', 'state_values', 'w', 'visits', 'w_sum')),
                              out['small'][6].data_ptr())
     with torch.cuda.device(dev):
@@ -326,91 +325,53 @@ def plan_maze_batch(problems, device, seeds, net, t_max=1000, stop_when_success=
 
     Returns one dict per problem with :func:`plan_host`'s fields (``guided`` at the top level instead of ``stats``) plus
     ``status``.  ``net.check_status()`` and, with ``check``, a non-zero status word raise."""
-    import time
     import torch
     from .next_model import NextNet
-
-    def mark(name, t_prev):
-        if timings is None:
-            return t_prev
-        torch.cuda.current_stream().synchronize()
-        now = time.perf_counter()
-        timings[name] = timings.get(name, 0.) + now - t_prev
-        return now
+    who = 'next_plan.plan_maze_batch'
     B, t_max = len(problems), int(t_max)
     if B == 0:
         return []
-    if len(seeds) != B:
-        raise ValueError('next_plan.plan_maze_batch: one seed per problem')
+    check_stream_args(B, seeds, draws, who)
     if t_max < 1 or t_max + 1 > max_nodes():
         raise ValueError('next_plan.plan_maze_batch: t_max is 1 .. %d (the device loop keeps the tree in LDS)' % (max_nodes() - 1))
-    if draws not in ('host', 'device'):
-        raise ValueError("next_plan.plan_maze_batch: draws is 'host' or 'device'")
     if not isinstance(net, NextNet):
         raise TypeError('next_plan.plan_maze_batch: net is a loaded gnnmp.next_model.NextNet')
     dev = torch.device(device)
-    dims = {int(np.asarray(pr['init_state']).reshape(-1).shape[0]) for pr in problems}
-    if len(dims) != 1:
-        raise ValueError('next_plan.plan_maze_batch: point-robot and stick-robot problems in one batch')
-    dim = dims.pop()
+    with torch.cuda.device(dev):
+        dim, maps, init64, goal64 = problem_tensors(problems, dev, who)
     if dim != net.dim:
         raise ValueError('next_plan.plan_maze_batch: dim %d problems, a dim %d network' % (dim, net.dim))
-    n_draws = draws_per_problem(t_max, dim)
-    f64 = lambda key: torch.from_numpy(np.ascontiguousarray(np.asarray(        # noqa: E731
-        [np.asarray(pr[key], dtype=np.float64).reshape(-1) if key != 'map' else np.asarray(pr[key], dtype=np.float64) for pr in problems]))).to(dev)
     if eps is None:
         eps = default_eps(seeds, t_max, k, dim)
     eps = torch.as_tensor(eps, dtype=torch.float32)
     if eps.dim() != 4 or int(eps.shape[0]) != B or int(eps.shape[2]) != int(k) or int(eps.shape[3]) != dim:
         raise ValueError('next_plan.plan_maze_batch: eps is [B, rows, k, dim]')
-    tm = time.perf_counter()
+    clock = StageClock(timings)
     with torch.cuda.device(dev):
-        maps, init64, goal64 = f64('map'), f64('init_state'), f64('goal_state')
         eps_dev = eps.to(dev).contiguous()
         pb_rep = net.pb_forward(maps.to(torch.float32), goal64.to(torch.float32))
-        tm = mark('pb_forward', tm)
-        if draws == 'device':
-            from .rng import MTStreams
-            streams = MTStreams(seeds, dev)
-            rows, gstat = streams.uniform([n_draws] * B, 0.0, 1.0)       # low 0, range 1: the raw doubles; not committed
-            raw = rows.reshape(B, n_draws)
-        else:
-            raw = torch.from_numpy(np.stack([np.random.RandomState(int(s) & 0xffffffff).random_sample(n_draws) for s in seeds])).to(dev)
-        tm = mark('draws', tm)
-        out = next_plan_device(maps, init64, goal64, raw, pb_rep, net._weights(dev), eps_dev, t_max, stop_when_success, g_explore_eps,
-                               c, int(k), policy_scale(std, dim))
-        if draws == 'device':
-            streams.advance(out['small'][3], 1)                          # by the doubles each problem consumed
-            if gstat.cpu().numpy().any():
-                raise RuntimeError('gnnmp_mt19937_uniform: a stream reported a status')
-            if streams_out is not None:
-                streams_out.append(streams)
-        tm = mark('plan', tm)
-        n_nodes, success, last_i, used, plen, status, guided = out['small'].cpu().numpy()
+        clock.mark('pb_forward')
+        block = RawDoubles(seeds, draws_per_problem(t_max, dim), dev, draws)
+        clock.mark('draws')
+        out = next_plan_device(maps, init64, goal64, block.raw, pb_rep, net._weights(dev), eps_dev, t_max, stop_when_success,
+                               g_explore_eps, c, int(k), policy_scale(std, dim))
+        block.finish(out['small'][3], streams_out)                       # by the doubles each problem consumed
+        clock.mark('plan')
+        small = out['small'].cpu().numpy()
+        status, guided = small[5], small[6]
         net.check_status()
         if check and status.any():
             bad = np.flatnonzero(status)
             raise RuntimeError('gnnmp_next_plan: status %s for problem(s) %s (1 = draw block too short, 2 = cycle in rewired_parents, '
                                '4 = eps block too short, 8 = a score was not finite)' % (status[bad].tolist(), bad.tolist()))
-        host = {key: out[key].cpu().numpy() for key in ('states', 'parents', 'rewired_parents', 'flags', 'costs', 'path_lengths',
-                                                       'cumulated_checks', 'path', 'expanded_by_rrt', 'state_values', 'w', 'visits',
-                                                       'w_sum')}
-    res = []
-    for b in range(B):
-        n = int(n_nodes[b])
-        pts = host['states'][b, :n].copy()
-        ids = host['path'][b, :plen[b]].astype(np.int64)
-        flags = host['flags'][b, :n]
-        res.append({'states': pts, 'parents': host['parents'][b, :n].astype(np.int64),
-                    'rewired_parents': host['rewired_parents'][b, :n].astype(np.int64), 'freesp': (flags & 1).astype(bool),
-                    'in_goal_region': (flags & 2).astype(bool), 'costs': host['costs'][b, :n].copy(),
-                    'path_lengths': host['path_lengths'][b, :n].copy(),
-                    'cumulated_collision_checks': host['cumulated_checks'][b, :n].copy(), 'success': bool(success[b]),
-                    'i': int(last_i[b]), 'path_ids': ids, 'path': pts[ids], 'draws': int(used[b]),
-                    'expanded_by_rrt': host['expanded_by_rrt'][b, :n].copy(), 'state_values': host['state_values'][b, :n].copy(),
-                    'w': host['w'][b, :n].copy(), 'w_sum': float(host['w_sum'][b]), 'visits': host['visits'][b, :n].astype(np.int64),
-                    'guided': int(guided[b]), 'status': int(status[b])})
-    mark('results', tm)
+        host = {key: out[key].cpu().numpy() for key in TREE_TENSORS + ('expanded_by_rrt', 'state_values', 'w', 'visits', 'w_sum')}
+    res = tree_results(host, small)
+    for b, r in enumerate(res):
+        n = r['states'].shape[0]
+        r.update(expanded_by_rrt=host['expanded_by_rrt'][b, :n].copy(), state_values=host['state_values'][b, :n].copy(),
+                 w=host['w'][b, :n].copy(), w_sum=float(host['w_sum'][b]), visits=host['visits'][b, :n].astype(np.int64),
+                 guided=int(guided[b]))
+    clock.mark('results')
     return res
 
 
@@ -420,20 +381,13 @@ def eval_next_device(env, indexes, net, seed=1234, seeds=None, t_max=1000, devic
     :func:`plan_maze_batch` with ``stop_when_success=True``, ``chunk`` problems per launch: ``(n_success, collision,
     solution_cost, paths)`` through :func:`gnnmp.rrtstar.eval_aggregate`, with the same first-iteration quirk of ``collision``;
     ``paths`` are the float64 states of ``search_tree.path()``.  Problem ``indexes[i]`` draws from ``RandomState(seeds[i])`` and
-    from :func:`default_eps` of ``seeds[i]``; default :func:`gnnmp.planner.stream_seeds`.  The numbers DIFFER from
+    from :func:`default_eps` of ``seeds[i]``; default :func:`gnnmp.streams_batch.stream_seeds`.  The numbers DIFFER from
     ``eval_next``'s, which walks ONE global numpy stream and ONE global torch stream problem after problem -- other samples of
     the same distributions -- and in exchange they do not depend on the order of ``indexes`` or on ``chunk``.  ``rows_out``: a
     list that receives per problem (success, checks with the quirk, path_lengths[-1], nodes, last iteration, guided)."""
-    from .planner import stream_seeds
-    from .rrtstar import eval_aggregate
-    indexes = list(indexes)
-    seeds = stream_seeds(seed, indexes) if seeds is None else list(seeds)
     results = []
-    for c0 in range(0, len(indexes), max(int(chunk), 1)):
-        part = indexes[c0:c0 + max(int(chunk), 1)]
-        pr = [dict(map=env.maps[i], init_state=env.init_states[i], goal_state=env.goal_states[i]) for i in part]
-        results.extend(plan_maze_batch(pr, device, seeds[c0:c0 + len(part)], net, t_max=t_max, stop_when_success=True, draws=draws,
-                                       timings=timings))
+    for pr, chunk_seeds in eval_chunks(env, indexes, seed, seeds, chunk):
+        results.extend(plan_maze_batch(pr, device, chunk_seeds, net, t_max=t_max, stop_when_success=True, draws=draws, timings=timings))
     if rows_out is not None:
         rows_out.extend((int(r['success']), int(r['cumulated_collision_checks'][-1]) - int(r['cumulated_collision_checks'][1]),
                          float(r['path_lengths'][-1]), r['states'].shape[0], r['i'], r['guided']) for r in results)

@@ -18,6 +18,8 @@ import numpy as np
 import torch
 
 from .graph_build import create_data, create_data_gpu
+from .streams_batch import (AttemptBlocks, StageClock, check_stream_args, eval_chunks, maze_class, maze_streams_batch,  # noqa: F401
+                            problem_tensors, stream_seeds)
 
 
 def path_cost(path):
@@ -448,14 +450,6 @@ def _collect(res, wall, t_explore, sol, paths, smooth_paths, rows_out):
             rows_out.append(sol[-1][:5] + (len(paths[-1]), len(r['explored'])))
 
 
-def _maze_class(dim):
-    """Host environment of a maze problem by the width of its configurations: 2 = point robot, 3 = stick robot."""
-    from .maze2d import Maze2D, Maze3D
-    if int(dim) not in (2, 3):
-        raise ValueError('maze problems have configurations of width 2 or 3, got %d' % dim)
-    return Maze3D if int(dim) == 3 else Maze2D
-
-
 def _problems_dim(problems):
     return int(np.asarray(problems[0]['init_state']).size)
 
@@ -466,7 +460,7 @@ def skip_maze_sampling(env, indexes, batch=500):
     block at the stream position the sequential reference loop would have reached (0.07 ms per skipped problem of the point
     robot; the stick robot's vectorised classification, ``Maze3D.sample_n_points_stream``, costs more)."""
     from .maze2d import AttemptStream
-    cls = _maze_class(env.config_dim)
+    cls = maze_class(env.config_dim)
     stream = AttemptStream(limits=cls.SAMPLE_LIMITS)
     for i in indexes:
         e = cls(np.asarray(env.maps[i])[None], np.asarray(env.init_states[i])[None], np.asarray(env.goal_states[i])[None])
@@ -649,7 +643,7 @@ def sample_maze_problems(problems, batch, k):
     from .maze2d import AttemptStream
     envs, vs, n_free, k1s = [], [], [], []
     dim = _problems_dim(problems) if problems else 2
-    cls = _maze_class(dim)
+    cls = maze_class(dim)
     stream = AttemptStream(limits=cls.SAMPLE_LIMITS)
     for pr in problems:
         env = cls(np.asarray(pr['map'])[None], np.asarray(pr['init_state'])[None], np.asarray(pr['goal_state'])[None])
@@ -690,7 +684,7 @@ def sample_maze_problems_device(problems, batch, k, device):
     B = len(problems)
     dev = torch.device(device)
     dim = _problems_dim(problems)
-    cls = _maze_class(dim)
+    cls = maze_class(dim)
     envs = []
     for pr in problems:
         env = cls(np.asarray(pr['map'])[None], np.asarray(pr['init_state'])[None], np.asarray(pr['goal_state'])[None])
@@ -811,14 +805,7 @@ def explore_maze_batch(problems, model, device, batch=500, k=30, loop=5, model_s
     ``timings``: optional dict that receives wall-clock seconds per stage (adds device syncs).
     ``presampled``: the result of :func:`sample_maze_problems` for these problems (lets a caller sample the next
     chunk on the host while the device works on this one)."""
-    def mark(name, t_prev):
-        if timings is None:
-            return t_prev
-        torch.cuda.current_stream().synchronize()      # (this pass's stream only: other passes may be in flight)
-        now = time.perf_counter()
-        timings[name] = timings.get(name, 0.) + now - t_prev
-        return now
-    tm = time.perf_counter()
+    clock = StageClock(timings)
     from .batch import GraphBatch
     from .graph_build import build_edges_gpu
     B = len(problems)
@@ -828,16 +815,16 @@ def explore_maze_batch(problems, model, device, batch=500, k=30, loop=5, model_s
         v, node_ptr = dsamp['v'], dsamp['node_ptr']
         ptr = torch.from_numpy(np.asarray(dsamp['node_ptr_host'], dtype=np.int64))
         vs = None
-        tm = mark('host_sampling', tm)
+        clock.mark('host_sampling')
     else:
         envs, vs, n_free, k1s = presampled if presampled is not None else sample_maze_problems(problems, batch, k)
-        tm = mark('host_sampling', tm)
+        clock.mark('host_sampling')
         ptr = torch.zeros(B + 1, dtype=torch.int64)
         ptr[1:] = torch.tensor([x.shape[0] for x in vs]).cumsum(0)
         node_ptr = ptr.to(torch.int32).to(device)
         v = torch.cat(vs).to(device)
     ei, edge_ptr = build_edges_gpu(v, node_ptr, n_free, k1s)
-    tm = mark('graph_build', tm)
+    clock.mark('graph_build')
     obs = [np.asarray(e.obstacles).reshape(-1, 2) for e in envs]
     ocount = np.array([o.shape[0] for o in obs], dtype=np.int64)
     optr = np.zeros(B + 1, dtype=np.int32)
@@ -848,7 +835,7 @@ def explore_maze_batch(problems, model, device, batch=500, k=30, loop=5, model_s
     gb = GraphBatch(v, goals, torch.from_numpy(obs_all).to(device), ei, node_ptr, edge_ptr,
                     torch.from_numpy(optr).to(device), int(ocount.max()))
     scores = model.forward_batch(gb, loop)
-    tm = mark('explorer_forward', tm)
+    clock.mark('explorer_forward')
     if dsamp is not None:
         maps, goal64 = dsamp['maps'], dsamp['goal64']
     else:
@@ -857,12 +844,12 @@ def explore_maze_batch(problems, model, device, batch=500, k=30, loop=5, model_s
     success, n_expl, n_pairs, plen, checks, expl, ee, ee_off, path = maze_explore_device(
         v, node_ptr, edge_ptr, n_free, ei, scores, maps, goal64)
     nptr = ptr.tolist()
-    tm = mark('greedy_explore', tm)
+    clock.mark('greedy_explore')
     smoothed = {}
     if model_s is not None and any(success):
         smoothed = _smooth_maze_batch(model_s, [b for b in range(B) if success[b]], v, nptr, n_free, path, plen, maps,
                                       smooth_iters, device)
-        tm = mark('smoothing', tm)
+        clock.mark('smoothing')
     out = []
     if vs is None:                                                       # device sampling: one copy of the node rows for the results
         v_host = v.cpu().numpy()
@@ -881,7 +868,7 @@ def explore_maze_batch(problems, model, device, batch=500, k=30, loop=5, model_s
         if model_s is not None:
             sp, cs = smoothed.get(b, (np.zeros((0, int(v.shape[1])), dtype=np.float32), 0))
             out[-1].update(smooth_path=sp, c_smooth=cs)
-    mark('results', tm)
+    clock.mark('results')
     return out
 
 
@@ -1161,15 +1148,10 @@ def maze_sample_streams(store, attempts, att_ptr_host, maps, init64, goal64, n, 
     import ctypes
     from . import _lib
     dev = store.device
-    att_ptr_host = np.ascontiguousarray(att_ptr_host, dtype=np.int64)
-    att_ptr = torch.from_numpy(att_ptr_host).to(dev)
+    sb, keep = maze_streams_batch(store.B, maps.shape[1], n, store.cap, attempts, att_ptr_host, maps, init64, goal64, active)
     used = torch.zeros(store.B, dtype=torch.int32, device=dev)
     checks = torch.zeros(store.B, dtype=torch.int64, device=dev)
     status = torch.zeros(store.B, dtype=torch.int32, device=dev)
-    attempts = attempts.contiguous()
-    sb = _lib.MazeStreamsBatch(store.B, int(maps.shape[1]), int(n), store.cap, int(attempts.shape[0]), attempts.data_ptr(),
-                               att_ptr.data_ptr(), att_ptr_host.ctypes.data, maps.data_ptr(), init64.data_ptr(), goal64.data_ptr(),
-                               active.data_ptr() if active is not None else None)
     with torch.cuda.device(dev):
         st = torch.cuda.current_stream().cuda_stream
         _lib.check(_lib.lib().gnnmp_maze_sample_streams(ctypes.byref(sb), store.dim, store.free_pool.data_ptr(), store.n_free.data_ptr(),
@@ -1271,27 +1253,17 @@ def plan_maze_rounds_batch(problems, model, device, seeds, batch=500, t_max=500,
     from .batch import GraphBatch
     from .graph_build import build_edges_gpu, k1_of
 
-    def mark(name, t_prev):
-        if timings is None:
-            return t_prev
-        torch.cuda.current_stream().synchronize()
-        now = time.perf_counter()
-        timings[name] = timings.get(name, 0.) + now - t_prev
-        return now
+    who = 'plan_maze_rounds_batch'
     B, n, t_max = len(problems), int(batch), int(t_max)
     if B == 0:
         return []
-    if len(seeds) != B:
-        raise ValueError('plan_maze_rounds_batch: one seed per problem')
+    check_stream_args(B, seeds, draws, who)
     if n < 1 or n > t_max:
         raise ValueError('plan_maze_rounds_batch: 1 <= batch <= t_max')
-    if draws not in ('host', 'device'):
-        raise ValueError("plan_maze_rounds_batch: draws is 'host' or 'device'")
-    tm = time.perf_counter()
+    clock = StageClock(timings)
     dev = torch.device(device)
-    dim = _problems_dim(problems)
-    cls = _maze_class(dim)
-    limits = np.asarray(cls.SAMPLE_LIMITS, dtype=np.float64)
+    dim, maps, init64, goal64 = problem_tensors(problems, dev, who)
+    cls = maze_class(dim)
     envs = []
     for pr in problems:
         env = cls(np.asarray(pr['map'])[None], np.asarray(pr['init_state'])[None], np.asarray(pr['goal_state'])[None])
@@ -1299,88 +1271,31 @@ def plan_maze_rounds_batch(problems, model, device, seeds, batch=500, t_max=500,
         envs.append(env)
     cap = -(-t_max // n) * n
     store = MazeRoundsStore(B, cap, rounds_pair_cap(n, t_max, k), dim, dev)
-    maps = torch.from_numpy(np.ascontiguousarray(np.asarray([np.asarray(pr['map'], dtype=np.float64) for pr in problems]))).to(dev)
-    init64 = torch.from_numpy(np.ascontiguousarray(np.asarray([np.asarray(e.init_state, dtype=np.float64).reshape(dim) for e in envs]))).to(dev)
-    goal64 = torch.from_numpy(np.ascontiguousarray(np.asarray([np.asarray(e.goal_state, dtype=np.float64).reshape(dim) for e in envs]))).to(dev)
     goals32 = goal64.to(torch.float32)
     obs = [np.asarray(e.obstacles).reshape(-1, 2) for e in envs]
     ocount = np.array([o.shape[0] for o in obs], dtype=np.int64)
     optr_all = np.zeros(B + 1, dtype=np.int64)
     optr_all[1:] = np.cumsum(ocount)
     obs_all = torch.from_numpy(np.ascontiguousarray(np.concatenate(obs), dtype=np.float32)).to(dev)
-    if draws == 'device':
-        from .rng import MTStreams
-        streams = MTStreams(seeds, dev)
-    else:
-        gens = [np.random.RandomState(int(s) & 0xffffffff) for s in seeds]
-        bufs = [np.zeros((0, dim))] * B                                  # drawn, not yet consumed
+    blocks = AttemptBlocks(seeds, dim, dev, draws, _DRAWS_PER_FREE, gstat_values=True)
     samp_checks = torch.zeros(B, dtype=torch.int64, device=dev)
     n_coll_h = np.zeros(B, dtype=np.int64)
     rounds = np.zeros(B, dtype=np.int64)
     act = np.arange(B)
     done_rounds = 0
+
+    def sample(att, att_ptr, mask_d):
+        used, checks, status = maze_sample_streams(store, att, att_ptr, maps, init64, goal64, n, active=mask_d)
+        samp_checks.add_(checks * mask_d)                                # (a problem that ran out reports 0)
+        return status, used, store.n_coll
     with torch.cuda.device(dev):
         while True:
             # ---- sampling: a block per active problem from its own generator, longer for whoever ran out
-            pending, want = act, int(n * _DRAWS_PER_FREE[dim - 2] * 1.25) + 64
             act_mask = np.zeros(B, dtype=np.uint8)
             act_mask[act] = 1
             act_mask_d = torch.from_numpy(act_mask).to(dev)
-            drawn = consumed = 0
-            while pending.size and draws == 'device':
-                counts = np.zeros(B, dtype=np.int64)
-                counts[pending] = want
-                att_ptr = np.zeros(B + 1, dtype=np.int64)
-                att_ptr[1:] = np.cumsum(counts)
-                mask = np.zeros(B, dtype=np.uint8)
-                mask[pending] = 1
-                mask_d = torch.from_numpy(mask).to(dev)
-                att, gstat = streams.uniform(counts, -limits, limits, out_ptr=att_ptr, active=mask_d)      # not committed
-                used, checks, status = maze_sample_streams(store, att, att_ptr, maps, init64, goal64, n, active=mask_d)
-                samp_checks += checks * mask_d
-                streams.advance(used, dim, active=mask_d)                # used is 0 for whoever ran out: those stay put
-                status_h, used_h, ncoll, gstat_h = torch.stack((status, used, store.n_coll, gstat)).cpu().numpy()
-                if gstat_h[pending].any():
-                    raise RuntimeError('gnnmp_mt19937_uniform: status %s for problem(s) %s'
-                                       % (gstat_h[pending][gstat_h[pending] != 0].tolist(), pending[gstat_h[pending] != 0].tolist()))
-                if (status_h[pending] > 1).any():
-                    raise RuntimeError('gnnmp_maze_sample_streams: no room in the pools of problem(s) %s'
-                                       % pending[status_h[pending] > 1].tolist())
-                fin = pending[status_h[pending] == 0]
-                n_coll_h[fin] = ncoll[fin]
-                drawn += n * int(fin.size)
-                consumed += int(used_h[fin].sum())
-                pending = pending[status_h[pending] == 1]
-                want *= 2
-            while pending.size:
-                counts = np.zeros(B, dtype=np.int64)
-                for i in pending:
-                    short = want - bufs[i].shape[0]
-                    if short > 0:
-                        bufs[i] = np.concatenate((bufs[i], gens[i].uniform(-limits, limits, (short, dim))))
-                    counts[i] = bufs[i].shape[0]
-                att_ptr = np.zeros(B + 1, dtype=np.int64)
-                att_ptr[1:] = np.cumsum(counts)
-                att = torch.from_numpy(np.concatenate([bufs[i] for i in pending])).to(dev)
-                mask = np.zeros(B, dtype=np.uint8)
-                mask[pending] = 1
-                mask_d = torch.from_numpy(mask).to(dev)
-                used, checks, status = maze_sample_streams(store, att, att_ptr, maps, init64, goal64, n, active=mask_d)
-                samp_checks += checks * mask_d                           # (a problem that ran out reports 0)
-                status_h, used_h, ncoll = torch.stack((status, used, store.n_coll)).cpu().numpy()
-                if (status_h[pending] > 1).any():
-                    raise RuntimeError('gnnmp_maze_sample_streams: no room in the pools of problem(s) %s'
-                                       % pending[status_h[pending] > 1].tolist())
-                for i in pending:
-                    if status_h[i] == 0:
-                        bufs[i] = bufs[i][used_h[i]:]
-                        n_coll_h[i] = ncoll[i]
-                        drawn += n
-                        consumed += int(used_h[i])
-                pending = pending[status_h[pending] == 1]
-                want *= 2
-            _DRAWS_PER_FREE[dim - 2] = max(1.5, 0.5 * _DRAWS_PER_FREE[dim - 2] + 0.5 * consumed / max(drawn, 1))
-            tm = mark('sampling', tm)
+            n_coll_h[act] = blocks.run(act, n, sample, no_room='gnnmp_maze_sample_streams: no room in the pools of problem(s) %s')[2][act]
+            clock.mark('sampling')
             # ---- this round's graphs
             A, nf = int(act.size), 2 + (done_rounds + 1) * n
             everyone = A == B
@@ -1388,7 +1303,7 @@ def plan_maze_rounds_batch(problems, model, device, seeds, batch=500, t_max=500,
             g = maze_rounds_gather(store, A, A * nf + int(n_coll_h[act].sum()), active=None if everyone else act_mask_d)
             k1 = torch.full((A,), k1_of(k, nf), dtype=torch.int32, device=dev)
             ei, edge_ptr = build_edges_gpu(g['v'], g['node_ptr'], g['n_free'], k1)
-            tm = mark('graph_build', tm)
+            clock.mark('graph_build')
             if everyone:
                 obs_r, optr = obs_all, optr_all
             else:
@@ -1400,11 +1315,11 @@ def plan_maze_rounds_batch(problems, model, device, seeds, batch=500, t_max=500,
             gb = GraphBatch(g['v'], goals32 if everyone else goals32[act_d], obs_r, ei, g['node_ptr'], edge_ptr,
                             torch.from_numpy(optr.astype(np.int32)).to(dev), int(ocount[act].max()))
             scores = model.forward_batch(gb, loop)
-            tm = mark('explorer_forward', tm)
+            clock.mark('explorer_forward')
             cstat = maze_rounds_explore(store, g, ei, edge_ptr, scores, maps if everyone else maps[act_d].contiguous(),
                                         goal64 if everyone else goal64[act_d].contiguous())
             flags = torch.cat((store.tree_success, cstat)).cpu().numpy()     # the one read that decides who continues
-            tm = mark('greedy_explore', tm)
+            clock.mark('greedy_explore')
             if flags[B:].any():
                 raise RuntimeError('gnnmp_maze_rounds_carry: pair list or tree beyond its slot for problem(s) %s'
                                    % act[flags[B:] != 0].tolist())
@@ -1433,7 +1348,7 @@ def plan_maze_rounds_batch(problems, model, device, seeds, batch=500, t_max=500,
                 path_all[nptr[b]:nptr[b] + plen[b]] = paths[b, :plen[b]]
             smoothed = _smooth_maze_batch(model_s, [b for b in range(B) if success[b]], g['v'], nptr, n_free_h, path_all, plen,
                                           maps, smooth_iters, dev)
-            tm = mark('smoothing', tm)
+            clock.mark('smoothing')
     out, po = [], 0
     for b in range(B):
         ok = bool(success[b])
@@ -1446,13 +1361,8 @@ def plan_maze_rounds_batch(problems, model, device, seeds, batch=500, t_max=500,
         if model_s is not None:
             sp, cs = smoothed.get(b, (np.zeros((0, dim), dtype=np.float32), 0))
             out[-1].update(smooth_path=sp, c_smooth=cs)
-    mark('results', tm)
+    clock.mark('results')
     return out
-
-
-def stream_seeds(seed, indexes):
-    """Default per-problem seeds of :func:`eval_gnn_device_streams`: ``(seed + 0x9E3779B1 * (index + 1)) mod 2**32``."""
-    return [(int(seed) + 0x9E3779B1 * (int(i) + 1)) % (1 << 32) for i in indexes]
 
 
 def eval_gnn_device_streams(env, indexes, model, model_s=None, seed=1234, seeds=None, batch=500, t_max=500, k=30, device='cuda',
@@ -1470,14 +1380,10 @@ def eval_gnn_device_streams(env, indexes, model, model_s=None, seed=1234, seeds=
     model.eval()                       # eval_gnn.py:109-110
     if model_s is not None:
         model_s.eval()
-    indexes = list(indexes)
-    seeds = stream_seeds(seed, indexes) if seeds is None else list(seeds)
     dim = env.config_dim
     sol = []
-    for c0 in range(0, len(indexes), max(int(chunk), 1)):
-        part = indexes[c0:c0 + max(int(chunk), 1)]
-        pr = [dict(map=env.maps[i], init_state=env.init_states[i], goal_state=env.goal_states[i]) for i in part]
-        res = plan_maze_rounds_batch(pr, model, device, seeds[c0:c0 + len(part)], batch=batch, t_max=t_max, k=k, loop=loop,
+    for pr, chunk_seeds in eval_chunks(env, indexes, seed, seeds, chunk):
+        res = plan_maze_rounds_batch(pr, model, device, chunk_seeds, batch=batch, t_max=t_max, k=k, loop=loop,
                                      model_s=model_s, timings=timings, draws=draws)
         for r in res:
             p = r['path'] if r['success'] else np.zeros((0, dim), dtype=np.float32)

@@ -24,6 +24,7 @@ their order or on how a batch is cut.
 import numpy as np
 
 from . import maze2d
+from .streams_batch import RawDoubles, StageClock, check_stream_args, eval_chunks, maze_class, problem_env, problem_tensors, sample_limits
 
 MODEL_EPS = 0.05                       # tsa.py:13 model_eps: the goal bias
 RRT_EPS = maze2d.RRT_EPS               # steering step and goal radius
@@ -35,22 +36,8 @@ STATUS_DRAWS_SHORT, STATUS_PATH_BOUND = 1, 2
 
 TREE_FIELDS = ('states', 'parents', 'rewired_parents', 'freesp', 'in_goal_region', 'costs', 'path_lengths',
                'cumulated_collision_checks', 'success', 'i', 'path_ids', 'draws')
-
-
-def _maze_class(dim):
-    if dim == 2:
-        return maze2d.Maze2D
-    if dim == 3:
-        return maze2d.Maze3D
-    raise ValueError('rrtstar: maze problems have 2 (point robot) or 3 (stick robot) coordinates')
-
-
-def _problem_env(problem):
-    init = np.asarray(problem['init_state'], dtype=np.float64).reshape(-1)
-    env = _maze_class(init.shape[0])(np.asarray(problem['map'])[None], init[None],
-                                     np.asarray(problem['goal_state'], dtype=np.float64).reshape(1, -1))
-    env.init_new_problem(0)
-    return env
+# the per-node arrays of a device tree (include/gnnmp.h, gnnmp_rrtstar_tree), in the struct's order
+TREE_TENSORS = ('states', 'parents', 'rewired_parents', 'flags', 'costs', 'path_lengths', 'cumulated_checks', 'path')
 
 
 def draws_per_problem(t_max, dim):
@@ -60,7 +47,7 @@ def draws_per_problem(t_max, dim):
 
 def sample_bounds(dim):
     """(low, high - low) of ``uniform_sample`` (maze_env.py:131)."""
-    limits = np.asarray(_maze_class(dim).SAMPLE_LIMITS, dtype=np.float64)
+    limits = sample_limits(dim, 'rrtstar')
     return -limits, limits - (-limits)
 
 
@@ -186,7 +173,7 @@ def plan_host(problem, seed, t_max=1000, stop_when_success=True, raw=None):
     the call's first improvement, where a running minimum and one frozen at the start of the group differ), ``rewire_ties`` near nodes with ``cost_new == costs[j]``
     in pass 2.  ``raw``: the problem's block of raw doubles (``draws_per_problem`` of them) instead of
     ``RandomState(seed).random_sample(...)``; ``seed`` is not used then."""
-    env = _problem_env(problem)
+    env = problem_env(problem, 'rrtstar')
     dim = env.config_dim
     low, ranges = sample_bounds(dim)
     if raw is None:
@@ -283,9 +270,7 @@ def rrtstar_plan(maps, init64, goal64, draws, t_max, stop_when_success=True):
     ws = torch.empty(need.value, dtype=torch.uint8, device=dev) if need.value else None
     batch = _lib.RRTStarBatch(B, dim, int(maps.shape[1]), int(t_max), 1 if stop_when_success else 0, int(draws.shape[1]),
                               maps.data_ptr(), init64.data_ptr(), goal64.data_ptr(), draws.data_ptr())
-    tree = _lib.RRTStarTree(*(out[k].data_ptr() for k in ('states', 'parents', 'rewired_parents', 'flags', 'costs', 'path_lengths',
-                                                           'cumulated_checks', 'path')),
-                            *(out['small'][r].data_ptr() for r in range(6)))
+    tree = _lib.RRTStarTree(*(out[k].data_ptr() for k in TREE_TENSORS), *(out['small'][r].data_ptr() for r in range(6)))
     with torch.cuda.device(dev):
         _lib.check(L.gnnmp_rrtstar_plan(ctypes.byref(batch), ctypes.byref(tree), ws.data_ptr() if ws is not None else None,
                                         need.value, torch.cuda.current_stream(dev).cuda_stream), 'gnnmp_rrtstar_plan')
@@ -304,62 +289,43 @@ def plan_maze_batch(problems, device, seeds, t_max=1000, stop_when_success=True,
     advanced by the kernel's ``used`` counts, so their state afterwards is numpy's after the plan (``streams_out``: a list
     that receives the :class:`MTStreams` object).  Returns one dict per problem with :func:`plan_host`'s tree fields plus
     ``status`` (0 = fine; a non-zero one raises)."""
-    import time
     import torch
-
-    def mark(name, t_prev):
-        if timings is None:
-            return t_prev
-        torch.cuda.current_stream().synchronize()
-        now = time.perf_counter()
-        timings[name] = timings.get(name, 0.) + now - t_prev
-        return now
+    who = 'rrtstar.plan_maze_batch'
     B, t_max = len(problems), int(t_max)
     if B == 0:
         return []
-    if len(seeds) != B:
-        raise ValueError('rrtstar.plan_maze_batch: one seed per problem')
+    check_stream_args(B, seeds, draws, who)
     if t_max < 1:
         raise ValueError('rrtstar.plan_maze_batch: t_max >= 1')
-    if draws not in ('host', 'device'):
-        raise ValueError("rrtstar.plan_maze_batch: draws is 'host' or 'device'")
     dev = torch.device(device)
-    dims = {int(np.asarray(pr['init_state']).reshape(-1).shape[0]) for pr in problems}
-    if len(dims) != 1:
-        raise ValueError('rrtstar.plan_maze_batch: point-robot and stick-robot problems in one batch')
-    dim = dims.pop()
-    _maze_class(dim)
-    n_draws = draws_per_problem(t_max, dim)
-    f64 = lambda key: torch.from_numpy(np.ascontiguousarray(np.asarray(        # noqa: E731
-        [np.asarray(pr[key], dtype=np.float64).reshape(-1) if key != 'map' else np.asarray(pr[key], dtype=np.float64) for pr in problems]))).to(dev)
-    tm = time.perf_counter()
+    clock = StageClock(timings)
     with torch.cuda.device(dev):
-        maps, init64, goal64 = f64('map'), f64('init_state'), f64('goal_state')
-        if draws == 'device':
-            from .rng import MTStreams
-            streams = MTStreams(seeds, dev)
-            rows, gstat = streams.uniform([n_draws] * B, 0.0, 1.0)       # low 0, range 1: the raw doubles; not committed
-            raw = rows.reshape(B, n_draws)
-        else:
-            raw = torch.from_numpy(np.stack([np.random.RandomState(int(s) & 0xffffffff).random_sample(n_draws) for s in seeds])).to(dev)
-        tm = mark('draws', tm)
-        out = rrtstar_plan(maps, init64, goal64, raw, t_max, stop_when_success)
-        if draws == 'device':
-            streams.advance(out['small'][3], 1)                          # by the doubles each problem consumed
-            if gstat.cpu().numpy().any():
-                raise RuntimeError('gnnmp_mt19937_uniform: a stream reported a status')
-            if streams_out is not None:
-                streams_out.append(streams)
-        tm = mark('plan', tm)
-        n_nodes, success, last_i, used, plen, status = out['small'].cpu().numpy()
+        dim, maps, init64, goal64 = problem_tensors(problems, dev, who)
+        maze_class(dim, 'rrtstar')
+        block = RawDoubles(seeds, draws_per_problem(t_max, dim), dev, draws)
+        clock.mark('draws')
+        out = rrtstar_plan(maps, init64, goal64, block.raw, t_max, stop_when_success)
+        block.finish(out['small'][3], streams_out)                       # by the doubles each problem consumed
+        clock.mark('plan')
+        small = out['small'].cpu().numpy()
+        status = small[5]
         if status.any():
             bad = np.flatnonzero(status)
             raise RuntimeError('gnnmp_rrtstar_plan: status %s for problem(s) %s (1 = draw block too short, 2 = cycle in rewired_parents)'
                                % (status[bad].tolist(), bad.tolist()))
-        host = {k: out[k].cpu().numpy() for k in ('states', 'parents', 'rewired_parents', 'flags', 'costs', 'path_lengths',
-                                                  'cumulated_checks', 'path')}
+        host = {k: out[k].cpu().numpy() for k in TREE_TENSORS}
+    res = tree_results(host, small)
+    clock.mark('results')
+    return res
+
+
+def tree_results(host, small):
+    """One dict per problem with :func:`plan_host`'s tree fields plus ``status``, from the host copies ``host`` of the device
+    tree (:data:`TREE_TENSORS`, ``[B, t_max + 1, ...]``) and its per-problem words ``small`` (rows n_nodes, success,
+    last_iter, used, path_len, status)."""
+    n_nodes, success, last_i, used, plen, status = small[:6]
     res = []
-    for b in range(B):
+    for b in range(len(n_nodes)):
         n = int(n_nodes[b])
         pts = host['states'][b, :n].copy()
         ids = host['path'][b, :plen[b]].astype(np.int64)
@@ -370,7 +336,6 @@ def plan_maze_batch(problems, device, seeds, t_max=1000, stop_when_success=True,
                     'path_lengths': host['path_lengths'][b, :n].copy(),
                     'cumulated_collision_checks': host['cumulated_checks'][b, :n].copy(), 'success': bool(success[b]),
                     'i': int(last_i[b]), 'path_ids': ids, 'path': pts[ids], 'draws': int(used[b]), 'status': int(status[b])})
-    mark('results', tm)
     return res
 
 
@@ -391,19 +356,13 @@ def eval_rrt_device(env, indexes, seed=1234, seeds=None, t_max=1000, device='cud
     :func:`plan_maze_batch` with ``stop_when_success=True``, ``chunk`` problems per launch: ``(n_success, collision,
     solution_cost, paths)`` -- see :func:`eval_aggregate` for the first-iteration quirk of ``collision``; ``paths`` are the
     float64 states of ``search_tree.path()``.  Problem ``indexes[i]`` draws from ``np.random.RandomState(seeds[i])``; default
-    :func:`gnnmp.planner.stream_seeds`.  The numbers DIFFER from ``eval_rrt``'s, which walks ONE global stream problem after
+    :func:`gnnmp.streams_batch.stream_seeds`.  The numbers DIFFER from ``eval_rrt``'s, which walks ONE global stream problem after
     problem -- other samples of the same distribution -- and in exchange they do not depend on the order of ``indexes`` or on
     ``chunk``.  ``rows_out``: a list that receives per problem (success, checks with the quirk, path_lengths[-1], nodes,
     last iteration).  The global numpy generator is left alone."""
-    from .planner import stream_seeds
-    indexes = list(indexes)
-    seeds = stream_seeds(seed, indexes) if seeds is None else list(seeds)
     results = []
-    for c0 in range(0, len(indexes), max(int(chunk), 1)):
-        part = indexes[c0:c0 + max(int(chunk), 1)]
-        pr = [dict(map=env.maps[i], init_state=env.init_states[i], goal_state=env.goal_states[i]) for i in part]
-        results.extend(plan_maze_batch(pr, device, seeds[c0:c0 + len(part)], t_max=t_max, stop_when_success=True, draws=draws,
-                                       timings=timings))
+    for pr, chunk_seeds in eval_chunks(env, indexes, seed, seeds, chunk):
+        results.extend(plan_maze_batch(pr, device, chunk_seeds, t_max=t_max, stop_when_success=True, draws=draws, timings=timings))
     if rows_out is not None:
         rows_out.extend((int(r['success']), int(r['cumulated_collision_checks'][-1]) - int(r['cumulated_collision_checks'][1]),
                          float(r['path_lengths'][-1]), r['states'].shape[0], r['i']) for r in results)
