@@ -505,6 +505,17 @@ def manifest(kind, dims):
     return out
 
 
+def grads_by_manifest(grad, manifest, tensors, trainable):
+    """The flat gradient blob of a train_backward call cut by ``manifest`` into one gradient per parameter of ``tensors``,
+    ``None`` where ``trainable(name)`` is false.  Parameters may live on the host (the reference keeps them wherever .to() put
+    them): gradients follow them."""
+    out, off = [], 0
+    for (name, numel), t in zip(manifest, tensors):
+        out.append(grad[off:off + numel].view_as(t).to(t.device) if trainable(name) else None)
+        off += numel
+    return tuple(out)
+
+
 class NativeHandle:
     """Owns one gnnmp_*_create handle: destroyed when the last reference goes (the module drops its reference when the
     weights change; an autograd graph keeps the handle its forward ran with until its backward is done)."""

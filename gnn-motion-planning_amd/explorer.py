@@ -75,24 +75,26 @@ def _check_edge_ids(batch):
 class _TrainScores(torch.autograd.Function):
     """Per-edge scores with gradients for the parameters the reference's policy loss trains (train_explorer.py:156-186;
     node_free_code / edge_free_code are detached at model.py:141,142,146, so the obstacle-attention stack gets none).
-    Forward and backward run in libgnnmp.so (gnnmp_explorer_train_forward / _backward)."""
+    Forward and backward run in libgnnmp.so: ``entry`` + _workspace_bytes / _forward / _backward, with the host arguments
+    ``host`` after the batch -- gnnmp_explorer_train with (loop,), or gnnmp_explorer_train_batch with the int32 arrays
+    (loops, node_counts, edge_counts) of graphs ordered longest loop first: one forward and one backward whatever the loop
+    values are."""
 
     @staticmethod
-    def forward(ctx, model, batch, loop, *params):
+    def forward(ctx, model, batch, entry, host, *params):
         dev = batch.v.device
         h = model._native(dev)
         cb = model._cbatch(batch)
         need = ctypes.c_size_t()
-        _lib.check(_lib.lib().gnnmp_explorer_train_workspace_bytes(h, ctypes.byref(cb), int(loop), ctypes.byref(need)),
-                   'gnnmp_explorer_train_workspace_bytes')
+        _lib.check(getattr(_lib.lib(), entry + '_workspace_bytes')(h, ctypes.byref(cb), *host, ctypes.byref(need)),
+                   entry + '_workspace_bytes')
         ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
         scores = torch.empty(batch.total_edges, dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
             st = torch.cuda.current_stream().cuda_stream
-            _lib.check(_lib.lib().gnnmp_explorer_train_forward(h, ctypes.byref(cb), int(loop), 1 if model.use_obstacles else 0,
-                                                               scores.data_ptr(), ws.data_ptr(), ws.numel(), st),
-                       'gnnmp_explorer_train_forward')
-        ctx.model, ctx.batch, ctx.loop, ctx.ws, ctx.handle = model, batch, int(loop), ws, h
+            _lib.check(getattr(_lib.lib(), entry + '_forward')(h, ctypes.byref(cb), *host, 1 if model.use_obstacles else 0,
+                                                               scores.data_ptr(), ws.data_ptr(), ws.numel(), st), entry + '_forward')
+        ctx.model, ctx.batch, ctx.entry, ctx.host, ctx.ws, ctx.handle = model, batch, entry, host, ws, h
         return scores
 
     @staticmethod
@@ -104,59 +106,11 @@ class _TrainScores(torch.autograd.Function):
         d_scores = d_scores.contiguous().float()
         with torch.cuda.device(dev):
             st = torch.cuda.current_stream().cuda_stream
-            _lib.check(_lib.lib().gnnmp_explorer_train_backward(ctx.handle, ctypes.byref(cb), ctx.loop, d_scores.data_ptr(),
-                                                                grad.data_ptr(), ctx.ws.data_ptr(), ctx.ws.numel(), st),
-                       'gnnmp_explorer_train_backward')
-        out, off = [], 0
-        for (name, numel), t in zip(model._manifest, model._live_weights()):
-            # parameters may live on the host (the reference keeps them wherever .to() put them): gradients follow them
-            g = grad[off:off + numel].view_as(t).to(t.device) if name.split('.')[0] in TRAINABLE else None
-            out.append(g)
-            off += numel
-        return (None, None, None) + tuple(out)
-
-
-class _TrainScoresBatch(torch.autograd.Function):
-    """:class:`_TrainScores` with a loop count per graph, graphs longest loop first (gnnmp_explorer_train_batch_forward /
-    _backward): one forward and one backward whatever the loop values are."""
-
-    @staticmethod
-    def forward(ctx, model, batch, loops, node_counts, edge_counts, *params):
-        dev = batch.v.device
-        h = model._native(dev)
-        cb = model._cbatch(batch)
-        host = tuple(_lib.i32_array(x) for x in (loops, node_counts, edge_counts))
-        need = ctypes.c_size_t()
-        _lib.check(_lib.lib().gnnmp_explorer_train_batch_workspace_bytes(h, ctypes.byref(cb), *host, ctypes.byref(need)),
-                   'gnnmp_explorer_train_batch_workspace_bytes')
-        ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
-        scores = torch.empty(batch.total_edges, dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            st = torch.cuda.current_stream().cuda_stream
-            _lib.check(_lib.lib().gnnmp_explorer_train_batch_forward(h, ctypes.byref(cb), *host, 1 if model.use_obstacles else 0,
-                                                                     scores.data_ptr(), ws.data_ptr(), ws.numel(), st),
-                       'gnnmp_explorer_train_batch_forward')
-        ctx.model, ctx.batch, ctx.host, ctx.ws, ctx.handle = model, batch, host, ws, h
-        return scores
-
-    @staticmethod
-    def backward(ctx, d_scores):
-        model, batch, dev = ctx.model, ctx.batch, ctx.batch.v.device
-        cb = model._cbatch(batch)
-        n = int(_lib.lib().gnnmp_explorer_grad_floats(ctx.handle))
-        grad = torch.empty(n, dtype=torch.float32, device=dev)
-        d_scores = d_scores.contiguous().float()
-        with torch.cuda.device(dev):
-            st = torch.cuda.current_stream().cuda_stream
-            _lib.check(_lib.lib().gnnmp_explorer_train_batch_backward(ctx.handle, ctypes.byref(cb), *ctx.host, d_scores.data_ptr(),
-                                                                      grad.data_ptr(), ctx.ws.data_ptr(), ctx.ws.numel(), st),
-                       'gnnmp_explorer_train_batch_backward')
-        out, off = [], 0
-        for (name, numel), t in zip(model._manifest, model._live_weights()):
-            g = grad[off:off + numel].view_as(t).to(t.device) if name.split('.')[0] in TRAINABLE else None
-            out.append(g)
-            off += numel
-        return (None, None, None, None, None) + tuple(out)
+            _lib.check(getattr(_lib.lib(), ctx.entry + '_backward')(ctx.handle, ctypes.byref(cb), *ctx.host, d_scores.data_ptr(),
+                                                                    grad.data_ptr(), ctx.ws.data_ptr(), ctx.ws.numel(), st),
+                       ctx.entry + '_backward')
+        return (None, None, None, None) + _lib.grads_by_manifest(grad, model._manifest, model._live_weights(),
+                                                                 lambda name: name.split('.')[0] in TRAINABLE)
 
 
 # top-level modules that receive a gradient from the policy loss (everything else forward() reads is behind a detach)
@@ -496,7 +450,7 @@ class EncoderProcessDecoder(nn.Module):
         if batch.v.device.type != 'cuda':
             raise RuntimeError('gnnmp runs on the GPU only (got %s tensors); there is no CPU fallback' % batch.v.device)
         self._native(batch.v.device)                      # builds the manifest / packed + raw weights on the device
-        return _TrainScores.apply(self, batch, loop, *self._live_weights())
+        return _TrainScores.apply(self, batch, 'gnnmp_explorer_train', (int(loop),), *self._live_weights())
 
     def train_scores_batch(self, batch, loops, node_counts=None, edge_counts=None):
         """:meth:`train_scores` with a loop count per graph (train_explorer.py:148 draws one per sample): graph g's scores are
@@ -529,12 +483,11 @@ class EncoderProcessDecoder(nn.Module):
             raise ValueError('node_counts / edge_counts must have one entry per graph')
         self._native(batch.v.device)
         order = sorted(range(G), key=lambda g: -loops[g])                               # stable: ties keep the caller's order
+        host = tuple(_lib.i32_array([x[g] for g in order]) for x in (loops, node_counts, edge_counts))
         if order == list(range(G)):
-            return _TrainScoresBatch.apply(self, batch, loops, node_counts, edge_counts, *self._live_weights())
+            return _TrainScores.apply(self, batch, 'gnnmp_explorer_train_batch', host, *self._live_weights())
         sb, inv = self._sorted_batch(batch, order, node_counts, edge_counts)
-        scores = _TrainScoresBatch.apply(self, sb, [loops[g] for g in order], [node_counts[g] for g in order],
-                                         [edge_counts[g] for g in order], *self._live_weights())
-        return scores[inv]
+        return _TrainScores.apply(self, sb, 'gnnmp_explorer_train_batch', host, *self._live_weights())[inv]
 
     @staticmethod
     def _sorted_batch(batch, order, node_counts, edge_counts):

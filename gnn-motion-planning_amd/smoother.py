@@ -123,32 +123,33 @@ def _check_limits(sb):
 
 
 class _TrainSmooth(torch.autograd.Function):
-    """New path [P, C] of ONE smoothing problem with gradients for the smoother's parameters, the way the reference
-    trains it (train_smoother.py:33-61, model.train()): BatchNorm with batch statistics, gradients through the loop's
-    in-place path updates.  Forward and backward run in libgnnmp.so (gnnmp_smoother_train_forward / _backward)."""
+    """New waypoints with gradients for the smoother's parameters, the way the reference trains it (train_smoother.py:33-61,
+    model.train()): BatchNorm with batch statistics, gradients through the loop's in-place path updates.  Forward and backward
+    run in libgnnmp.so: ``entry`` + _workspace_bytes / _forward / _backward -- gnnmp_smoother_train for ONE problem [P, C]
+    with ``loop`` an int, or gnnmp_smoother_train_batch for B problems [sum P, C] ordered by loop count, longest first, with
+    ``loop`` that order's ctypes int32 array: B per-problem calls as one.  The BatchNorm batch statistics land in ``stats``
+    ([max(loop, 1), 2, d], or [B, max loop, 2, d]: plain output, no gradient)."""
 
     @staticmethod
-    def forward(ctx, model, sb, loop, *params):
+    def forward(ctx, model, sb, entry, loop, stats, *params):
         dev = sb.path.device
         _check_limits(sb)
         h = model._native(dev, for_training=True)
         cb = _cbatch(sb)
         need = ctypes.c_size_t()
-        _lib.check(_lib.lib().gnnmp_smoother_train_workspace_bytes(h, ctypes.byref(cb), int(loop), ctypes.byref(need)),
-                   'gnnmp_smoother_train_workspace_bytes')
+        _lib.check(getattr(_lib.lib(), entry + '_workspace_bytes')(h, ctypes.byref(cb), loop, ctypes.byref(need)),
+                   entry + '_workspace_bytes')
         ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
         out = torch.empty_like(sb.path)
-        stats = torch.zeros(max(int(loop), 1), 2, model.embed_size, dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
             st = torch.cuda.current_stream().cuda_stream
-            _lib.check(_lib.lib().gnnmp_smoother_train_forward(h, ctypes.byref(cb), int(loop), out.data_ptr(), stats.data_ptr(),
-                                                               ws.data_ptr(), ws.numel(), st), 'gnnmp_smoother_train_forward')
-        ctx.model, ctx.sb, ctx.loop, ctx.ws, ctx.handle, ctx.names = model, sb, int(loop), ws, h, [n for n, _ in model._manifest]
-        ctx.mark_non_differentiable(stats)
-        return out, stats
+            _lib.check(getattr(_lib.lib(), entry + '_forward')(h, ctypes.byref(cb), loop, out.data_ptr(), stats.data_ptr(),
+                                                               ws.data_ptr(), ws.numel(), st), entry + '_forward')
+        ctx.model, ctx.sb, ctx.entry, ctx.loop, ctx.ws, ctx.handle = model, sb, entry, loop, ws, h
+        return out
 
     @staticmethod
-    def backward(ctx, d_out, _d_stats):
+    def backward(ctx, d_out):
         model, sb, dev = ctx.model, ctx.sb, ctx.sb.path.device
         cb = _cbatch(sb)
         n = int(_lib.lib().gnnmp_smoother_grad_floats(ctx.handle))
@@ -156,16 +157,12 @@ class _TrainSmooth(torch.autograd.Function):
         d_out = d_out.contiguous().float()
         with torch.cuda.device(dev):
             st = torch.cuda.current_stream().cuda_stream
-            _lib.check(_lib.lib().gnnmp_smoother_train_backward(ctx.handle, ctypes.byref(cb), ctx.loop, d_out.data_ptr(),
-                                                                grad.data_ptr(), ctx.ws.data_ptr(), ctx.ws.numel(), st),
-                       'gnnmp_smoother_train_backward')
+            _lib.check(getattr(_lib.lib(), ctx.entry + '_backward')(ctx.handle, ctypes.byref(cb), ctx.loop, d_out.data_ptr(),
+                                                                    grad.data_ptr(), ctx.ws.data_ptr(), ctx.ws.numel(), st),
+                       ctx.entry + '_backward')
         sd = model.state_dict(keep_vars=True)
-        out, off = [], 0
-        for name, numel in model._manifest:
-            t = sd[name]
-            out.append(grad[off:off + numel].view_as(t).to(t.device) if name in SMOOTHER_TRAINABLE else None)
-            off += numel
-        return (None, None, None) + tuple(out)
+        return (None, None, None, None, None) + _lib.grads_by_manifest(grad, model._manifest, [sd[n] for n, _ in model._manifest],
+                                                                       lambda name: name in SMOOTHER_TRAINABLE)
 
 
 def _reordered(sb, order):
@@ -183,53 +180,6 @@ def _reordered(sb, order):
                                    sb.collided.index_select(0, rows(sb.coll_counts)),
                                    sb.edge_index.index_select(1, rows(sb.edge_counts)), pick(sb.path_counts),
                                    pick(sb.free_counts), pick(sb.coll_counts), pick(sb.edge_counts))
-
-
-class _TrainSmoothBatch(torch.autograd.Function):
-    """New waypoints [sum P, C] of B smoothing problems, each with its own loop count, with gradients for the smoother's
-    parameters: B calls of :class:`_TrainSmooth` as one (gnnmp_smoother_train_batch_forward / _backward).  ``sb`` holds the
-    problems ordered by loop count, longest first; ``loops`` is that order's ctypes int32 array."""
-
-    @staticmethod
-    def forward(ctx, model, sb, loops, *params):
-        dev = sb.path.device
-        _check_limits(sb)
-        h = model._native(dev, for_training=True)
-        cb = _cbatch(sb)
-        need = ctypes.c_size_t()
-        _lib.check(_lib.lib().gnnmp_smoother_train_batch_workspace_bytes(h, ctypes.byref(cb), loops, ctypes.byref(need)),
-                   'gnnmp_smoother_train_batch_workspace_bytes')
-        ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
-        out = torch.empty_like(sb.path)
-        stats = torch.empty(sb.n, max(loops), 2, model.embed_size, dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            st = torch.cuda.current_stream().cuda_stream
-            _lib.check(_lib.lib().gnnmp_smoother_train_batch_forward(h, ctypes.byref(cb), loops, out.data_ptr(), stats.data_ptr(),
-                                                                     ws.data_ptr(), ws.numel(), st),
-                       'gnnmp_smoother_train_batch_forward')
-        ctx.model, ctx.sb, ctx.loops, ctx.ws, ctx.handle = model, sb, loops, ws, h
-        ctx.mark_non_differentiable(stats)
-        return out, stats
-
-    @staticmethod
-    def backward(ctx, d_out, _d_stats):
-        model, sb, dev = ctx.model, ctx.sb, ctx.sb.path.device
-        cb = _cbatch(sb)
-        n = int(_lib.lib().gnnmp_smoother_grad_floats(ctx.handle))
-        grad = torch.empty(n, dtype=torch.float32, device=dev)
-        d_out = d_out.contiguous().float()
-        with torch.cuda.device(dev):
-            st = torch.cuda.current_stream().cuda_stream
-            _lib.check(_lib.lib().gnnmp_smoother_train_batch_backward(ctx.handle, ctypes.byref(cb), ctx.loops, d_out.data_ptr(),
-                                                                      grad.data_ptr(), ctx.ws.data_ptr(), ctx.ws.numel(), st),
-                       'gnnmp_smoother_train_batch_backward')
-        sd = model.state_dict(keep_vars=True)
-        out, off = [], 0
-        for name, numel in model._manifest:
-            t = sd[name]
-            out.append(grad[off:off + numel].view_as(t).to(t.device) if name in SMOOTHER_TRAINABLE else None)
-            off += numel
-        return (None, None, None) + tuple(out)
 
 
 class ModelSmoother(nn.Module):
@@ -418,7 +368,8 @@ class ModelSmoother(nn.Module):
         sb = SmoothBatch([path], [free], [collided], [edge_index], path.device)
         self._native(path.device, for_training=True)
         sd = self.state_dict(keep_vars=True)
-        out, stats = _TrainSmooth.apply(self, sb, loop, *[sd[n] for n, _ in self._manifest])
+        stats = torch.zeros(max(int(loop), 1), 2, self.embed_size, dtype=torch.float32, device=path.device)
+        out = _TrainSmooth.apply(self, sb, 'gnnmp_smoother_train', int(loop), stats, *[sd[n] for n, _ in self._manifest])
         bn = self.node_code[1]
         with torch.no_grad():
             for it in range(int(loop)):
@@ -454,7 +405,8 @@ class ModelSmoother(nn.Module):
         self._native(sb.path.device, for_training=True)
         sd = self.state_dict(keep_vars=True)
         c_loops = (ctypes.c_int32 * sb.n)(*[loops[b] for b in order])
-        out, stats = _TrainSmoothBatch.apply(self, run, c_loops, *[sd[n] for n, _ in self._manifest])
+        stats = torch.empty(sb.n, max(loops), 2, self.embed_size, dtype=torch.float32, device=sb.path.device)
+        out = _TrainSmooth.apply(self, run, 'gnnmp_smoother_train_batch', c_loops, stats, *[sd[n] for n, _ in self._manifest])
         if not ordered:                       # rows back in the caller's order (differentiable)
             starts = [0]
             for b in order:

@@ -2,7 +2,8 @@
 episodes.forward_scores_batched): one forward and one backward for a batch whose graphs stop after their own number of
 iterations (train_explorer.py:148 draws one per sample).
 
-  1  uniform loops are the existing call, bit for bit (scores and parameter gradients)
+  1  uniform loops are the existing call, bit for bit (scores and parameter gradients); the existing call past the batched
+     call's loop bound
   2  ragged loops against the fp64 oracle: scores per graph at the bar of parity_bar.py, gradients against the SUM over
      graphs of the oracle's float64 gradients at the bound of test_explorer_autograd_gpu.py,
          |g - g64| <= max(1e-4 max|g64|, 4 own) + 1e-6 per tensor, own = max|g32 - g64| of the same oracle in float32;
@@ -156,6 +157,38 @@ def test_uniform_loops_are_the_existing_call():
         # and with the host sizes handed in instead of read back
         s2 = m.train_scores_batch(b, [L] * 3, [40, 64, 130], [g['edge_index'].shape[1] for g in graphs])
         assert torch.equal(s0.detach(), s2.detach())
+
+
+def test_uniform_call_past_the_batched_loop_bound():
+    """train_scores takes any loop count (its plan is one row count, not a table of TRAIN_BATCH_MAX_LOOP entries);
+    train_scores_batch keeps its bound."""
+    L = _lib.TRAIN_BATCH_MAX_LOOP + 1
+    graphs = graphs_of('maze2', (33,), 4, 100)
+    m = make('maze2')
+    b = batch_of('maze2', graphs)
+    coef = coef_of(graphs).float().to(DEV)
+    runs = []
+    for _ in range(2):
+        s = m.train_scores(b, L)
+        runs.append((s.detach().clone(), grads_of(m, (s * coef).sum())))
+    s0, g0 = runs[0]
+    assert s0.shape == (b.total_edges,) and bool(torch.isfinite(s0).all())
+    assert_frozen_untouched(m, g0)
+    assert all(bool(torch.isfinite(g).all()) for g in g0.values())
+    assert torch.equal(s0, runs[1][0]) and set(g0) == set(runs[1][1])
+    for n in g0:
+        assert torch.equal(g0[n], runs[1][1][n]), n
+    with pytest.raises(ValueError):
+        m.train_scores_batch(b, [L])
+    g, w = graphs[0], load_weights(ENVS['maze2']['ckpt'])
+    ref = {}
+    for dt in (torch.float32, torch.float64):
+        wd = {n: (t.to(dt) if t.is_floating_point() else t) for n, t in w.items()}
+        with torch.no_grad():
+            ref[dt] = ref_cpu.explorer_forward(wd, g['v'].to(dt), g['goal'].to(dt), g['obstacles'].to(dt), g['edge_index'], L,
+                                               use_obstacles=True, detach=True)
+    c = assert_fp32_parity(s0.cpu(), ref[torch.float32], ref[torch.float64], 'maze2 N 33 loop %d' % L)
+    print('loop %d: max|gpu - oracle64| %.3e  own %.3e  bar %.3e' % (L, c['err64'], c['own'], c['atol']))
 
 
 # ---------------------------------------------------------------------------------------------------------------- 2

@@ -50,12 +50,12 @@ def timed(fn, reps=REPS):
     return a.elapsed_time(b) / reps
 
 
-def train_launches(loop, batched):
+def train_launches(loop):
     """Kernel launches of one training forward + backward at `loop` iterations, counted from csrc/api.cpp
-    (gnnmp_explorer_train_forward / _backward and their _batch_ forms): forward 18 + 8 per iteration, backward 34 + 25 per
-    iteration (a weight gradient is two launches); the batched backward has one more (the decoder gradient waits in a buffer
-    of its own).  Not counted: the frozen attention front stage (once per call in both forms), memsets, torch's own kernels."""
-    return 18 + 8 * loop + 34 + 25 * loop + (1 if batched else 0)
+    (explorer_train_forward_body / _backward_body, one pair behind both forms): forward 18 + 8 per iteration, backward 35 + 25
+    per iteration (a weight gradient is two launches; the decoder gradient waits in a buffer of its own and t_seed_dh fetches
+    it).  Not counted: the frozen attention front stage (once per call in both forms), memsets, torch's own kernels."""
+    return 18 + 8 * loop + 35 + 25 * loop
 
 
 def workspace_bytes(m, g, goal, loops, batched):
@@ -125,7 +125,7 @@ def main():
             if r < 2:
                 reps_g.append(timed(fb))
         legs.append(dict(B=B, edges=g.total_edges, loops=sorted(set(loops)), grouped=reps_g, batched=reps_b,
-                         launches_g=sum(train_launches(lp, False) for lp in set(loops)), launches_b=train_launches(max(loops), True),
+                         launches_g=sum(train_launches(lp) for lp in set(loops)), launches_b=train_launches(max(loops)),
                          ws_g=workspace_bytes(m, g, paths['goal'], loops, False), ws_b=workspace_bytes(m, g, paths['goal'], loops, True)))
 
         def episodes():
