@@ -25,7 +25,7 @@ from .next_model import Model2D, NextNet  # noqa: F401,E402
 from .next_plan import plan_host as next_plan_host  # noqa: F401,E402
 from . import next_model3d  # noqa: F401,E402  (the NEXT planning network of the arm families: gnnmp_next3d_*)
 from .next_model3d import Model3D, NextNet3D  # noqa: F401,E402
-from . import next_train  # noqa: F401,E402  (NEXT training, host side: get_label, train()'s loss, the adjoint of pack_weights)
+from . import next_train  # noqa: F401,E402  (NEXT training: labels, loss, packing and its adjoint, NextNetTrain on the device)
 
 __all__ = ['graph_build', 'hostenv', 'synth', 'GraphBatch', 'EncoderProcessDecoder', 'ModelSmoother', 'SmoothBatch', 'episodes',
            'oracle_smooth', 'frontier', 'rng', 'lazysp', 'eval_lazysp_device', 'lazysp_plan_host', 'plan_lazysp_maze_batch', 'rrtstar',

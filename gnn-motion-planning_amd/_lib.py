@@ -127,6 +127,22 @@ class NextStateForward(ctypes.Structure):
                 ('weights', ctypes.c_void_p), ('y', ctypes.c_void_p), ('status', ctypes.c_void_p)]
 
 
+class NextTrain(ctypes.Structure):              # gnnmp_next_train
+    _fields_ = [('n_problems', ctypes.c_int32), ('n_states', ctypes.c_int32), ('dim', ctypes.c_int32), ('width', ctypes.c_int32),
+                ('iters', ctypes.c_int32), ('maps', ctypes.c_void_p), ('goals', ctypes.c_void_p), ('states', ctypes.c_void_p),
+                ('problem_of_state', ctypes.c_void_p), ('weights', ctypes.c_void_p), ('pb_rep', ctypes.c_void_p),
+                ('y', ctypes.c_void_p), ('status', ctypes.c_void_p), ('workspace', ctypes.c_void_p),
+                ('workspace_bytes', ctypes.c_size_t)]
+
+
+class NextTrainBwd(ctypes.Structure):           # gnnmp_next_train_bwd
+    _fields_ = [('n_problems', ctypes.c_int32), ('n_states', ctypes.c_int32), ('dim', ctypes.c_int32), ('width', ctypes.c_int32),
+                ('iters', ctypes.c_int32), ('goals', ctypes.c_void_p), ('states', ctypes.c_void_p),
+                ('problem_of_state', ctypes.c_void_p), ('weights', ctypes.c_void_p), ('weights_t', ctypes.c_void_p),
+                ('pb_rep', ctypes.c_void_p), ('dy', ctypes.c_void_p), ('dpb_rep', ctypes.c_void_p), ('dweights', ctypes.c_void_p),
+                ('workspace', ctypes.c_void_p), ('workspace_bytes', ctypes.c_size_t)]
+
+
 class Next3dPbForward(ctypes.Structure):
     _fields_ = [('n_problems', ctypes.c_int32), ('dim', ctypes.c_int32), ('point_dim', ctypes.c_int32), ('width', ctypes.c_int32),
                 ('iters', ctypes.c_int32), ('maps', ctypes.c_void_p), ('goals', ctypes.c_void_p), ('weights', ctypes.c_void_p),
@@ -293,6 +309,11 @@ def lib():
     L.gnnmp_next_weights_floats.argtypes = [ctypes.c_int32, ctypes.POINTER(sz)]
     L.gnnmp_next_pb_forward.argtypes = [ctypes.POINTER(NextPbForward), vp]
     L.gnnmp_next_state_forward.argtypes = [ctypes.POINTER(NextStateForward), vp]
+    L.gnnmp_next_train_workspace_bytes.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(sz)]
+    L.gnnmp_next_weights_t_floats.argtypes = [ctypes.c_int32, ctypes.POINTER(sz)]
+    L.gnnmp_next_train_forward.argtypes = [ctypes.POINTER(NextTrain), vp]
+    L.gnnmp_next_state_backward.argtypes = [ctypes.POINTER(NextTrainBwd), vp]
+    L.gnnmp_next_pb_backward.argtypes = [ctypes.POINTER(NextTrainBwd), vp]
     L.gnnmp_next3d_weights_floats.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(sz)]
     L.gnnmp_next3d_workspace_bytes.argtypes = [ctypes.c_int32, ctypes.POINTER(sz)]
     L.gnnmp_next3d_pb_forward.argtypes = [ctypes.POINTER(Next3dPbForward), vp]

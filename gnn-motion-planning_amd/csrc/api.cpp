@@ -1980,6 +1980,76 @@ extern "C" int gnnmp_next_state_forward(const gnnmp_next_states* d, void* hip_st
 }
 
 // =============================================================================================
+// training the NEXT network on maze problems (next_train_kernels.hip).  One order of checks for every entry point: the struct,
+// dims, negative counts, NULL arrays, then the no-work return BEFORE ANY HIP CALL (it writes nothing), then the workspace.
+// =============================================================================================
+extern "C" int gnnmp_next_train_workspace_bytes(int32_t n_problems, int32_t iters, int32_t n_states, size_t* bytes) {
+    if (!bytes) return GNNMP_ERR_NULL;
+    if (n_problems < 0 || iters < 0 || n_states < 0) return GNNMP_ERR_ARG;
+    NextTrainCarve c;
+    next_train_carve(n_problems, iters, n_states, c);
+    *bytes = c.total;
+    return GNNMP_OK;
+}
+
+extern "C" int gnnmp_next_weights_t_floats(int32_t dim, size_t* n_floats) {
+    if (!n_floats) return GNNMP_ERR_NULL;
+    if (dim != 2 && dim != 3) return GNNMP_ERR_DIMS;
+    *n_floats = next_weights_t_floats();
+    return GNNMP_OK;
+}
+
+static int next_train_ws(int32_t B, int32_t iters, int32_t S, const void* ws, size_t ws_bytes, NextTrainCarve& c) {
+    next_train_carve(B, iters, S, c);
+    if (ws_bytes < c.total || (reinterpret_cast<uintptr_t>(ws) & 255)) return GNNMP_ERR_WORKSPACE;
+    return GNNMP_OK;
+}
+
+extern "C" int gnnmp_next_train_forward(const gnnmp_next_train* d, void* hip_stream) {
+    if (!d) return GNNMP_ERR_NULL;
+    if (d->dim != 2 && d->dim != 3) return GNNMP_ERR_DIMS;
+    if (d->width != 15) return GNNMP_ERR_DIMS;
+    if (d->n_problems < 0 || d->n_states < 0 || d->iters < 0) return GNNMP_ERR_ARG;
+    if (!d->maps || !d->goals || !d->states || !d->problem_of_state || !d->weights || !d->pb_rep || !d->y || !d->status || !d->workspace)
+        return GNNMP_ERR_NULL;
+    if (d->n_problems == 0) return GNNMP_OK;                   // no work: no HIP call, nothing written
+    NextTrainCarve c;
+    if (int rc = next_train_ws(d->n_problems, d->iters, d->n_states, d->workspace, d->workspace_bytes, c)) return rc;
+    NextPbParams p;
+    p.B = d->n_problems; p.dim = d->dim; p.iters = d->iters;
+    p.maps = d->maps; p.goals = d->goals; p.weights = d->weights; p.pb_rep = d->pb_rep;
+    NextStateParams q;
+    q.S = d->n_states; q.B = d->n_problems; q.dim = d->dim;
+    q.states = d->states; q.problem_of_state = d->problem_of_state; q.pb_rep = d->pb_rep; q.weights = d->weights; q.y = d->y;
+    q.status = d->status;
+    HIP_TRY(launch_next_train_forward(p, q, static_cast<char*>(d->workspace), c, static_cast<hipStream_t>(hip_stream)));
+    return GNNMP_OK;
+}
+
+static int next_train_bwd(const gnnmp_next_train_bwd* d, void* hip_stream, bool state_call) {
+    if (!d) return GNNMP_ERR_NULL;
+    if (d->dim != 2 && d->dim != 3) return GNNMP_ERR_DIMS;
+    if (d->width != 15) return GNNMP_ERR_DIMS;
+    if (d->n_problems < 0 || d->n_states < 0 || d->iters < 0) return GNNMP_ERR_ARG;
+    if (!d->goals || !d->states || !d->problem_of_state || !d->weights || !d->weights_t || !d->pb_rep || !d->dy || !d->dpb_rep ||
+        !d->dweights || !d->workspace)
+        return GNNMP_ERR_NULL;
+    if (d->n_problems == 0 || (state_call && d->n_states == 0)) return GNNMP_OK;       // no work: no HIP call, nothing written
+    NextTrainBwdParams p;
+    if (int rc = next_train_ws(d->n_problems, d->iters, d->n_states, d->workspace, d->workspace_bytes, p.c)) return rc;
+    p.B = d->n_problems; p.S = d->n_states; p.dim = d->dim; p.iters = d->iters;
+    p.goals = d->goals; p.states = d->states; p.problem_of_state = d->problem_of_state; p.weights = d->weights;
+    p.weights_t = d->weights_t; p.pb_rep = d->pb_rep; p.dy = d->dy; p.dpb_rep = d->dpb_rep; p.dweights = d->dweights;
+    p.ws = static_cast<char*>(d->workspace);
+    if (state_call) HIP_TRY(launch_next_state_backward(p, static_cast<hipStream_t>(hip_stream)));
+    else HIP_TRY(launch_next_pb_backward(p, static_cast<hipStream_t>(hip_stream)));
+    return GNNMP_OK;
+}
+
+extern "C" int gnnmp_next_state_backward(const gnnmp_next_train_bwd* d, void* hip_stream) { return next_train_bwd(d, hip_stream, true); }
+extern "C" int gnnmp_next_pb_backward(const gnnmp_next_train_bwd* d, void* hip_stream) { return next_train_bwd(d, hip_stream, false); }
+
+// =============================================================================================
 // the NEXT planning network of the arm families (next3d_kernels.hip; next_model/model3D.py:87-213)
 // =============================================================================================
 static bool next3d_dims_ok(int32_t dim, int32_t point_dim) { return dim >= 1 && dim <= 15 && (point_dim == 3 || point_dim == 6); }

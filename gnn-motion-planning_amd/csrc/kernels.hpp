@@ -354,6 +354,36 @@ hipError_t launch_next_pb_forward(const NextPbParams& p, hipStream_t st);
 hipError_t launch_next_state_forward(const NextStateParams& p, hipStream_t st);
 size_t next_weights_floats();
 
+// ---- training the NEXT network on maze problems (next_train_kernels.hip): the forward that keeps its activations, the backward
+// byte offsets into the caller's workspace, every one a multiple of 256 and computed in size_t
+struct NextTrainCarve {
+    size_t saved;                         // float [B][saved_floats]: x9, hl, H [iters + 1], C [iters], X [iters] as [cell][channel] rows
+    size_t saved_floats;                  // floats a problem
+    size_t dg;                            // float [B][256][256]: a round's gate gradients
+    size_t part_pb;                       // double [B][conv / lstm range of the packed weights]
+    size_t part_goal;                     // double [B][attention range]
+    size_t goal_d;                        // double [B][225][8]: the gradient of x9's attention channels
+    size_t part_state;                    // double [S][per-state range]
+    size_t st_d;                          // double [S][528]: a12, dT, da12, da3 of a state
+    size_t attn_acc;                      // double [per-state range]: the sum over the states
+    size_t total;
+};
+void next_train_carve(int B, int iters, int S, NextTrainCarve& c);
+struct NextTrainBwdParams {
+    int B, S, dim, iters;
+    const float *goals, *states;          // [B, dim], [S, dim]
+    const int* problem_of_state;          // [S]
+    const float *weights, *weights_t;     // packed; the transposed packing (next_weights_t_floats())
+    const float *pb_rep, *dy;             // [B, 64, 15, 15] of the forward, [S, dim + 1]
+    float *dpb_rep, *dweights;            // [B, 64, 15, 15]; next_weights_floats()
+    char* ws;
+    NextTrainCarve c;
+};
+hipError_t launch_next_train_forward(const NextPbParams& pb, const NextStateParams& st, char* ws, const NextTrainCarve& c, hipStream_t s);
+hipError_t launch_next_state_backward(const NextTrainBwdParams& p, hipStream_t st);
+hipError_t launch_next_pb_backward(const NextTrainBwdParams& p, hipStream_t st);
+size_t next_weights_t_floats();
+
 // ---- the NEXT planning network of the arm families (next3d_kernels.hip, next_model/model3D.py:87-213)
 struct Next3dPbParams {
     int B, dim, pd, iters;                // problems, state size 1 .. 15, point size 3 / 6, LSTM rounds

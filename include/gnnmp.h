@@ -18,6 +18,8 @@
  *       not have at all (it attends over ALL obstacles it is given, model.py:125-130), reported without synchronising the forward
  *   gnnmp_next_weights_floats / gnnmp_next_pb_forward / gnnmp_next_state_forward      (ABI 8)
  *       PPN.pb_forward / PPN.state_forward, batched           next_model/model2D.py:151-210 (calls model2D.py:244, 254)
+ *   gnnmp_next_train_workspace_bytes / gnnmp_next_train_forward / gnnmp_next_state_backward / gnnmp_next_pb_backward
+ *       one training step of PPN: forward with saved activations, backward    train_next.py:41-69 (next_model/model2D.py:84-210)
  *   gnnmp_next_plan / gnnmp_next_plan_max_nodes                                       (ABI 9)
  *       NEXT_plan with a model, batched, one launch            algorithm/tsa.py:12-81, 141-220 (call eval_next.py:65)
  *   gnnmp_next3d_weights_floats / gnnmp_next3d_workspace_bytes / gnnmp_next3d_pb_forward / gnnmp_next3d_state_forward
@@ -940,6 +942,71 @@ int gnnmp_next_weights_floats(int32_t dim, size_t* n_floats);
  * 2 / 3, width not 15), GNNMP_ERR_ARG (n_problems / n_states < 0, iters < 0), GNNMP_ERR_NULL (an array). */
 int gnnmp_next_pb_forward(const gnnmp_next_pb* desc, void* hip_stream);
 int gnnmp_next_state_forward(const gnnmp_next_states* desc, void* hip_stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Training the NEXT planning network on maze problems (additive to ABI 9; next_train_kernels.hip) -- the forward that keeps its
+ * activations and the backward, for dim 2 / 3, width 15.
+ *   gnnmp_next_train_forward   what gnnmp_next_pb_forward followed by gnnmp_next_state_forward computes, with the same bits in
+ *                              pb_rep and y, and into the workspace x9, the hidden layer, every round's h and c going in and the
+ *                              conv output (about 3.6 MB a problem at 20 rounds).
+ *   gnnmp_next_state_backward  dy [S, dim + 1] -> dpb_rep [B, 64, 15, 15] and dweights[0, per-state range): the shared attention
+ *                              MLP, mlp.0, mlp.2 and the policy MLP, summed over the states in ascending state index in double.
+ *   gnnmp_next_pb_backward     dpb_rep -> dweights of hidden, h0, c0, conv and lstm, summed over the problems in ascending
+ *                              problem index in double.  The gradient also reaches the goal attention through x9: this call
+ *                              REWRITES the attention range of dweights (the six shared layers, mlp.0, mlp.2) as float(the state
+ *                              call's double sum, kept in the workspace, + the goals' sum in ascending problem index).  So it
+ *                              runs after gnnmp_next_state_backward on the same struct and workspace; with n_states == 0 the
+ *                              state sum counts as zero and the policy range is written as zero.
+ * dweights is float32, gnnmp_next_weights_floats long, in the packed layout; padding lanes receive zero.  When there is work
+ * (below) dweights and dpb_rep are overwritten, never accumulated into.  No floating-point atomics: two runs are bit-identical.
+ * A problem_of_state outside [0, B) is counted in the forward's status words, its row of y is NaN, and nothing is read or
+ * written for it in the forward or the backward.
+ *
+ * weights_t (gnnmp_next_weights_t_floats floats; gnnmp.next_train.pack_weights_t writes them): conv, h0 and c0 with flipped taps
+ * and the channel matrix transposed, in the convolution packing above, the LSTM's [256 gate rows][x 64 | h 64] in the MFMA
+ * packing, and 64 zeros.
+ *
+ * Checks, in this order, each before any HIP call: GNNMP_ERR_NULL (the struct), GNNMP_ERR_DIMS (dim not 2 / 3, width not 15),
+ * GNNMP_ERR_ARG (a negative count), GNNMP_ERR_NULL (an array), then GNNMP_OK WITHOUT ANY HIP CALL AND WITHOUT WRITING ANYTHING
+ * when there is no work -- n_problems == 0, and for gnnmp_next_state_backward n_states == 0 as well (gnnmp_next_train_forward
+ * with n_states == 0 computes pb_rep only) -- then GNNMP_ERR_WORKSPACE (workspace_bytes below
+ * gnnmp_next_train_workspace_bytes, or the workspace not 256-byte aligned).
+ * ---------------------------------------------------------------------------------------- */
+typedef struct {
+    int32_t n_problems, n_states, dim, width, iters;
+    const float* maps;                   /* [B, 15, 15]                                                                    */
+    const float* goals;                  /* [B, dim]                                                                       */
+    const float* states;                 /* [S, dim]                                                                       */
+    const int32_t* problem_of_state;     /* [S]  any order, repeats allowed                                                */
+    const float* weights;                /* packed, gnnmp_next_weights_floats floats                                       */
+    float* pb_rep;                       /* out [B, 64, 15, 15]                                                            */
+    float* y;                            /* out [S, dim + 1]                                                               */
+    int32_t* status;                     /* [2] accumulated, as gnnmp_next_states.status                                   */
+    void* workspace;                     /* device memory, 256-byte aligned; the backward reads it                         */
+    size_t workspace_bytes;
+} gnnmp_next_train;
+
+typedef struct {
+    int32_t n_problems, n_states, dim, width, iters;      /* as in the forward                                              */
+    const float* goals;                  /* [B, dim]                                                                       */
+    const float* states;                 /* [S, dim]                                                                       */
+    const int32_t* problem_of_state;     /* [S]                                                                            */
+    const float* weights;                /* packed                                                                         */
+    const float* weights_t;              /* the transposed packing, see above                                              */
+    const float* pb_rep;                 /* [B, 64, 15, 15]  the forward's                                                 */
+    const float* dy;                     /* [S, dim + 1]                                                                   */
+    float* dpb_rep;                      /* [B, 64, 15, 15]  out of the state call, in of the pb call                      */
+    float* dweights;                     /* out, gnnmp_next_weights_floats floats                                          */
+    void* workspace;                     /* the forward's                                                                  */
+    size_t workspace_bytes;
+} gnnmp_next_train_bwd;
+
+/* GNNMP_ERR_NULL (bytes), GNNMP_ERR_ARG (a negative count).  A multiple of 256, strictly increasing in each argument. */
+int gnnmp_next_train_workspace_bytes(int32_t n_problems, int32_t iters, int32_t n_states, size_t* bytes);
+int gnnmp_next_weights_t_floats(int32_t dim, size_t* n_floats);
+int gnnmp_next_train_forward(const gnnmp_next_train* desc, void* hip_stream);
+int gnnmp_next_state_backward(const gnnmp_next_train_bwd* desc, void* hip_stream);
+int gnnmp_next_pb_backward(const gnnmp_next_train_bwd* desc, void* hip_stream);
 
 /* ------------------------------------------------------------------------------------------
  * The NEXT planning network of the arm families (additive to ABI 9) -- the PPN of next_model/model3D.py:87-213 behind Model3D
