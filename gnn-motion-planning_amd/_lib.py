@@ -155,6 +155,22 @@ class Next3dStateForward(ctypes.Structure):
                 ('pb_rep', ctypes.c_void_p), ('weights', ctypes.c_void_p), ('y', ctypes.c_void_p), ('status', ctypes.c_void_p)]
 
 
+class Next3dTrain(ctypes.Structure):            # gnnmp_next3d_train
+    _fields_ = [('n_problems', ctypes.c_int32), ('n_states', ctypes.c_int32), ('dim', ctypes.c_int32), ('point_dim', ctypes.c_int32),
+                ('width', ctypes.c_int32), ('iters', ctypes.c_int32), ('maps', ctypes.c_void_p), ('goals', ctypes.c_void_p),
+                ('inputs', ctypes.c_void_p), ('problem_of_state', ctypes.c_void_p), ('weights', ctypes.c_void_p),
+                ('pb_rep', ctypes.c_void_p), ('y', ctypes.c_void_p), ('status', ctypes.c_void_p), ('workspace', ctypes.c_void_p),
+                ('workspace_bytes', ctypes.c_size_t)]
+
+
+class Next3dTrainBwd(ctypes.Structure):         # gnnmp_next3d_train_bwd
+    _fields_ = [('n_problems', ctypes.c_int32), ('n_states', ctypes.c_int32), ('dim', ctypes.c_int32), ('point_dim', ctypes.c_int32),
+                ('width', ctypes.c_int32), ('iters', ctypes.c_int32), ('goals', ctypes.c_void_p), ('inputs', ctypes.c_void_p),
+                ('problem_of_state', ctypes.c_void_p), ('weights', ctypes.c_void_p), ('weights_t', ctypes.c_void_p),
+                ('pb_rep', ctypes.c_void_p), ('dy', ctypes.c_void_p), ('dpb_rep', ctypes.c_void_p), ('dweights', ctypes.c_void_p),
+                ('workspace', ctypes.c_void_p), ('workspace_bytes', ctypes.c_size_t)]
+
+
 class NextPlanBatch(ctypes.Structure):
     _fields_ = RRTStarBatch._fields_ + [('g_explore_eps', ctypes.c_double), ('c', ctypes.c_double), ('k', ctypes.c_int32),
                                         ('eps_rows', ctypes.c_int32), ('scale', ctypes.c_float), ('pb_rep', ctypes.c_void_p),
@@ -318,6 +334,11 @@ def lib():
     L.gnnmp_next3d_workspace_bytes.argtypes = [ctypes.c_int32, ctypes.POINTER(sz)]
     L.gnnmp_next3d_pb_forward.argtypes = [ctypes.POINTER(Next3dPbForward), vp]
     L.gnnmp_next3d_state_forward.argtypes = [ctypes.POINTER(Next3dStateForward), vp]
+    L.gnnmp_next3d_train_workspace_bytes.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(sz)]
+    L.gnnmp_next3d_weights_t_floats.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(sz)]
+    L.gnnmp_next3d_train_forward.argtypes = [ctypes.POINTER(Next3dTrain), vp]
+    L.gnnmp_next3d_state_backward.argtypes = [ctypes.POINTER(Next3dTrainBwd), vp]
+    L.gnnmp_next3d_pb_backward.argtypes = [ctypes.POINTER(Next3dTrainBwd), vp]
     L.gnnmp_next_plan_max_nodes.argtypes = []
     L.gnnmp_next_plan.argtypes = [ctypes.POINTER(NextPlanBatch), ctypes.POINTER(NextPlanTree), vp]
     L.gnnmp_maze_steer.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, vp, vp, vp, vp, vp, vp, vp, vp]

@@ -2098,6 +2098,74 @@ extern "C" int gnnmp_next3d_state_forward(const gnnmp_next3d_states* d, void* hi
 }
 
 // =============================================================================================
+// training the 3-D NEXT network (next3d_train_kernels.hip).  The order of checks of the 2-D training entry points: the struct,
+// dims, negative counts, NULL arrays, then the no-work return BEFORE ANY HIP CALL (it writes nothing), then the workspace.
+// =============================================================================================
+extern "C" int gnnmp_next3d_train_workspace_bytes(int32_t n_problems, int32_t iters, int32_t n_states, size_t* bytes) {
+    if (!bytes) return GNNMP_ERR_NULL;
+    if (n_problems < 0 || iters < 0 || n_states < 0) return GNNMP_ERR_ARG;
+    Next3dTrainCarve c;
+    next3d_train_carve(n_problems, iters, n_states, c);
+    *bytes = c.total;
+    return GNNMP_OK;
+}
+
+extern "C" int gnnmp_next3d_weights_t_floats(int32_t dim, int32_t point_dim, size_t* n_floats) {
+    if (!n_floats) return GNNMP_ERR_NULL;
+    if (!next3d_dims_ok(dim, point_dim)) return GNNMP_ERR_DIMS;
+    *n_floats = next3d_weights_t_floats();
+    return GNNMP_OK;
+}
+
+static int next3d_train_ws(int32_t B, int32_t iters, int32_t S, const void* ws, size_t ws_bytes, Next3dTrainCarve& c) {
+    next3d_train_carve(B, iters, S, c);
+    if (ws_bytes < c.total || (reinterpret_cast<uintptr_t>(ws) & 255)) return GNNMP_ERR_WORKSPACE;
+    return GNNMP_OK;
+}
+
+extern "C" int gnnmp_next3d_train_forward(const gnnmp_next3d_train* d, void* hip_stream) {
+    if (!d) return GNNMP_ERR_NULL;
+    if (!next3d_dims_ok(d->dim, d->point_dim) || d->width != 15) return GNNMP_ERR_DIMS;
+    if (d->n_problems < 0 || d->n_states < 0 || d->iters < 0) return GNNMP_ERR_ARG;
+    if (!d->maps || !d->goals || !d->inputs || !d->problem_of_state || !d->weights || !d->pb_rep || !d->y || !d->status || !d->workspace)
+        return GNNMP_ERR_NULL;
+    if (d->n_problems == 0) return GNNMP_OK;                   // no work: no HIP call, nothing written
+    Next3dTrainCarve c;
+    if (int rc = next3d_train_ws(d->n_problems, d->iters, d->n_states, d->workspace, d->workspace_bytes, c)) return rc;
+    Next3dPbParams p;
+    p.B = d->n_problems; p.dim = d->dim; p.pd = d->point_dim; p.iters = d->iters;
+    p.maps = d->maps; p.goals = d->goals; p.weights = d->weights; p.pb_rep = d->pb_rep; p.workspace = nullptr;
+    Next3dStateParams q;
+    q.S = d->n_states; q.B = d->n_problems; q.dim = d->dim; q.pd = d->point_dim;
+    q.inputs = d->inputs; q.problem_of_state = d->problem_of_state; q.pb_rep = d->pb_rep; q.weights = d->weights; q.y = d->y;
+    q.status = d->status;
+    HIP_TRY(launch_next3d_train_forward(p, q, static_cast<char*>(d->workspace), c, static_cast<hipStream_t>(hip_stream)));
+    return GNNMP_OK;
+}
+
+static int next3d_train_bwd(const gnnmp_next3d_train_bwd* d, void* hip_stream, bool state_call) {
+    if (!d) return GNNMP_ERR_NULL;
+    if (!next3d_dims_ok(d->dim, d->point_dim) || d->width != 15) return GNNMP_ERR_DIMS;
+    if (d->n_problems < 0 || d->n_states < 0 || d->iters < 0) return GNNMP_ERR_ARG;
+    if (!d->goals || !d->inputs || !d->problem_of_state || !d->weights || !d->weights_t || !d->pb_rep || !d->dy || !d->dpb_rep ||
+        !d->dweights || !d->workspace)
+        return GNNMP_ERR_NULL;
+    if (d->n_problems == 0 || (state_call && d->n_states == 0)) return GNNMP_OK;       // no work: no HIP call, nothing written
+    Next3dTrainBwdParams p;
+    if (int rc = next3d_train_ws(d->n_problems, d->iters, d->n_states, d->workspace, d->workspace_bytes, p.c)) return rc;
+    p.B = d->n_problems; p.S = d->n_states; p.dim = d->dim; p.pd = d->point_dim; p.iters = d->iters;
+    p.goals = d->goals; p.inputs = d->inputs; p.problem_of_state = d->problem_of_state; p.weights = d->weights;
+    p.weights_t = d->weights_t; p.pb_rep = d->pb_rep; p.dy = d->dy; p.dpb_rep = d->dpb_rep; p.dweights = d->dweights;
+    p.ws = static_cast<char*>(d->workspace);
+    if (state_call) HIP_TRY(launch_next3d_state_backward(p, static_cast<hipStream_t>(hip_stream)));
+    else HIP_TRY(launch_next3d_pb_backward(p, static_cast<hipStream_t>(hip_stream)));
+    return GNNMP_OK;
+}
+
+extern "C" int gnnmp_next3d_state_backward(const gnnmp_next3d_train_bwd* d, void* hip_stream) { return next3d_train_bwd(d, hip_stream, true); }
+extern "C" int gnnmp_next3d_pb_backward(const gnnmp_next3d_train_bwd* d, void* hip_stream) { return next3d_train_bwd(d, hip_stream, false); }
+
+// =============================================================================================
 // NEXT's guided tree loop on maze problems (next_plan_kernels.hip; algorithm/tsa.py:12-81, 141-220)
 // =============================================================================================
 extern "C" int gnnmp_next_plan_max_nodes(void) { return next_plan_max_nodes(); }

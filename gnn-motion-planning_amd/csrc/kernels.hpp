@@ -406,6 +406,38 @@ hipError_t launch_next3d_state_forward(const Next3dStateParams& p, hipStream_t s
 size_t next3d_weights_floats();
 size_t next3d_workspace_bytes(int B);
 
+// ---- training the 3-D NEXT network (next3d_train_kernels.hip): the forward that keeps its activations, the backward
+// byte offsets into the caller's workspace, every one a multiple of 256 and computed in size_t
+struct Next3dTrainCarve {
+    size_t saved;                         // float [B][saved_floats]: x9 [3376][16], then [3376][64] slots: hl, H [iters + 1], C [iters + 1], X [iters]
+    size_t saved_floats;                  // floats a problem
+    size_t bwd;                           // float [B][3][3376][64]: dh, dc, dx of the round in flight
+    size_t dg;                            // float [B][3456][256]: a round's gate gradients
+    size_t part_pb;                       // double [B][conv / lstm range of the packed weights]
+    size_t part_goal;                     // double [B][attention range]
+    size_t goal_d;                        // double [B][3375][8]: the gradient of x9's attention channels
+    size_t part_state;                    // double [S][per-state range]
+    size_t st_d;                          // double [S][6824]: a123, da123, dT, da3 of a row
+    size_t attn_acc;                      // double [per-state range]: the sum over the rows
+    size_t total;
+};
+void next3d_train_carve(int B, int iters, int S, Next3dTrainCarve& c);
+struct Next3dTrainBwdParams {
+    int B, S, dim, pd, iters;
+    const float *goals, *inputs;          // [B, pd + dim], [S, pd + dim]
+    const int* problem_of_state;          // [S]
+    const float *weights, *weights_t;     // packed; the transposed packing (next3d_weights_t_floats())
+    const float *pb_rep, *dy;             // [B, 64, 15, 15, 15] of the forward, [S, dim + 1]
+    float *dpb_rep, *dweights;            // [B, 64, 15, 15, 15]; next3d_weights_floats()
+    char* ws;
+    Next3dTrainCarve c;
+};
+hipError_t launch_next3d_train_forward(const Next3dPbParams& pb, const Next3dStateParams& st, char* ws, const Next3dTrainCarve& c,
+                                       hipStream_t s);
+hipError_t launch_next3d_state_backward(const Next3dTrainBwdParams& p, hipStream_t st);
+hipError_t launch_next3d_pb_backward(const Next3dTrainBwdParams& p, hipStream_t st);
+size_t next3d_weights_t_floats();
+
 // ---- NEXT's guided tree loop on maze problems (next_plan_kernels.hip, algorithm/tsa.py:12-81, 141-220)
 struct NextPlanParams {
     RrtParams t;                          // the RRT* fields (the workspace pointers are unused: the node state lives in LDS)

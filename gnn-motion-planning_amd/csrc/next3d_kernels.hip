@@ -33,180 +33,18 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include "kernels.hpp"
+#include "next3d_pb.hpp"
 
 namespace gnnmp {
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int kW = 15, kV = kW * kW * kW, kLat = 64;
-constexpr int kRows = kV + 1, kZeroRow = kV;     // rows of a workspace buffer; the last one stays zero
-constexpr int kXC = 16;                          // channels of an x9 row (9 used)
-constexpr int kMT = 2, kWaves = 4, kThreads = 64 * kWaves, kTileV = 16 * kMT * kWaves, kTiles = (kV + kTileV - 1) / kTileV;
-constexpr int kLS = 68;                          // LDS row stride in floats: 16-byte aligned, rows 4 banks apart
-constexpr int kAtThreads = 512;                 // attention and read-out: 8 waves, seven voxels a thread
-constexpr int kIn1 = 12, kMIn = 16, kPOut = 16;    // padded widths: first attention layer's inputs (point_dim + 3 <= 9), the
-                                                 // a3 MLP's inputs (dim <= 15), the policy's outputs (dim + 1 <= 16)
-constexpr int kF64Rounds = 1;                    // LSTM rounds that accumulate in double (see next3d_round_kernel)
-
-// workspace of one problem, in floats
-constexpr size_t wsX9 = 0, wsHL = wsX9 + (size_t)kRows * kXC, wsHA = wsHL + (size_t)kRows * kLat, wsHB = wsHA + (size_t)kRows * kLat,
-                 wsC = wsHB + (size_t)kRows * kLat, kWsFloats = wsC + (size_t)kRows * kLat;
-
-// packed weights (floats), one layout for every (dim, point_dim); gnnmp.next_model3d.pack_weights writes this order
-constexpr int oW1 = 0, oB1 = oW1 + 16 * kIn1, oW2 = oB1 + 16, oB2 = oW2 + 256, oW3 = oB2 + 16, oB3 = oW3 + 512, oW4 = oB3 + 32,
-              oB4 = oW4 + 1024, oW5 = oB4 + 32, oB5 = oW5 + 2048, oW6 = oB5 + 64, oB6 = oW6 + 64, oM1 = oB6 + 4,
-              oMB1 = oM1 + 64 * kMIn, oM2 = oMB1 + 64, oMB2 = oM2 + 512, oP1 = oMB2 + 8, oPB1 = oP1 + 1024, oP2 = oPB1 + 128,
-              oPB2 = oP2 + 8192, oP3 = oPB2 + 64, oPB3 = oP3 + kPOut * 64, oHidW = oPB3 + kPOut, oHidB = oHidW + 27 * 1024,
-              oH0W = oHidB + 64, oH0B = oH0W + 108 * 1024, oC0W = oH0B + 64, oC0B = oC0W + 108 * 1024, oCvW = oC0B + 64,
-              oCvB = oCvW + 108 * 1024, oLsW = oCvB + 64, oLsB = oLsW + 8 * 16 * 256, kWeightFloats = oLsB + 256;
-static_assert(oHidW % 4 == 0 && oH0W % 4 == 0 && oC0W % 4 == 0 && oCvW % 4 == 0 && oLsW % 4 == 0, "16-byte weight loads");
-static_assert(wsHL % 4 == 0 && wsHA % 4 == 0 && wsHB % 4 == 0 && wsC % 4 == 0 && kWsFloats % 4 == 0, "16-byte row loads");
-
-__device__ __forceinline__ double relu(double v) { return v > 0. ? v : 0.; }
-__device__ __forceinline__ double wave_max(double v) {
-    for (int o = 32; o; o >>= 1) v = fmax(v, __shfl_xor(v, o));
-    return v;
-}
-__device__ __forceinline__ double wave_sum(double v) {
-    for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-// the shared MLP of the attention behind its first layer, for one voxel: `a` = the first layer's 16 outputs (after ReLU) -> the
-// logit.  In double, as in the 2-D network: the logits reach tens and the recurrent rounds amplify an error in exp().
-__device__ __forceinline__ double attn_tail(const float* __restrict__ W, const double (&a)[16]) {
-    double b[16], c[32], d[32];
-#pragma unroll
-    for (int o = 0; o < 16; ++o) {
-        double v = W[oB2 + o];
-#pragma unroll
-        for (int i = 0; i < 16; ++i) v = fma((double)W[oW2 + o * 16 + i], a[i], v);
-        b[o] = relu(v);
-    }
-#pragma unroll
-    for (int o = 0; o < 32; ++o) {
-        double v = W[oB3 + o];
-#pragma unroll
-        for (int i = 0; i < 16; ++i) v = fma((double)W[oW3 + o * 16 + i], b[i], v);
-        c[o] = relu(v);
-    }
-#pragma unroll
-    for (int o = 0; o < 32; ++o) {
-        double v = W[oB4 + o];
-#pragma unroll
-        for (int i = 0; i < 32; ++i) v = fma((double)W[oW4 + o * 32 + i], c[i], v);
-        d[o] = relu(v);
-    }
-    double logit = W[oB6];
-#pragma unroll 2
-    for (int o = 0; o < 64; ++o) {             // layer 5 output o goes straight into the last layer's dot product
-        double v = W[oB5 + o];
-#pragma unroll
-        for (int i = 0; i < 32; ++i) v = fma((double)W[oW5 + o * 32 + i], d[i], v);
-        logit = fma((double)W[oW6 + o], relu(v), logit);
-    }
-    return logit;
-}
-
-// LDS scratch of one attention, in doubles
-struct AttnScratch {
-    double base[16];                           // first layer: bias + the point's part, the same for every voxel
-    double red[kAtThreads / 64], sum[kAtThreads / 64];
-    double z[64], o[8], a3[8];
-};
-
-// The attention of one input row [point (pd), state (dim)] for a workgroup of kAtThreads threads, in double: a123 of every voxel
-// in a123[] (LDS; thread tid owns voxels tid + q kAtThreads and may read those back without a barrier), a3[8] in s.a3.  Voxel
-// v = (i 15 + j) 15 + k enters as [point, j, i, k].  The voxel loop stays rolled and keeps its logits in LDS, not in registers.
-__device__ __forceinline__ void attention3d(const float* __restrict__ W, const float* inp, int dim, int pd, int tid, AttnScratch& s,
-                                            double* a123) {
-    constexpr int NWV = kAtThreads / 64;
-    if (tid < 16) {
-        double v = W[oB1 + tid];
-        for (int q = 0; q < pd; ++q) v = fma((double)W[oW1 + tid * kIn1 + q], (double)inp[q], v);
-        s.base[tid] = v;
-    }
-    if (tid >= 64 && tid < 128) {
-        const int o = tid - 64;
-        double v = W[oMB1 + o];
-        for (int q = 0; q < dim; ++q) v = fma((double)W[oM1 + o * kMIn + q], (double)inp[pd + q], v);
-        s.z[o] = relu(v);
-    }
-    __syncthreads();
-    if (tid < 8) {
-        double v = W[oMB2 + tid];
-        for (int i = 0; i < 64; ++i) v = fma((double)W[oM2 + tid * 64 + i], s.z[i], v);
-        s.o[tid] = v;
-    }
-    double mx = -INFINITY;
-#pragma unroll 1
-    for (int v = tid; v < kV; v += kAtThreads) {
-        const int i = v / (kW * kW), j = (v / kW) % kW, k = v % kW;
-        // the weights are re-read (scalar loads, cached) for every voxel: were the pointer visibly loop-invariant, the compiler
-        // would hoist all 4 k converted weights out of the loop and spill them
-        const float* Wv = W;
-        asm volatile("" : "+s"(Wv));
-        double l1[16];
-#pragma unroll
-        for (int o = 0; o < 16; ++o)
-            l1[o] = relu(fma((double)Wv[oW1 + o * kIn1 + pd + 2], (double)k, fma((double)Wv[oW1 + o * kIn1 + pd + 1], (double)i,
-                         fma((double)Wv[oW1 + o * kIn1 + pd], (double)j, s.base[o]))));
-        const double logit = attn_tail(Wv, l1);
-        a123[v] = logit;
-        mx = fmax(mx, logit);
-    }
-    mx = wave_max(mx);
-    if ((tid & 63) == 0) s.red[tid >> 6] = mx;
-    __syncthreads();
-    mx = s.red[0];
-#pragma unroll
-    for (int w = 1; w < NWV; ++w) mx = fmax(mx, s.red[w]);
-    double e = 0.;
-    for (int v = tid; v < kV; v += kAtThreads) {
-        const double ev = exp(a123[v] - mx);
-        a123[v] = ev;
-        e += ev;
-    }
-    e = wave_sum(e);
-    if ((tid & 63) == 0) s.sum[tid >> 6] = e;
-    if (tid < 8) {
-        double m8 = s.o[0];
-        for (int i = 1; i < 8; ++i) m8 = fmax(m8, s.o[i]);
-        double den = 0.;
-        for (int i = 0; i < 8; ++i) den += exp(s.o[i] - m8);
-        s.a3[tid] = exp(s.o[tid] - m8) / den;
-    }
-    __syncthreads();
-    double tot = 0.;
-#pragma unroll
-    for (int w = 0; w < NWV; ++w) tot += s.sum[w];
-    for (int v = tid; v < kV; v += kAtThreads) a123[v] = a123[v] / tot;
-}
 
 __global__ __launch_bounds__(kAtThreads) void next3d_attn_kernel(Next3dPbParams p) {
     __shared__ AttnScratch sc;
     __shared__ double a123[kV + 1];
     const int b = blockIdx.x, tid = threadIdx.x;
     float* ws = p.workspace + (size_t)b * kWsFloats;
-    attention3d(p.weights, p.goals + (size_t)b * (p.pd + p.dim), p.dim, p.pd, tid, sc, a123);
-    for (int v = tid; v < kV; v += kAtThreads) {
-        const double a = a123[v];
-        float* row = ws + wsX9 + (size_t)v * kXC;
-        f32x4 r0, r1, r2 = f32x4{0.f, 0.f, 0.f, 0.f};
-        r0[0] = p.maps[(size_t)b * kV + v];
-        r0[1] = (float)(sc.a3[0] * a); r0[2] = (float)(sc.a3[1] * a); r0[3] = (float)(sc.a3[2] * a);
-        r1[0] = (float)(sc.a3[3] * a); r1[1] = (float)(sc.a3[4] * a); r1[2] = (float)(sc.a3[5] * a);
-        r1[3] = (float)(sc.a3[6] * a);
-        r2[0] = (float)(sc.a3[7] * a);
-        reinterpret_cast<f32x4*>(row)[0] = r0;
-        reinterpret_cast<f32x4*>(row)[1] = r1;
-        reinterpret_cast<f32x4*>(row)[2] = r2;
-        reinterpret_cast<f32x4*>(row)[3] = f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-    // the zero rows: what a voxel outside the map reads
-    if (tid < kXC) ws[wsX9 + (size_t)kZeroRow * kXC + tid] = 0.f;
-    if (tid < kLat) {
+    next3d_x9_body(p, b, ws + wsX9, sc, a123, tid);
+    if (tid < kLat) {                                           // the zero rows of the other buffers
         ws[wsHL + (size_t)kZeroRow * kLat + tid] = 0.f;
         ws[wsHA + (size_t)kZeroRow * kLat + tid] = 0.f;
         ws[wsHB + (size_t)kZeroRow * kLat + tid] = 0.f;
@@ -214,127 +52,17 @@ __global__ __launch_bounds__(kAtThreads) void next3d_attn_kernel(Next3dPbParams 
     }
 }
 
-// this lane's voxel in row tile m of the wave as (i << 8 | j << 4 | k), -1 behind the last voxel
-__device__ __forceinline__ int lane_cell(int tile, int wave, int m, int lane) {
-    const int v = tile * kTileV + (wave * kMT + m) * 16 + (lane & 15);
-    return v < kV ? ((v / (kW * kW)) << 8 | ((v / kW) % kW) << 4 | (v % kW)) : -1;
-}
-
-// row of the voxel that tap (di, dj, dk) = (tap / 9, tap / 3 % 3, tap % 3) of a cell reads: the neighbour, or the zero row
-__device__ __forceinline__ int nbr_row(int cell, int tap) {
-    const int di = tap / 9, dj = (tap / 3) % 3, dk = tap % 3;
-    const int i = (cell >> 8) + di - 1, j = ((cell >> 4) & 15) + dj - 1, k = (cell & 15) + dk - 1;
-    const bool in = cell >= 0 && i >= 0 && i < kW && j >= 0 && j < kW && k >= 0 && k < kW;
-    return in ? (i * kW + j) * kW + k : kZeroRow;
-}
-
-typedef double f64x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-__device__ __forceinline__ f64x4 mfma4(float a, float b, f64x4 c) {
-    return __builtin_amdgcn_mfma_f64_16x16x4f64((double)a, (double)b, c, 0, 0, 0);
-}
-template <typename ACC> struct elem_of;
-template <> struct elem_of<f32x4> { typedef float type; };
-template <> struct elem_of<f64x4> { typedef double type; };
-// row of a 16 x 16 result tile that register r of lane l holds (the column is l & 15): the two instructions differ
-template <typename ACC> __device__ __forceinline__ int acc_row(int lane, int r);
-template <> __device__ __forceinline__ int acc_row<f32x4>(int lane, int r) { return 4 * (lane >> 4) + r; }
-template <> __device__ __forceinline__ int acc_row<f64x4>(int lane, int r) { return 4 * r + (lane >> 4); }
-
-// ---- 3 x 3 x 3 convolution of the wave's two row tiles: acc[m][nt] = bias + sum over 27 taps x CG channel groups of 16; src rows
-// of STRIDE floats in global memory.  ACC = f32x4: exact fp32 MFMA, as a two-level sum -- the three taps of one (di, dj) go into
-// a fresh accumulator which then joins the total: nine chains of 192 and a sum of nine.  ACC = f64x4: the same operands through
-// v_mfma_f64_16x16x4_f64 (same lane layout, half the rate), one chain: for the stretches whose sums are large (|h0| reaches 258:
-// one fp32 chain over K = 1728 was 3.6e-4 off there, the two-level sum 4e-5, the reference's own fp32 run 9e-5).
-template <int CG, int STRIDE, typename ACC>
-__device__ __forceinline__ void conv27(const float* __restrict__ src, const float* __restrict__ wk, const float* __restrict__ bias,
-                                       const int (&cell)[kMT], int lane, ACC (&acc)[kMT][4]) {
-    typedef typename elem_of<ACC>::type T;
-    constexpr bool two_level = sizeof(T) == 4;
-#pragma unroll
-    for (int nt = 0; nt < 4; ++nt) {
-        const T bv = bias[nt * 16 + (lane & 15)];
-#pragma unroll
-        for (int m = 0; m < kMT; ++m) acc[m][nt] = ACC{bv, bv, bv, bv};
-    }
-    const f32x4* wv = reinterpret_cast<const f32x4*>(wk) + lane;
-    const int koff = 4 * (lane >> 4);
-#pragma unroll 1
-    for (int grp = 0; grp < 9; ++grp) {
-        ACC part[kMT][4];
-#pragma unroll
-        for (int m = 0; m < kMT; ++m)
-#pragma unroll
-            for (int nt = 0; nt < 4; ++nt) part[m][nt] = two_level ? ACC{0, 0, 0, 0} : acc[m][nt];
-#pragma unroll 1
-        for (int dk = 0; dk < 3; ++dk) {         // rolled: one tap's operands in flight
-            const int tap = grp * 3 + dk;
-            const float* row[kMT];
-#pragma unroll
-            for (int m = 0; m < kMT; ++m) row[m] = src + (size_t)nbr_row(cell[m], tap) * STRIDE + koff;
-#pragma unroll
-            for (int cg = 0; cg < CG; ++cg) {
-                f32x4 a[kMT], bw[4];
-#pragma unroll
-                for (int m = 0; m < kMT; ++m) a[m] = *reinterpret_cast<const f32x4*>(row[m] + cg * 16);
-#pragma unroll
-                for (int nt = 0; nt < 4; ++nt) bw[nt] = wv[((tap * CG + cg) * 4 + nt) * 64];
-#pragma unroll
-                for (int s = 0; s < 4; ++s)
-#pragma unroll
-                    for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-                        for (int m = 0; m < kMT; ++m) part[m][nt] = mfma4(a[m][s], bw[nt][s], part[m][nt]);
-            }
-        }
-#pragma unroll
-        for (int m = 0; m < kMT; ++m)
-#pragma unroll
-            for (int nt = 0; nt < 4; ++nt) acc[m][nt] = two_level ? acc[m][nt] + part[m][nt] : part[m][nt];
-    }
-}
-
-// accumulator tiles -> channel-last rows in global memory: lane l, register r of column tile nt is (row acc_row(l, r), column
-// 16 nt + (l & 15)); rows behind the last voxel are not written
-template <typename ACC>
-__device__ __forceinline__ void store_rows(float* dst, const ACC (&acc)[kMT][4], int tile, int wave, int lane) {
-#pragma unroll
-    for (int m = 0; m < kMT; ++m)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int v = tile * kTileV + (wave * kMT + m) * 16 + acc_row<ACC>(lane, r);
-            if (v < kV) {
-#pragma unroll
-                for (int nt = 0; nt < 4; ++nt) dst[(size_t)v * kLat + nt * 16 + (lane & 15)] = (float)acc[m][nt][r];
-            }
-        }
-}
-
 __global__ __launch_bounds__(kThreads) void next3d_hidden_kernel(Next3dPbParams p) {
     const int b = blockIdx.x / kTiles, tile = blockIdx.x % kTiles, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     float* ws = p.workspace + (size_t)b * kWsFloats;
-    int cell[kMT];
-#pragma unroll
-    for (int m = 0; m < kMT; ++m) cell[m] = lane_cell(tile, wave, m, lane);
-    f64x4 acc[kMT][4];
-    conv27<1, kXC>(ws + wsX9, p.weights + oHidW, p.weights + oHidB, cell, lane, acc);
-    store_rows(ws + wsHL, acc, tile, wave, lane);
+    next3d_hidden_body(p.weights, ws + wsX9, ws + wsHL, tile, lane, wave);
 }
 
 __global__ __launch_bounds__(kThreads) void next3d_h0c0_kernel(Next3dPbParams p) {
     const int b = blockIdx.x / kTiles, tile = blockIdx.x % kTiles, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     float* ws = p.workspace + (size_t)b * kWsFloats;
-    int cell[kMT];
-#pragma unroll
-    for (int m = 0; m < kMT; ++m) cell[m] = lane_cell(tile, wave, m, lane);
-    f64x4 acc[kMT][4];
-    conv27<4, kLat>(ws + wsHL, p.weights + oC0W, p.weights + oC0B, cell, lane, acc);
-    store_rows(ws + wsC, acc, tile, wave, lane);
-    conv27<4, kLat>(ws + wsHL, p.weights + oH0W, p.weights + oH0B, cell, lane, acc);
-    store_rows(ws + wsHA, acc, tile, wave, lane);
+    next3d_h0c0_body(p.weights, ws + wsHL, ws + wsHA, ws + wsC, tile, lane, wave);
 }
-
-__device__ __forceinline__ float sigmoidf(float v) { return 1.f / (1.f + expf(-v)); }
 
 // one round: h_in -> h_out (two different buffers), c in place.  ACC = f64x4 for the first kF64Rounds rounds, whose h is still
 // h0-sized (all-fp32 missed the bar at 1 and 2 rounds: profiles/next3d_parity.txt); behind them |h| <= 1 and exact fp32 MFMA holds
@@ -430,15 +158,9 @@ __global__ __launch_bounds__(256) void next3d_out_kernel(Next3dPbParams p) {
     if (i < kLat * kV) p.pb_rep[(size_t)b * (kLat * kV) + i] = h[(size_t)(i % kV) * kLat + i / kV];
 }
 
-struct StateScratch {
-    AttnScratch at;
-    double a123[kV + 1];
-    double T[kLat], x[8], h1[128], h2[64];
-};
-
 __global__ __launch_bounds__(kAtThreads) void next3d_state_kernel(Next3dStateParams p) {
     __shared__ StateScratch s;
-    const int st = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int st = blockIdx.x, tid = threadIdx.x;
     const int nout = p.dim + 1;
     const int pr = p.problem_of_state[st];
     if (pr < 0 || pr >= p.B) {                                  // uniform over the workgroup: reported, not read, not clamped
@@ -450,38 +172,7 @@ __global__ __launch_bounds__(kAtThreads) void next3d_state_kernel(Next3dStatePar
         return;
     }
     const float* __restrict__ W = p.weights;
-    const float* __restrict__ pb = p.pb_rep + (size_t)pr * (kLat * kV);
-    attention3d(W, p.inputs + (size_t)st * (p.pd + p.dim), p.dim, p.pd, tid, s.at, s.a123);
-    __syncthreads();
-    for (int c = wave; c < kLat; c += kAtThreads / 64) {        // T[c]: a wave per channel, voxels over the lanes
-        double t = 0.;
-        for (int q = lane; q < kV; q += 64) t = fma(s.a123[q], (double)pb[(size_t)c * kV + q], t);
-        t = wave_sum(t);
-        if (lane == 0) s.T[c] = t;
-    }
-    __syncthreads();
-    if (tid < 8) {
-        double x = 0.;
-        for (int cap = 0; cap < 8; ++cap) x = fma(s.at.a3[cap], s.T[tid * 8 + cap], x);
-        s.x[tid] = x;
-    }
-    __syncthreads();
-    if (tid < 128) {
-        double v = (double)W[oPB1 + tid];
-        for (int i = 0; i < 8; ++i) v = fma((double)W[oP1 + tid * 8 + i], s.x[i], v);
-        s.h1[tid] = v > 0. ? v : 0.;
-    }
-    __syncthreads();
-    if (tid < 256) {
-        const int j = tid >> 2, part = tid & 3;                 // 64 outputs, four threads each
-        double v = 0.;
-        for (int i = part; i < 128; i += 4) v = fma((double)W[oP2 + j * 128 + i], s.h1[i], v);
-        v += __shfl_xor(v, 1);
-        v += __shfl_xor(v, 2);
-        v += (double)W[oPB2 + j];
-        if (part == 0) s.h2[j] = v > 0. ? v : 0.;
-    }
-    __syncthreads();
+    next3d_state_readout(W, p.inputs + (size_t)st * (p.pd + p.dim), p.dim, p.pd, p.pb_rep + (size_t)pr * (kLat * kV), s, tid);
     if (tid < nout) {
         double v = (double)W[oPB3 + tid];
         for (int i = 0; i < 64; ++i) v = fma((double)W[oP3 + tid * 64 + i], s.h2[i], v);

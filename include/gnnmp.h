@@ -24,6 +24,9 @@
  *       NEXT_plan with a model, batched, one launch            algorithm/tsa.py:12-81, 141-220 (call eval_next.py:65)
  *   gnnmp_next3d_weights_floats / gnnmp_next3d_workspace_bytes / gnnmp_next3d_pb_forward / gnnmp_next3d_state_forward
  *       PPN.pb_forward / PPN.state_forward of the arm families, batched   next_model/model3D.py:154-213 (calls model3D.py:251, 265)
+ *   gnnmp_next3d_train_workspace_bytes / gnnmp_next3d_weights_t_floats / gnnmp_next3d_train_forward /
+ *   gnnmp_next3d_state_backward / gnnmp_next3d_pb_backward
+ *       one training step of the arm families' PPN            train_next.py:41-69 (next_model/model3D.py:87-213)
  *   gnnmp_graph_workspace_bytes / gnnmp_graph_build
  *       create_data's edge construction                       eval_gnn.py:159-164
  *   gnnmp_maze_sample
@@ -1063,6 +1066,74 @@ int gnnmp_next3d_workspace_bytes(int32_t n_problems, size_t* bytes);
  * not 16-byte aligned), GNNMP_ERR_NULL (an array, the workspace included). */
 int gnnmp_next3d_pb_forward(const gnnmp_next3d_pb* desc, void* hip_stream);
 int gnnmp_next3d_state_forward(const gnnmp_next3d_states* desc, void* hip_stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Training the 3-D NEXT network of the arm families (additive to ABI 9; next3d_train_kernels.hip) -- the forward that keeps its
+ * activations and the backward, for 1 <= dim <= 15, point_dim 3 / 6, width 15.  The 2-D training calls above, for Model3D:
+ *   gnnmp_next3d_train_forward   what gnnmp_next3d_pb_forward followed by gnnmp_next3d_state_forward computes, with the same bits
+ *                                in pb_rep and y, and into the workspace x9, the hidden layer, h and c of every round (round r
+ *                                reads slot r and writes slot r + 1) and every round's conv output, as [3376][64] rows whose last
+ *                                row stays zero (about 0.86 MB a slot, 55 MB a problem at 20 rounds).
+ *   gnnmp_next3d_state_backward  dy [S, dim + 1] -> dpb_rep [B, 64, 15, 15, 15] and dweights[0, per-state range): the shared
+ *                                attention MLP, mlp.0, mlp.2 and the policy MLP, summed over the rows in ascending row index in
+ *                                double.
+ *   gnnmp_next3d_pb_backward     dpb_rep -> dweights of hidden, h0, c0, conv and lstm, summed over the problems in ascending
+ *                                problem index in double.  As gnnmp_next_pb_backward it REWRITES the attention range of dweights
+ *                                as float(the state call's double sum, kept in the workspace, + the goals' sum in ascending
+ *                                problem index): it runs after gnnmp_next3d_state_backward on the same struct and workspace; with
+ *                                n_states == 0 the state sum counts as zero and the policy range is written as zero.
+ * dweights is float32, gnnmp_next3d_weights_floats long, in the packed layout; padding lanes receive zero.  When there is work
+ * dweights and dpb_rep are overwritten, never accumulated into.  No floating-point atomics: two runs are bit-identical.  A
+ * problem_of_state outside [0, B) is counted in the forward's status words, its row of y is NaN, and nothing is read or written
+ * for it in the forward or the backward.
+ *
+ * weights_t (gnnmp_next3d_weights_t_floats floats; gnnmp.next_train3d.pack_weights_t writes them): conv, h0 and c0 with the taps
+ * flipped on all three axes and the channel matrix transposed, in the convolution packing above, the LSTM's
+ * [256 gate rows][x 64 | h 64] in the MFMA packing, and 64 zeros.
+ *
+ * Checks, in this order, each before any HIP call: GNNMP_ERR_NULL (the struct), GNNMP_ERR_DIMS (dim, point_dim, width not 15),
+ * GNNMP_ERR_ARG (a negative count), GNNMP_ERR_NULL (an array), then GNNMP_OK WITHOUT ANY HIP CALL AND WITHOUT WRITING ANYTHING
+ * when there is no work -- n_problems == 0, and for gnnmp_next3d_state_backward n_states == 0 as well
+ * (gnnmp_next3d_train_forward with n_states == 0 computes pb_rep only) -- then GNNMP_ERR_WORKSPACE (workspace_bytes below
+ * gnnmp_next3d_train_workspace_bytes, or the workspace not 256-byte aligned).
+ * ---------------------------------------------------------------------------------------- */
+typedef struct {
+    int32_t n_problems, n_states, dim, point_dim, width, iters;
+    const float* maps;                   /* [B, 15, 15, 15]                                                                */
+    const float* goals;                  /* [B, point_dim + dim]                                                           */
+    const float* inputs;                 /* [S, point_dim + dim]                                                           */
+    const int32_t* problem_of_state;     /* [S]  any order, repeats allowed                                                */
+    const float* weights;                /* packed, gnnmp_next3d_weights_floats floats                                     */
+    float* pb_rep;                       /* out [B, 64, 15, 15, 15]                                                        */
+    float* y;                            /* out [S, dim + 1]                                                               */
+    int32_t* status;                     /* [2] accumulated, as gnnmp_next3d_states.status                                 */
+    void* workspace;                     /* device memory, 256-byte aligned; the backward reads it                         */
+    size_t workspace_bytes;
+} gnnmp_next3d_train;
+
+typedef struct {
+    int32_t n_problems, n_states, dim, point_dim, width, iters;   /* as in the forward                                     */
+    const float* goals;                  /* [B, point_dim + dim]                                                           */
+    const float* inputs;                 /* [S, point_dim + dim]                                                           */
+    const int32_t* problem_of_state;     /* [S]                                                                            */
+    const float* weights;                /* packed                                                                         */
+    const float* weights_t;              /* the transposed packing, see above                                              */
+    const float* pb_rep;                 /* [B, 64, 15, 15, 15]  the forward's                                             */
+    const float* dy;                     /* [S, dim + 1]                                                                   */
+    float* dpb_rep;                      /* [B, 64, 15, 15, 15]  out of the state call, in of the pb call                  */
+    float* dweights;                     /* out, gnnmp_next3d_weights_floats floats                                        */
+    void* workspace;                     /* the forward's                                                                  */
+    size_t workspace_bytes;
+} gnnmp_next3d_train_bwd;
+
+/* GNNMP_ERR_NULL (bytes), GNNMP_ERR_ARG (a negative count).  A multiple of 256, strictly increasing in each argument, computed
+ * in size_t. */
+int gnnmp_next3d_train_workspace_bytes(int32_t n_problems, int32_t iters, int32_t n_states, size_t* bytes);
+/* GNNMP_ERR_NULL (n_floats), GNNMP_ERR_DIMS (dim outside 1 .. 15, point_dim not 3 / 6). */
+int gnnmp_next3d_weights_t_floats(int32_t dim, int32_t point_dim, size_t* n_floats);
+int gnnmp_next3d_train_forward(const gnnmp_next3d_train* desc, void* hip_stream);
+int gnnmp_next3d_state_backward(const gnnmp_next3d_train_bwd* desc, void* hip_stream);
+int gnnmp_next3d_pb_backward(const gnnmp_next3d_train_bwd* desc, void* hip_stream);
 
 /* ------------------------------------------------------------------------------------------
  * NEXT's guided planner on maze problems (ABI 9) -- eval_next.py's NEXT_plan(env, model, T=t_max, g_explore_eps=0.1,
