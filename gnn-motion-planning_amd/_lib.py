@@ -143,6 +143,29 @@ class NextTrainBwd(ctypes.Structure):           # gnnmp_next_train_bwd
                 ('workspace', ctypes.c_void_p), ('workspace_bytes', ctypes.c_size_t)]
 
 
+class NextReplay(ctypes.Structure):             # gnnmp_next_replay
+    _fields_ = [('dim', ctypes.c_int32), ('cap_paths', ctypes.c_int32), ('cap_states', ctypes.c_int32),
+                ('states64', ctypes.c_void_p), ('states32', ctypes.c_void_p), ('actions', ctypes.c_void_p),
+                ('values', ctypes.c_void_p), ('path_ptr', ctypes.c_void_p), ('problem', ctypes.c_void_p),
+                ('counts', ctypes.c_void_p), ('status', ctypes.c_void_p), ('pending', ctypes.c_void_p)]
+
+
+class NextReplayTrees(ctypes.Structure):        # gnnmp_next_replay_trees
+    _fields_ = [('n_problems', ctypes.c_int32), ('t_max', ctypes.c_int32), ('states', ctypes.c_void_p), ('path', ctypes.c_void_p),
+                ('path_len', ctypes.c_void_p), ('success', ctypes.c_void_p), ('problem_ids', ctypes.c_void_p)]
+
+
+class NextReplayPaths(ctypes.Structure):        # gnnmp_next_replay_paths
+    _fields_ = [('n_paths', ctypes.c_int32), ('n_states', ctypes.c_int32), ('paths64', ctypes.c_void_p),
+                ('path_ptr', ctypes.c_void_p), ('problem_ids', ctypes.c_void_p)]
+
+
+class NextPathLoss(ctypes.Structure):           # gnnmp_next_path_loss_desc
+    _fields_ = [('n_paths', ctypes.c_int32), ('n_states', ctypes.c_int32), ('dim', ctypes.c_int32), ('divisor', ctypes.c_int32),
+                ('y', ctypes.c_void_p), ('actions', ctypes.c_void_p), ('values', ctypes.c_void_p), ('ptr', ctypes.c_void_p),
+                ('terms', ctypes.c_void_p), ('loss', ctypes.c_void_p), ('dy', ctypes.c_void_p)]
+
+
 class Next3dPbForward(ctypes.Structure):
     _fields_ = [('n_problems', ctypes.c_int32), ('dim', ctypes.c_int32), ('point_dim', ctypes.c_int32), ('width', ctypes.c_int32),
                 ('iters', ctypes.c_int32), ('maps', ctypes.c_void_p), ('goals', ctypes.c_void_p), ('weights', ctypes.c_void_p),
@@ -330,6 +353,9 @@ def lib():
     L.gnnmp_next_train_forward.argtypes = [ctypes.POINTER(NextTrain), vp]
     L.gnnmp_next_state_backward.argtypes = [ctypes.POINTER(NextTrainBwd), vp]
     L.gnnmp_next_pb_backward.argtypes = [ctypes.POINTER(NextTrainBwd), vp]
+    L.gnnmp_next_replay_append_trees.argtypes = [ctypes.POINTER(NextReplay), ctypes.POINTER(NextReplayTrees), vp]
+    L.gnnmp_next_replay_append_paths.argtypes = [ctypes.POINTER(NextReplay), ctypes.POINTER(NextReplayPaths), vp]
+    L.gnnmp_next_path_loss.argtypes = [ctypes.POINTER(NextPathLoss), vp]
     L.gnnmp_next3d_weights_floats.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(sz)]
     L.gnnmp_next3d_workspace_bytes.argtypes = [ctypes.c_int32, ctypes.POINTER(sz)]
     L.gnnmp_next3d_pb_forward.argtypes = [ctypes.POINTER(Next3dPbForward), vp]

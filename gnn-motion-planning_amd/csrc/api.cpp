@@ -2050,6 +2050,63 @@ extern "C" int gnnmp_next_state_backward(const gnnmp_next_train_bwd* d, void* hi
 extern "C" int gnnmp_next_pb_backward(const gnnmp_next_train_bwd* d, void* hip_stream) { return next_train_bwd(d, hip_stream, false); }
 
 // =============================================================================================
+// the replay of NEXT's training loop (next_replay_kernels.hip).  The order of checks of the training entry points: the structs,
+// dims, negative counts, NULL arrays, then the no-work return BEFORE ANY HIP CALL (it writes nothing).  There is no workspace.
+// =============================================================================================
+static int next_replay_store(const gnnmp_next_replay* s, NextReplayStore& st) {
+    st.dim = s->dim; st.cap_paths = s->cap_paths; st.cap_states = s->cap_states;
+    st.states64 = s->states64; st.states32 = s->states32; st.actions = s->actions; st.values = s->values;
+    st.path_ptr = s->path_ptr; st.problem = s->problem; st.counts = s->counts; st.status = s->status; st.pending = s->pending;
+    return !s->states64 || !s->states32 || !s->actions || !s->values || !s->path_ptr || !s->problem || !s->counts || !s->status ||
+                   !s->pending
+               ? GNNMP_ERR_NULL
+               : GNNMP_OK;
+}
+
+extern "C" int gnnmp_next_replay_append_trees(const gnnmp_next_replay* s, const gnnmp_next_replay_trees* t, void* hip_stream) {
+    if (!s || !t) return GNNMP_ERR_NULL;
+    if (s->dim != 2 && s->dim != 3) return GNNMP_ERR_DIMS;
+    if (s->cap_paths < 0 || s->cap_states < 0 || t->n_problems < 0 || t->t_max < 0 || t->t_max == INT32_MAX) return GNNMP_ERR_ARG;
+    NextReplayStore st;
+    if (int rc = next_replay_store(s, st)) return rc;
+    if (!t->states || !t->path || !t->path_len || !t->success || !t->problem_ids) return GNNMP_ERR_NULL;
+    if (t->n_problems == 0) return GNNMP_OK;                   // no work: no HIP call, nothing written
+    NextReplaySrc src;
+    src.n = t->n_problems; src.t1 = t->t_max + 1; src.n_rows = 0; src.rows = t->states; src.path = t->path;
+    src.path_len = t->path_len; src.success = t->success; src.ptr = nullptr; src.problem_ids = t->problem_ids;
+    HIP_TRY(launch_next_replay_append(st, src, true, static_cast<hipStream_t>(hip_stream)));
+    return GNNMP_OK;
+}
+
+extern "C" int gnnmp_next_replay_append_paths(const gnnmp_next_replay* s, const gnnmp_next_replay_paths* q, void* hip_stream) {
+    if (!s || !q) return GNNMP_ERR_NULL;
+    if (s->dim != 2 && s->dim != 3) return GNNMP_ERR_DIMS;
+    if (s->cap_paths < 0 || s->cap_states < 0 || q->n_paths < 0 || q->n_states < 0) return GNNMP_ERR_ARG;
+    NextReplayStore st;
+    if (int rc = next_replay_store(s, st)) return rc;
+    if (!q->paths64 || !q->path_ptr || !q->problem_ids) return GNNMP_ERR_NULL;
+    if (q->n_paths == 0) return GNNMP_OK;                      // no work: no HIP call, nothing written
+    NextReplaySrc src;
+    src.n = q->n_paths; src.t1 = 0; src.n_rows = q->n_states; src.rows = q->paths64; src.path = nullptr; src.path_len = nullptr;
+    src.success = nullptr; src.ptr = q->path_ptr; src.problem_ids = q->problem_ids;
+    HIP_TRY(launch_next_replay_append(st, src, false, static_cast<hipStream_t>(hip_stream)));
+    return GNNMP_OK;
+}
+
+extern "C" int gnnmp_next_path_loss(const gnnmp_next_path_loss_desc* d, void* hip_stream) {
+    if (!d) return GNNMP_ERR_NULL;
+    if (d->dim != 2 && d->dim != 3) return GNNMP_ERR_DIMS;
+    if (d->n_paths < 0 || d->n_states < 0 || d->divisor < 1) return GNNMP_ERR_ARG;
+    if (!d->y || !d->actions || !d->values || !d->ptr || (d->loss && !d->terms)) return GNNMP_ERR_NULL;
+    if (d->n_paths == 0 || (!d->terms && !d->dy)) return GNNMP_OK;          // no work: no HIP call, nothing written
+    NextPathLossParams p;
+    p.G = d->n_paths; p.S = d->n_states; p.dim = d->dim; p.divisor = d->divisor;
+    p.y = d->y; p.actions = d->actions; p.values = d->values; p.ptr = d->ptr; p.terms = d->terms; p.loss = d->loss; p.dy = d->dy;
+    HIP_TRY(launch_next_path_loss(p, static_cast<hipStream_t>(hip_stream)));
+    return GNNMP_OK;
+}
+
+// =============================================================================================
 // the NEXT planning network of the arm families (next3d_kernels.hip; next_model/model3D.py:87-213)
 // =============================================================================================
 static bool next3d_dims_ok(int32_t dim, int32_t point_dim) { return dim >= 1 && dim <= 15 && (point_dim == 3 || point_dim == 6); }

@@ -384,6 +384,33 @@ hipError_t launch_next_state_backward(const NextTrainBwdParams& p, hipStream_t s
 hipError_t launch_next_pb_backward(const NextTrainBwdParams& p, hipStream_t st);
 size_t next_weights_t_floats();
 
+// ---- the replay of NEXT's training loop (next_replay_kernels.hip, train_next.py:25-68, 88-108)
+struct NextReplayStore {
+    int dim, cap_paths, cap_states;
+    double* states64;                     // [cap_states, dim]
+    float *states32, *actions, *values;   // [cap_states, dim] x 2, [cap_states]
+    int *path_ptr, *problem;              // [cap_paths + 1], [cap_paths]
+    int *counts, *status, *pending;       // [2] paths and states in use; [1] bits 1 / 2 / 4; [4] the append call in flight
+};
+struct NextReplaySrc {
+    int n;                                // source paths: problems of a tree batch, or packed paths
+    int t1;                               // trees: t_max + 1 rows a problem
+    long long n_rows;                     // packed: rows of paths64
+    const double* rows;                   // trees: states [n, t1, dim]; packed: paths64 [n_rows, dim]
+    const int *path, *path_len, *success; // trees: [n, t1], [n], [n]
+    const int* ptr;                       // packed: [n + 1]
+    const int* problem_ids;               // [n]
+};
+struct NextPathLossParams {
+    int G, S, dim, divisor;
+    const float *y, *actions, *values;    // [S, dim + 1], [S, dim], [S]
+    const int* ptr;                       // [G + 1]
+    double *terms, *loss;                 // [G, 2], [1]
+    float* dy;                            // [S, dim + 1]
+};
+hipError_t launch_next_replay_append(const NextReplayStore& st, const NextReplaySrc& s, bool trees, hipStream_t stream);
+hipError_t launch_next_path_loss(const NextPathLossParams& p, hipStream_t stream);
+
 // ---- the NEXT planning network of the arm families (next3d_kernels.hip, next_model/model3D.py:87-213)
 struct Next3dPbParams {
     int B, dim, pd, iters;                // problems, state size 1 .. 15, point size 3 / 6, LSTM rounds

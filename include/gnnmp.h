@@ -20,6 +20,8 @@
  *       PPN.pb_forward / PPN.state_forward, batched           next_model/model2D.py:151-210 (calls model2D.py:244, 254)
  *   gnnmp_next_train_workspace_bytes / gnnmp_next_train_forward / gnnmp_next_state_backward / gnnmp_next_pb_backward
  *       one training step of PPN: forward with saved activations, backward    train_next.py:41-69 (next_model/model2D.py:84-210)
+ *   gnnmp_next_replay_append_trees / gnnmp_next_replay_append_paths / gnnmp_next_path_loss
+ *       train_env's replay with get_label's labels, and train()'s loss        train_next.py:25-68, 88-108
  *   gnnmp_next_plan / gnnmp_next_plan_max_nodes                                       (ABI 9)
  *       NEXT_plan with a model, batched, one launch            algorithm/tsa.py:12-81, 141-220 (call eval_next.py:65)
  *   gnnmp_next3d_weights_floats / gnnmp_next3d_workspace_bytes / gnnmp_next3d_pb_forward / gnnmp_next3d_state_forward
@@ -1010,6 +1012,85 @@ int gnnmp_next_weights_t_floats(int32_t dim, size_t* n_floats);
 int gnnmp_next_train_forward(const gnnmp_next_train* desc, void* hip_stream);
 int gnnmp_next_state_backward(const gnnmp_next_train_bwd* desc, void* hip_stream);
 int gnnmp_next_pb_backward(const gnnmp_next_train_bwd* desc, void* hip_stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The replay of NEXT's training loop on maze problems (additive to ABI 9; next_replay_kernels.hip) -- train_next.py:25-68,
+ * 88-108: the (problem, path) samples train() draws from, with get_label's actions and values, kept on the device, and the loss
+ * train() differentiates.
+ *
+ * The store is a struct of caller-owned device arrays; counts, status and path_ptr[0] start as zeros.  Path i is rows
+ * path_ptr[i] : path_ptr[i + 1] of states64 / states32 / actions / values and belongs to problem[i].
+ *   gnnmp_next_replay_append_trees   the path of every successful problem (success != 0 and path_len > 0) of one gnnmp_next_plan
+ *                                    batch, in ascending batch position: rows states[b, path[b, j]], j < path_len[b] -- what
+ *                                    search_tree.path()[0] returns.
+ *   gnnmp_next_replay_append_paths   every packed path (BIT*'s get_best_path() rows, anything collected elsewhere), in order.
+ * Both compute the slots and offsets with one exclusive scan (one wave, integers, no atomic ordering), then run get_label in
+ * float64, one wave per path, rounding to float32 once: edge = np.linalg.norm(next - prev); the running cost ONE serial
+ * left-to-right chain, value = cost - cost[last]; action = interpolate(prev, next, RRT_EPS / edge) - prev when edge > RRT_EPS
+ * (the stick robot's interpolate wraps the orientation gap and the result by one period), else next - prev; zero for the last
+ * state.  states32 is the float32 rounding of the rows, what Model2D.net_forward feeds the network.
+ * An append is all or nothing: when the new paths or states would not fit (status bit 1), or the source is malformed (bit 2: a
+ * path_len outside [0, t_max + 1]; path_ptr not from 0 to n_states or a path without a state; counts outside the capacities),
+ * counts and every row in use stay as they are.  Bit 4: a node id outside [0, t_max] in an appended path; its row is zeros.
+ * status is accumulated (OR), never cleared.  pending is the call's scratch: {first slot, first state, paths, states} of the
+ * last append; problem[] of the new slots holds source indices between the call's two launches.
+ *
+ *   gnnmp_next_path_loss   for a group of G paths over y [S, dim + 1] (path g is rows ptr[g] : ptr[g + 1]):
+ *                          terms[g] = {mean_s (values - y[:, dim])^2, mean_{s, j} (actions - y[:, :dim])^2} in double, one wave a
+ *                          path and every sum one ascending chain; loss = (sum_g terms[g, 0] + terms[g, 1]) / divisor in
+ *                          train()'s order; dy = d loss / d y in float32.  divisor is train()'s 8, whatever G is.  terms, loss
+ *                          and dy are optional (NULL: not computed; loss needs terms).  A path outside [0, S) or without rows
+ *                          gets NaN terms and touches no row; rows of dy outside every path are not written.
+ * No floating-point atomics, no scratch, no allocation, no synchronisation: two runs give the same bits.
+ *
+ * Checks, in this order, each before any HIP call: GNNMP_ERR_NULL (a struct), GNNMP_ERR_DIMS (dim not 2 / 3), GNNMP_ERR_ARG (a
+ * negative count or capacity, t_max + 1 beyond int32, divisor < 1), GNNMP_ERR_NULL (an array: the store's first, then the
+ * source's; loss without terms), then GNNMP_OK WITHOUT ANY HIP CALL AND WITHOUT WRITING ANYTHING when there is no work --
+ * n_problems == 0, n_paths == 0, or terms and dy both NULL.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct {
+    int32_t dim, cap_paths, cap_states;
+    double* states64;                    /* [cap_states, dim]                                                              */
+    float* states32;                     /* [cap_states, dim]                                                              */
+    float* actions;                      /* [cap_states, dim]                                                              */
+    float* values;                       /* [cap_states]                                                                   */
+    int32_t* path_ptr;                   /* [cap_paths + 1]                                                                */
+    int32_t* problem;                    /* [cap_paths]                                                                    */
+    int32_t* counts;                     /* [2]  paths and states in use                                                   */
+    int32_t* status;                     /* [1]  bits 1 / 2 / 4, see above                                                 */
+    int32_t* pending;                    /* [4]  scratch of an append call                                                 */
+} gnnmp_next_replay;
+
+typedef struct {
+    int32_t n_problems, t_max;           /* the batch and T of the gnnmp_next_plan call                                    */
+    const double* states;                /* [B, t_max + 1, dim]  gnnmp_next_plan_tree.states                               */
+    const int32_t* path;                 /* [B, t_max + 1]       node ids, start first                                     */
+    const int32_t* path_len;             /* [B]                                                                            */
+    const int32_t* success;              /* [B]                                                                            */
+    const int32_t* problem_ids;          /* [B]  what problem[] receives                                                   */
+} gnnmp_next_replay_trees;
+
+typedef struct {
+    int32_t n_paths, n_states;
+    const double* paths64;               /* [n_states, dim]                                                                */
+    const int32_t* path_ptr;             /* [n_paths + 1]  from 0 to n_states, every path a state at least                 */
+    const int32_t* problem_ids;          /* [n_paths]                                                                      */
+} gnnmp_next_replay_paths;
+
+typedef struct {
+    int32_t n_paths, n_states, dim, divisor;
+    const float* y;                      /* [S, dim + 1]                                                                   */
+    const float* actions;                /* [S, dim]                                                                       */
+    const float* values;                 /* [S]                                                                            */
+    const int32_t* ptr;                  /* [G + 1]                                                                        */
+    double* terms;                       /* out [G, 2], optional                                                           */
+    double* loss;                        /* out [1], optional                                                              */
+    float* dy;                           /* out [S, dim + 1], optional                                                     */
+} gnnmp_next_path_loss_desc;
+
+int gnnmp_next_replay_append_trees(const gnnmp_next_replay* store, const gnnmp_next_replay_trees* trees, void* hip_stream);
+int gnnmp_next_replay_append_paths(const gnnmp_next_replay* store, const gnnmp_next_replay_paths* paths, void* hip_stream);
+int gnnmp_next_path_loss(const gnnmp_next_path_loss_desc* desc, void* hip_stream);
 
 /* ------------------------------------------------------------------------------------------
  * The NEXT planning network of the arm families (additive to ABI 9) -- the PPN of next_model/model3D.py:87-213 behind Model3D
