@@ -30,10 +30,13 @@ from . import next_train3d  # noqa: F401,E402  (NEXT training of the arm familie
 from .next_train3d import NextNet3DTrain  # noqa: F401,E402
 from . import next_replay  # noqa: F401,E402  (NEXT's training loop on mazes: the replay on the device, train(), train_env: gnnmp_next_replay_*)
 from .next_replay import ReplayStore, collect_replay, path_loss, train_env_maze, train_replay  # noqa: F401,E402
+from . import smoother_replay  # noqa: F401,E402  (the smoother's training loop on mazes: replay, gather, loss, train_env: gnnmp_smooth_replay_*)
+from .smoother_replay import SmoothReplayStore, train_smoother_maze  # noqa: F401,E402
 
 __all__ = ['graph_build', 'hostenv', 'synth', 'GraphBatch', 'EncoderProcessDecoder', 'ModelSmoother', 'SmoothBatch', 'episodes',
            'oracle_smooth', 'frontier', 'rng', 'lazysp', 'eval_lazysp_device', 'lazysp_plan_host', 'plan_lazysp_maze_batch', 'rrtstar',
            'eval_rrt_device', 'rrtstar_plan_host', 'plan_rrtstar_maze_batch', 'bitstar', 'eval_bit_device', 'bitstar_plan_host',
            'plan_bitstar_maze_batch', 'next_model', 'next_plan', 'Model2D', 'NextNet', 'next_plan_host',
            'next_model3d', 'Model3D', 'NextNet3D', 'next_train', 'next_train3d',
-           'NextNet3DTrain', 'next_replay', 'ReplayStore', 'collect_replay', 'path_loss', 'train_env_maze', 'train_replay']
+           'NextNet3DTrain', 'next_replay', 'ReplayStore', 'collect_replay', 'path_loss', 'train_env_maze', 'train_replay',
+           'smoother_replay', 'SmoothReplayStore', 'train_smoother_maze']

@@ -166,6 +166,27 @@ class NextPathLoss(ctypes.Structure):           # gnnmp_next_path_loss_desc
                 ('terms', ctypes.c_void_p), ('loss', ctypes.c_void_p), ('dy', ctypes.c_void_p)]
 
 
+class SmoothReplay(ctypes.Structure):           # gnnmp_smooth_replay
+    _fields_ = [('config_size', ctypes.c_int32), ('cap_samples', ctypes.c_int32), ('cap_path_rows', ctypes.c_int32),
+                ('cap_free_rows', ctypes.c_int32), ('cap_coll_rows', ctypes.c_int32), ('epoch', ctypes.c_int32),
+                ('path', ctypes.c_void_p), ('target', ctypes.c_void_p), ('free_pts', ctypes.c_void_p), ('collided', ctypes.c_void_p),
+                ('path_ptr', ctypes.c_void_p), ('free_ptr', ctypes.c_void_p), ('coll_ptr', ctypes.c_void_p),
+                ('problem', ctypes.c_void_p), ('counts', ctypes.c_void_p), ('status', ctypes.c_void_p), ('pending', ctypes.c_void_p)]
+
+
+class SmoothReplaySrc(ctypes.Structure):        # gnnmp_smooth_replay_src
+    _fields_ = [('n_samples', ctypes.c_int32), ('total_path', ctypes.c_int32), ('total_nodes', ctypes.c_int32),
+                ('take_upper', ctypes.c_int32), ('path', ctypes.c_void_p), ('target', ctypes.c_void_p), ('v', ctypes.c_void_p),
+                ('path_ptr', ctypes.c_void_p), ('node_ptr', ctypes.c_void_p), ('n_free', ctypes.c_void_p), ('take', ctypes.c_void_p),
+                ('problem_ids', ctypes.c_void_p)]
+
+
+class SmoothPathLoss(ctypes.Structure):         # gnnmp_smooth_path_loss_desc
+    _fields_ = [('n_paths', ctypes.c_int32), ('total_rows', ctypes.c_int32), ('config_size', ctypes.c_int32),
+                ('divisor', ctypes.c_int32), ('path_ptr', ctypes.c_void_p), ('pred', ctypes.c_void_p), ('target', ctypes.c_void_p),
+                ('terms', ctypes.c_void_p), ('loss', ctypes.c_void_p), ('d_pred', ctypes.c_void_p)]
+
+
 class Next3dPbForward(ctypes.Structure):
     _fields_ = [('n_problems', ctypes.c_int32), ('dim', ctypes.c_int32), ('point_dim', ctypes.c_int32), ('width', ctypes.c_int32),
                 ('iters', ctypes.c_int32), ('maps', ctypes.c_void_p), ('goals', ctypes.c_void_p), ('weights', ctypes.c_void_p),
@@ -356,6 +377,10 @@ def lib():
     L.gnnmp_next_replay_append_trees.argtypes = [ctypes.POINTER(NextReplay), ctypes.POINTER(NextReplayTrees), vp]
     L.gnnmp_next_replay_append_paths.argtypes = [ctypes.POINTER(NextReplay), ctypes.POINTER(NextReplayPaths), vp]
     L.gnnmp_next_path_loss.argtypes = [ctypes.POINTER(NextPathLoss), vp]
+    L.gnnmp_smooth_replay_append.argtypes = [ctypes.POINTER(SmoothReplay), ctypes.POINTER(SmoothReplaySrc), vp]
+    L.gnnmp_smooth_replay_gather.argtypes = [ctypes.POINTER(SmoothReplay), ctypes.c_int32, ctypes.c_int32, vp,
+                                             ctypes.POINTER(SmoothBatch), vp, vp]
+    L.gnnmp_smooth_path_loss.argtypes = [ctypes.POINTER(SmoothPathLoss), vp]
     L.gnnmp_next3d_weights_floats.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(sz)]
     L.gnnmp_next3d_workspace_bytes.argtypes = [ctypes.c_int32, ctypes.POINTER(sz)]
     L.gnnmp_next3d_pb_forward.argtypes = [ctypes.POINTER(Next3dPbForward), vp]

@@ -2107,6 +2107,86 @@ extern "C" int gnnmp_next_path_loss(const gnnmp_next_path_loss_desc* d, void* hi
 }
 
 // =============================================================================================
+// the replay of the smoother's training loop (smoother_replay_kernels.hip).  The same order of checks: the structs, config_size,
+// negative counts, NULL arrays (the store's first), then the no-work return BEFORE ANY HIP CALL (it writes nothing).
+// =============================================================================================
+static bool smooth_replay_dims_ok(int32_t C) { return C >= 2 && C <= 14; }
+
+static bool smooth_replay_counts_bad(const gnnmp_smooth_replay* s) {
+    return s->cap_samples < 0 || s->cap_path_rows < 0 || s->cap_free_rows < 0 || s->cap_coll_rows < 0 || s->epoch < 0 ||
+           s->cap_samples == INT32_MAX;
+}
+
+static int smooth_replay_store(const gnnmp_smooth_replay* s, SmoothReplayStore& st) {
+    st.C = s->config_size; st.cap_samples = s->cap_samples; st.cap_path = s->cap_path_rows; st.cap_free = s->cap_free_rows;
+    st.cap_coll = s->cap_coll_rows; st.epoch = s->epoch;
+    st.path = s->path; st.target = s->target; st.free_pts = s->free_pts; st.coll = s->collided;
+    st.path_ptr = s->path_ptr; st.free_ptr = s->free_ptr; st.coll_ptr = s->coll_ptr; st.problem = s->problem;
+    st.counts = s->counts; st.status = s->status; st.pending = s->pending;
+    return !s->path || !s->target || !s->free_pts || !s->collided || !s->path_ptr || !s->free_ptr || !s->coll_ptr || !s->problem ||
+                   !s->counts || !s->status || !s->pending
+               ? GNNMP_ERR_NULL
+               : GNNMP_OK;
+}
+
+extern "C" int gnnmp_smooth_replay_append(const gnnmp_smooth_replay* s, const gnnmp_smooth_replay_src* q, void* hip_stream) {
+    if (!s || !q) return GNNMP_ERR_NULL;
+    if (!smooth_replay_dims_ok(s->config_size)) return GNNMP_ERR_DIMS;
+    if (smooth_replay_counts_bad(s) || q->n_samples < 0 || q->total_path < 0 || q->total_nodes < 0 || q->take_upper < 0 ||
+        q->take_upper > q->n_samples)
+        return GNNMP_ERR_ARG;
+    SmoothReplayStore st;
+    if (int rc = smooth_replay_store(s, st)) return rc;
+    if (!q->path || !q->target || !q->v || !q->path_ptr || !q->node_ptr || !q->n_free || !q->take || !q->problem_ids)
+        return GNNMP_ERR_NULL;
+    if (q->n_samples == 0 || q->take_upper == 0) return GNNMP_OK;          // no work: no HIP call, nothing written
+    SmoothReplaySrc src;
+    src.B = q->n_samples; src.total_path = q->total_path; src.total_nodes = q->total_nodes; src.take_upper = q->take_upper;
+    src.path = q->path; src.target = q->target; src.v = q->v; src.path_ptr = q->path_ptr; src.node_ptr = q->node_ptr;
+    src.n_free = q->n_free; src.take = q->take; src.problem_ids = q->problem_ids;
+    HIP_TRY(launch_smooth_replay_append(st, src, static_cast<hipStream_t>(hip_stream)));
+    return GNNMP_OK;
+}
+
+extern "C" int gnnmp_smooth_replay_gather(const gnnmp_smooth_replay* s, int32_t n_group, int32_t n_samples, const int32_t* idx,
+                                          const gnnmp_smooth_batch* out, float* out_target, void* hip_stream) {
+    if (!s || !out) return GNNMP_ERR_NULL;
+    if (!smooth_replay_dims_ok(s->config_size)) return GNNMP_ERR_DIMS;
+    if (smooth_replay_counts_bad(s) || n_group < 0 || n_samples < 0 || out->n_problems != n_group || out->total_path < 0 ||
+        out->total_free < 0 || out->total_collided < 0 || out->total_edges < 0)
+        return GNNMP_ERR_ARG;
+    SmoothReplayStore st;
+    if (int rc = smooth_replay_store(s, st)) return rc;
+    if (!idx || !out->path || !out->free_pts || !out->collided || !out->edge_index || !out->path_ptr || !out->free_ptr ||
+        !out->coll_ptr || !out->edge_ptr || !out_target)
+        return GNNMP_ERR_NULL;
+    if (n_group == 0) return GNNMP_OK;                                     // no work: no HIP call, nothing written
+    SmoothGatherParams p;
+    p.G = n_group; p.n_samples = n_samples; p.total_path = out->total_path; p.total_free = out->total_free;
+    p.total_coll = out->total_collided; p.total_edges = out->total_edges; p.idx = idx;
+    p.path = const_cast<float*>(out->path); p.target = out_target; p.free_pts = const_cast<float*>(out->free_pts);
+    p.coll = const_cast<float*>(out->collided);
+    p.edge_index = reinterpret_cast<long long*>(const_cast<int64_t*>(out->edge_index));
+    p.path_ptr = const_cast<int32_t*>(out->path_ptr); p.free_ptr = const_cast<int32_t*>(out->free_ptr);
+    p.coll_ptr = const_cast<int32_t*>(out->coll_ptr); p.edge_ptr = const_cast<int32_t*>(out->edge_ptr);
+    HIP_TRY(launch_smooth_replay_gather(st, p, static_cast<hipStream_t>(hip_stream)));
+    return GNNMP_OK;
+}
+
+extern "C" int gnnmp_smooth_path_loss(const gnnmp_smooth_path_loss_desc* d, void* hip_stream) {
+    if (!d) return GNNMP_ERR_NULL;
+    if (!smooth_replay_dims_ok(d->config_size)) return GNNMP_ERR_DIMS;
+    if (d->n_paths < 0 || d->total_rows < 0 || d->divisor < 1) return GNNMP_ERR_ARG;
+    if (!d->path_ptr || !d->pred || !d->target || !d->terms || !d->loss || !d->d_pred) return GNNMP_ERR_NULL;
+    if (d->n_paths == 0) return GNNMP_OK;                                  // no work: no HIP call, nothing written
+    SmoothPathLossParams p;
+    p.G = d->n_paths; p.total_rows = d->total_rows; p.C = d->config_size; p.divisor = d->divisor;
+    p.path_ptr = d->path_ptr; p.pred = d->pred; p.target = d->target; p.terms = d->terms; p.loss = d->loss; p.d_pred = d->d_pred;
+    HIP_TRY(launch_smooth_path_loss(p, static_cast<hipStream_t>(hip_stream)));
+    return GNNMP_OK;
+}
+
+// =============================================================================================
 // the NEXT planning network of the arm families (next3d_kernels.hip; next_model/model3D.py:87-213)
 // =============================================================================================
 static bool next3d_dims_ok(int32_t dim, int32_t point_dim) { return dim >= 1 && dim <= 15 && (point_dim == 3 || point_dim == 6); }

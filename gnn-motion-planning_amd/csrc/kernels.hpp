@@ -411,6 +411,37 @@ struct NextPathLossParams {
 hipError_t launch_next_replay_append(const NextReplayStore& st, const NextReplaySrc& s, bool trees, hipStream_t stream);
 hipError_t launch_next_path_loss(const NextPathLossParams& p, hipStream_t stream);
 
+// ---- the replay of the smoother's training loop (smoother_replay_kernels.hip, train_smoother.py:20-61, 91-99)
+struct SmoothReplayStore {
+    int C, cap_samples, cap_path, cap_free, cap_coll, epoch;
+    float *path, *target, *free_pts, *coll;            // [cap_path, C] x 2, [cap_free, C], [cap_coll, C]
+    int *path_ptr, *free_ptr, *coll_ptr, *problem;     // [cap_samples + 1] x 3, [cap_samples]
+    int *counts, *status, *pending;                    // [2, 4] banks (epoch & 1 is current); [1] bits 1 / 2 / 4; [8]
+};
+struct SmoothReplaySrc {
+    int B, total_path, total_nodes, take_upper;
+    const float *path, *target, *v;                    // [total_path, C] x 2, [total_nodes, C]
+    const int *path_ptr, *node_ptr, *n_free, *take, *problem_ids;      // [B + 1] x 2, [B] x 3
+};
+struct SmoothGatherParams {
+    int G, n_samples;                                  // group entries; samples in the store (the caller's mirror)
+    int total_path, total_free, total_coll, total_edges;               // the caller's totals: the sizes of the arrays below
+    const int* idx;                                    // [G]
+    float *path, *target, *free_pts, *coll;            // out
+    long long* edge_index;                             // out [2, total_edges]
+    int *path_ptr, *free_ptr, *coll_ptr, *edge_ptr;    // out [G + 1]
+};
+struct SmoothPathLossParams {
+    int G, total_rows, C, divisor;
+    const int* path_ptr;                               // [G + 1]
+    const float *pred, *target;                        // [total_rows, C]
+    double* terms;                                     // [G]
+    float *loss, *d_pred;                              // [1], [total_rows, C]
+};
+hipError_t launch_smooth_replay_append(const SmoothReplayStore& st, const SmoothReplaySrc& s, hipStream_t stream);
+hipError_t launch_smooth_replay_gather(const SmoothReplayStore& st, const SmoothGatherParams& p, hipStream_t stream);
+hipError_t launch_smooth_path_loss(const SmoothPathLossParams& p, hipStream_t stream);
+
 // ---- the NEXT planning network of the arm families (next3d_kernels.hip, next_model/model3D.py:87-213)
 struct Next3dPbParams {
     int B, dim, pd, iters;                // problems, state size 1 .. 15, point size 3 / 6, LSTM rounds

@@ -22,6 +22,8 @@
  *       one training step of PPN: forward with saved activations, backward    train_next.py:41-69 (next_model/model2D.py:84-210)
  *   gnnmp_next_replay_append_trees / gnnmp_next_replay_append_paths / gnnmp_next_path_loss
  *       train_env's replay with get_label's labels, and train()'s loss        train_next.py:25-68, 88-108
+ *   gnnmp_smooth_replay_append / gnnmp_smooth_replay_gather / gnnmp_smooth_path_loss
+ *       the smoother's replay, train()'s per-step batch and its loss          train_smoother.py:20-61, 91-99
  *   gnnmp_next_plan / gnnmp_next_plan_max_nodes                                       (ABI 9)
  *       NEXT_plan with a model, batched, one launch            algorithm/tsa.py:12-81, 141-220 (call eval_next.py:65)
  *   gnnmp_next3d_weights_floats / gnnmp_next3d_workspace_bytes / gnnmp_next3d_pb_forward / gnnmp_next3d_state_forward
@@ -1091,6 +1093,94 @@ typedef struct {
 int gnnmp_next_replay_append_trees(const gnnmp_next_replay* store, const gnnmp_next_replay_trees* trees, void* hip_stream);
 int gnnmp_next_replay_append_paths(const gnnmp_next_replay* store, const gnnmp_next_replay_paths* paths, void* hip_stream);
 int gnnmp_next_path_loss(const gnnmp_next_path_loss_desc* desc, void* hip_stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The replay of the smoother's training loop on maze problems (additive to ABI 9; smoother_replay_kernels.hip) --
+ * train_smoother.py:20-61, 91-99: the (path, path_smooth, free, collided) samples train() draws from, kept on the device, the
+ * gnnmp_smooth_batch of one optimizer step gathered from them, and the loss train() differentiates.  C = config_size, 2 .. 14.
+ *
+ * The store is a struct of caller-owned device arrays, all zero at first.  Sample i is rows path_ptr[i] : path_ptr[i + 1] of
+ * path and target, free_ptr[i] : free_ptr[i + 1] of free_pts, coll_ptr[i] : coll_ptr[i + 1] of collided, and belongs to
+ * problem[i].  counts holds TWO banks of {samples, path rows, free rows, collided rows}: a call reads bank (epoch & 1) and
+ * writes bank ((epoch + 1) & 1), so the workgroups of one launch never read a word another one writes; the caller passes the
+ * number of append calls it has made on the store so far as `epoch`.  INVARIANT: `epoch` counts every append call on these
+ * arrays that got past the no-work return, whether it appended or not, for the store's whole life, and ONE owner keeps it; a
+ * second owner of the same arrays (two wrappers over one allocation) would read the stale bank.  Nothing on the device detects
+ * that: pending[0 .. 4) reports the counts the call started from, and a caller that mirrors the store compares them with its own
+ * (the Python wrapper raises on a difference).
+ *
+ *   gnnmp_smooth_replay_append   ONE launch, one workgroup per source sample.  Every taken sample (take != 0), in ascending
+ *       position, receives the next slot: its P path rows and P target rows, its first min(n_free, 500) sample rows as free
+ *       rows and its first min(n_coll, 500) rows behind the free ones as collided rows, n_coll = (node_ptr[b + 1] -
+ *       node_ptr[b]) - n_free; a side without rows receives ONE all-zero filler row (obs_data of train_smoother.py:20-30).
+ *       Wave 0 of every workgroup runs the same exclusive scan over all B sources (integers, no atomics) and so knows its own
+ *       slot and four row offsets and whether the call fits; workgroup 0 alone writes the prefix arrays, problem[], pending[],
+ *       status and the other counts bank.  All or nothing: when a capacity would be exceeded (status bit 1) or the source is
+ *       malformed (bit 2: a taken sample with P <= 2, rows outside [0, total_path) / [0, total_nodes), n_free outside its node
+ *       rows, more taken samples than take_upper, counts outside the capacities) no row and no prefix entry is written and the
+ *       new bank repeats the old counts.  pending = {samples, path rows, free rows, collided rows before the call; the four
+ *       numbers the call added}.  status is accumulated (OR) and cleared by the caller.
+ *   gnnmp_smooth_replay_gather   ONE launch, one workgroup per group entry: the gnnmp_smooth_batch of samples idx[0 .. G) in
+ *       that order (repeats allowed): path, free_pts and collided rows, `target` rows aligned with path, edge_index
+ *       [2, sum (3 P - 2)] in chain_edge_index's order (i + 1 -> i for i < P - 1, then i -> i + 1, then the P self loops;
+ *       path-local ids) and the four prefix arrays [G + 1].  The totals of `out` are the caller's (it mirrors the store's
+ *       prefix arrays); when an index lies outside [0, n_samples) or the totals the kernel finds differ from out's, NOTHING is
+ *       written but status bit 4.  The arrays `out` points to are written although the struct declares them const.
+ *   gnnmp_smooth_path_loss       ONE launch, one workgroup, one wave per path (8 waves take the paths in turn): for path g of
+ *       P = path_ptr[g + 1] - path_ptr[g] rows, terms[g] = sum over the interior rows 1 .. P - 2 and the C columns of
+ *       (pred - target)^2, ONE ascending chain in double in (row, column) order, / ((P - 2) C) -- MSELoss(target[1:-1],
+ *       pred[1:-1]); loss = (sum_g terms[g], ascending g, one lane) / divisor rounded to float32 once; d_pred = 2 (pred -
+ *       target) / ((P - 2) C divisor) evaluated in double and rounded once on interior rows, exactly 0 on every other row of
+ *       the path.  P <= 2 (or path_ptr outside [0, total_rows]): terms[g] = 0 and, for a path inside the rows, zero rows.
+ * No floating-point atomics, no scratch, no allocation, no synchronisation: two runs give the same bits.
+ *
+ * Checks, in this order, each before any HIP call: GNNMP_ERR_NULL (a struct), GNNMP_ERR_DIMS (config_size outside 2 .. 14),
+ * GNNMP_ERR_ARG (a negative count, capacity, total or epoch; take_upper > n_samples; divisor < 1), GNNMP_ERR_NULL (an array:
+ * the store's first, then the call's own), then GNNMP_OK WITHOUT ANY HIP CALL AND WITHOUT WRITING ANYTHING when there is no
+ * work: n_samples == 0 or take_upper == 0 (append), n_group == 0 (gather), n_paths == 0 (path loss).
+ * ---------------------------------------------------------------------------------------- */
+typedef struct {
+    int32_t config_size, cap_samples, cap_path_rows, cap_free_rows, cap_coll_rows, epoch;
+    float* path;                         /* [cap_path_rows, C]                                                             */
+    float* target;                       /* [cap_path_rows, C]                                                             */
+    float* free_pts;                     /* [cap_free_rows, C]                                                             */
+    float* collided;                     /* [cap_coll_rows, C]                                                             */
+    int32_t* path_ptr;                   /* [cap_samples + 1]                                                              */
+    int32_t* free_ptr;                   /* [cap_samples + 1]                                                              */
+    int32_t* coll_ptr;                   /* [cap_samples + 1]                                                              */
+    int32_t* problem;                    /* [cap_samples]                                                                  */
+    int32_t* counts;                     /* [2, 4]  two banks, see above                                                   */
+    int32_t* status;                     /* [1]  bits 1 / 2 / 4, see above                                                 */
+    int32_t* pending;                    /* [8]  the last append call                                                      */
+} gnnmp_smooth_replay;
+
+typedef struct {
+    int32_t n_samples, total_path, total_nodes;
+    int32_t take_upper;                  /* an upper bound of the set take flags (n_samples when unknown); 0: no work      */
+    const float* path;                   /* [total_path, C]                                                                */
+    const float* target;                 /* [total_path, C]                                                                */
+    const float* v;                      /* [total_nodes, C]  per sample its free rows, then its collided rows             */
+    const int32_t* path_ptr;             /* [B + 1]                                                                        */
+    const int32_t* node_ptr;             /* [B + 1]                                                                        */
+    const int32_t* n_free;               /* [B]                                                                            */
+    const int32_t* take;                 /* [B]                                                                            */
+    const int32_t* problem_ids;          /* [B]  what problem[] receives                                                   */
+} gnnmp_smooth_replay_src;
+
+typedef struct {
+    int32_t n_paths, total_rows, config_size, divisor;
+    const int32_t* path_ptr;             /* [G + 1]                                                                        */
+    const float* pred;                   /* [total_rows, C]                                                                */
+    const float* target;                 /* [total_rows, C]                                                                */
+    double* terms;                       /* out [G]                                                                        */
+    float* loss;                         /* out [1]                                                                        */
+    float* d_pred;                       /* out [total_rows, C]                                                            */
+} gnnmp_smooth_path_loss_desc;
+
+int gnnmp_smooth_replay_append(const gnnmp_smooth_replay* store, const gnnmp_smooth_replay_src* src, void* hip_stream);
+int gnnmp_smooth_replay_gather(const gnnmp_smooth_replay* store, int32_t n_group, int32_t n_samples, const int32_t* idx,
+                               const gnnmp_smooth_batch* out, float* out_target, void* hip_stream);
+int gnnmp_smooth_path_loss(const gnnmp_smooth_path_loss_desc* desc, void* hip_stream);
 
 /* ------------------------------------------------------------------------------------------
  * The NEXT planning network of the arm families (additive to ABI 9) -- the PPN of next_model/model3D.py:87-213 behind Model3D
