@@ -32,6 +32,8 @@ from . import next_replay  # noqa: F401,E402  (NEXT's training loop on mazes: th
 from .next_replay import ReplayStore, collect_replay, path_loss, train_env_maze, train_replay  # noqa: F401,E402
 from . import smoother_replay  # noqa: F401,E402  (the smoother's training loop on mazes: replay, gather, loss, train_env: gnnmp_smooth_replay_*)
 from .smoother_replay import SmoothReplayStore, train_smoother_maze  # noqa: F401,E402
+from . import explorer_replay  # noqa: F401,E402  (the explorer's training loop on mazes: dataset, gather, loss, schedule: gnnmp_episode_dataset_gather / _frontier_loss)
+from .explorer_replay import ExplorerDataset, train_explorer_maze  # noqa: F401,E402
 
 __all__ = ['graph_build', 'hostenv', 'synth', 'GraphBatch', 'EncoderProcessDecoder', 'ModelSmoother', 'SmoothBatch', 'episodes',
            'oracle_smooth', 'frontier', 'rng', 'lazysp', 'eval_lazysp_device', 'lazysp_plan_host', 'plan_lazysp_maze_batch', 'rrtstar',
@@ -39,4 +41,5 @@ __all__ = ['graph_build', 'hostenv', 'synth', 'GraphBatch', 'EncoderProcessDecod
            'plan_bitstar_maze_batch', 'next_model', 'next_plan', 'Model2D', 'NextNet', 'next_plan_host',
            'next_model3d', 'Model3D', 'NextNet3D', 'next_train', 'next_train3d',
            'NextNet3DTrain', 'next_replay', 'ReplayStore', 'collect_replay', 'path_loss', 'train_env_maze', 'train_replay',
-           'smoother_replay', 'SmoothReplayStore', 'train_smoother_maze']
+           'smoother_replay', 'SmoothReplayStore', 'train_smoother_maze', 'explorer_replay', 'ExplorerDataset',
+           'train_explorer_maze']

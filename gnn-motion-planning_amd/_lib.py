@@ -181,6 +181,29 @@ class SmoothReplaySrc(ctypes.Structure):        # gnnmp_smooth_replay_src
                 ('problem_ids', ctypes.c_void_p)]
 
 
+class EpisodeDataset(ctypes.Structure):         # gnnmp_episode_dataset
+    _fields_ = [('n_problems', ctypes.c_int32), ('total_nodes', ctypes.c_int32), ('total_edges', ctypes.c_int32),
+                ('total_obs', ctypes.c_int32), ('config_size', ctypes.c_int32), ('obs_size', ctypes.c_int32),
+                ('v', ctypes.c_void_p), ('points64', ctypes.c_void_p), ('edge_index', ctypes.c_void_p), ('edge_free', ctypes.c_void_p),
+                ('edge_cost', ctypes.c_void_p), ('obstacles', ctypes.c_void_p), ('node_ptr', ctypes.c_void_p),
+                ('edge_ptr', ctypes.c_void_p), ('obs_ptr', ctypes.c_void_p), ('status', ctypes.c_void_p)]
+
+
+class EpisodeDatasetBatch(ctypes.Structure):    # gnnmp_episode_dataset_batch
+    _fields_ = [('n_problems', ctypes.c_int32), ('total_nodes', ctypes.c_int32), ('total_edges', ctypes.c_int32),
+                ('total_obs', ctypes.c_int32),
+                ('v', ctypes.c_void_p), ('points64', ctypes.c_void_p), ('edge_index', ctypes.c_void_p), ('edge_free', ctypes.c_void_p),
+                ('edge_cost', ctypes.c_void_p), ('obstacles', ctypes.c_void_p), ('node_ptr', ctypes.c_void_p),
+                ('edge_ptr', ctypes.c_void_p), ('obs_ptr', ctypes.c_void_p)]
+
+
+class EpisodeFrontierLoss(ctypes.Structure):    # gnnmp_episode_frontier_loss_desc
+    _fields_ = [('n_problems', ctypes.c_int32), ('total_edges', ctypes.c_int32), ('divisor', ctypes.c_double),
+                ('frontier', ctypes.c_void_p), ('frontier_len', ctypes.c_void_p), ('label', ctypes.c_void_p),
+                ('status', ctypes.c_void_p), ('edge_ptr', ctypes.c_void_p), ('scores', ctypes.c_void_p), ('terms', ctypes.c_void_p),
+                ('counted', ctypes.c_void_p), ('loss', ctypes.c_void_p), ('dscores', ctypes.c_void_p), ('bad', ctypes.c_void_p)]
+
+
 class SmoothPathLoss(ctypes.Structure):         # gnnmp_smooth_path_loss_desc
     _fields_ = [('n_paths', ctypes.c_int32), ('total_rows', ctypes.c_int32), ('config_size', ctypes.c_int32),
                 ('divisor', ctypes.c_int32), ('path_ptr', ctypes.c_void_p), ('pred', ctypes.c_void_p), ('target', ctypes.c_void_p),
@@ -381,6 +404,8 @@ def lib():
     L.gnnmp_smooth_replay_gather.argtypes = [ctypes.POINTER(SmoothReplay), ctypes.c_int32, ctypes.c_int32, vp,
                                              ctypes.POINTER(SmoothBatch), vp, vp]
     L.gnnmp_smooth_path_loss.argtypes = [ctypes.POINTER(SmoothPathLoss), vp]
+    L.gnnmp_episode_dataset_gather.argtypes = [ctypes.POINTER(EpisodeDataset), ctypes.c_int32, vp, ctypes.POINTER(EpisodeDatasetBatch), vp]
+    L.gnnmp_episode_frontier_loss.argtypes = [ctypes.POINTER(EpisodeFrontierLoss), vp]
     L.gnnmp_next3d_weights_floats.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(sz)]
     L.gnnmp_next3d_workspace_bytes.argtypes = [ctypes.c_int32, ctypes.POINTER(sz)]
     L.gnnmp_next3d_pb_forward.argtypes = [ctypes.POINTER(Next3dPbForward), vp]

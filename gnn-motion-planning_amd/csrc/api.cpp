@@ -2187,6 +2187,55 @@ extern "C" int gnnmp_smooth_path_loss(const gnnmp_smooth_path_loss_desc* d, void
 }
 
 // =============================================================================================
+// the explorer's training loop around one step (explorer_replay_kernels.hip).  The same order of checks: the structs, the dims,
+// negative counts, NULL arrays (the store's first), then the no-work return BEFORE ANY HIP CALL (it writes nothing).
+// =============================================================================================
+extern "C" int gnnmp_episode_dataset_gather(const gnnmp_episode_dataset* s, int32_t n_group, const int32_t* idx,
+                                            const gnnmp_episode_dataset_batch* out, void* hip_stream) {
+    if (!s || !out) return GNNMP_ERR_NULL;
+    if (s->config_size < 2 || s->config_size > 14 || s->obs_size < 1 || s->obs_size > 16) return GNNMP_ERR_DIMS;
+    if (s->n_problems < 0 || s->total_nodes < 0 || s->total_edges < 0 || s->total_obs < 0 || n_group < 0 ||
+        out->n_problems != n_group || out->total_nodes < 0 || out->total_edges < 0 || out->total_obs < 0)
+        return GNNMP_ERR_ARG;
+    if (!s->v || !s->points64 || !s->edge_index || !s->edge_free || !s->edge_cost || !s->obstacles || !s->node_ptr ||
+        !s->edge_ptr || !s->obs_ptr || !s->status)
+        return GNNMP_ERR_NULL;
+    if (!idx || !out->v || !out->points64 || !out->edge_index || !out->edge_free || !out->edge_cost || !out->obstacles ||
+        !out->node_ptr || !out->edge_ptr || !out->obs_ptr)
+        return GNNMP_ERR_NULL;
+    if (n_group == 0) return GNNMP_OK;                                     // no work: no HIP call, nothing written
+    EpisodeDatasetStore st;
+    st.n = s->n_problems; st.total_nodes = s->total_nodes; st.total_edges = s->total_edges; st.total_obs = s->total_obs;
+    st.C = s->config_size; st.S = s->obs_size;
+    st.v = s->v; st.points64 = s->points64; st.edge_index = reinterpret_cast<const long long*>(s->edge_index);
+    st.edge_free = s->edge_free; st.edge_cost = s->edge_cost; st.obstacles = s->obstacles;
+    st.node_ptr = s->node_ptr; st.edge_ptr = s->edge_ptr; st.obs_ptr = s->obs_ptr; st.status = s->status;
+    EpisodeGatherParams p;
+    p.G = n_group; p.total_nodes = out->total_nodes; p.total_edges = out->total_edges; p.total_obs = out->total_obs;
+    p.idx = idx; p.v = out->v; p.points64 = out->points64; p.edge_index = reinterpret_cast<long long*>(out->edge_index);
+    p.edge_free = out->edge_free; p.edge_cost = out->edge_cost; p.obstacles = out->obstacles;
+    p.node_ptr = out->node_ptr; p.edge_ptr = out->edge_ptr; p.obs_ptr = out->obs_ptr;
+    HIP_TRY(launch_episode_dataset_gather(st, p, static_cast<hipStream_t>(hip_stream)));
+    return GNNMP_OK;
+}
+
+extern "C" int gnnmp_episode_frontier_loss(const gnnmp_episode_frontier_loss_desc* d, void* hip_stream) {
+    if (!d) return GNNMP_ERR_NULL;
+    if (d->n_problems < 0 || d->total_edges < 0 || !(d->divisor > 0.0) || !std::isfinite(d->divisor)) return GNNMP_ERR_ARG;
+    if (!d->frontier || !d->frontier_len || !d->label || !d->status || !d->edge_ptr || !d->scores || !d->terms || !d->counted ||
+        !d->loss || !d->dscores || !d->bad)
+        return GNNMP_ERR_NULL;
+    if (d->n_problems == 0) return GNNMP_OK;                               // no work: no HIP call, nothing written
+    EpisodeFrontierLossParams p;
+    p.B = d->n_problems; p.total_edges = d->total_edges; p.divisor = d->divisor;
+    p.frontier = d->frontier; p.frontier_len = d->frontier_len; p.label = d->label; p.status = d->status;
+    p.edge_ptr = d->edge_ptr; p.scores = d->scores; p.terms = d->terms; p.counted = d->counted; p.loss = d->loss;
+    p.dscores = d->dscores; p.bad = d->bad;
+    HIP_TRY(launch_episode_frontier_loss(p, static_cast<hipStream_t>(hip_stream)));
+    return GNNMP_OK;
+}
+
+// =============================================================================================
 // the NEXT planning network of the arm families (next3d_kernels.hip; next_model/model3D.py:87-213)
 // =============================================================================================
 static bool next3d_dims_ok(int32_t dim, int32_t point_dim) { return dim >= 1 && dim <= 15 && (point_dim == 3 || point_dim == 6); }

@@ -442,6 +442,42 @@ hipError_t launch_smooth_replay_append(const SmoothReplayStore& st, const Smooth
 hipError_t launch_smooth_replay_gather(const SmoothReplayStore& st, const SmoothGatherParams& p, hipStream_t stream);
 hipError_t launch_smooth_path_loss(const SmoothPathLossParams& p, hipStream_t stream);
 
+// ---- the explorer's training loop around one step (explorer_replay_kernels.hip, train_explorer.py:96-210, dijkstra.py:91-97)
+struct EpisodeDatasetStore {
+    int n, total_nodes, total_edges, total_obs, C, S;  // problems; rows of the arrays below; config size; obstacle row size
+    const float* v;                                    // [total_nodes, C]
+    const double* points64;                            // [total_nodes, C]
+    const long long* edge_index;                       // [2, total_edges] graph-local
+    const unsigned char* edge_free;                    // [total_edges]
+    const double* edge_cost;                           // [total_edges]
+    const float* obstacles;                            // [total_obs, S]
+    const int *node_ptr, *edge_ptr, *obs_ptr;          // [n + 1]
+    int* status;                                       // [1] bits 1 / 2
+};
+struct EpisodeGatherParams {
+    int G, total_nodes, total_edges, total_obs;        // group entries; the caller's totals: the sizes of the arrays below
+    const int* idx;                                    // [G]
+    float* v;                                          // out, as in the store
+    double* points64;
+    long long* edge_index;                             // out [2, total_edges]
+    unsigned char* edge_free;
+    double* edge_cost;
+    float* obstacles;
+    int *node_ptr, *edge_ptr, *obs_ptr;                // out [G + 1]
+};
+struct EpisodeFrontierLossParams {
+    int B, total_edges;
+    double divisor;
+    const int *frontier, *frontier_len, *label, *status, *edge_ptr;    // [2 total_edges + B], [B] x 3, [B + 1]
+    const float* scores;                               // [total_edges]
+    float* terms;                                      // out [B]
+    int* counted;                                      // out [B]
+    float *loss, *dscores;                             // out [1], [total_edges]
+    int* bad;                                          // [1] bits 1 / 2 / 4, accumulated
+};
+hipError_t launch_episode_dataset_gather(const EpisodeDatasetStore& st, const EpisodeGatherParams& p, hipStream_t stream);
+hipError_t launch_episode_frontier_loss(const EpisodeFrontierLossParams& p, hipStream_t stream);
+
 // ---- the NEXT planning network of the arm families (next3d_kernels.hip, next_model/model3D.py:87-213)
 struct Next3dPbParams {
     int B, dim, pd, iters;                // problems, state size 1 .. 15, point size 3 / 6, LSTM rounds

@@ -46,15 +46,20 @@ class TrainingGraphs:
     training forward (obstacles [sumO, S], obs_ptr) -- what ``GraphBatch`` and the episode kernels read."""
 
     def __init__(self, v, edge_index, node_ptr_host, edge_ptr_host, edge_free, edge_cost, obstacles, obs_ptr_host,
-                 points64=None):
+                 points64=None, device_ptrs=None):
+        """``device_ptrs``: ``(node_ptr, edge_ptr, obs_ptr)`` as int32 device tensors that already hold (or, in stream order,
+        will hold) the values of the three host sequences; without it the host sequences are uploaded."""
         dev = v.device
         if dev.type != 'cuda':
             raise RuntimeError('gnnmp.episodes runs on the GPU only (got %s tensors); there is no CPU fallback' % dev)
         self.v, self.edge_index = v.contiguous(), edge_index.contiguous()
         self.node_ptr_host, self.edge_ptr_host, self.obs_ptr_host = list(node_ptr_host), list(edge_ptr_host), list(obs_ptr_host)
-        self.node_ptr = torch.tensor(self.node_ptr_host, dtype=torch.int32).to(dev)
-        self.edge_ptr = torch.tensor(self.edge_ptr_host, dtype=torch.int32).to(dev)
-        self.obs_ptr = torch.tensor(self.obs_ptr_host, dtype=torch.int32).to(dev)
+        if device_ptrs is None:
+            self.node_ptr = torch.tensor(self.node_ptr_host, dtype=torch.int32).to(dev)
+            self.edge_ptr = torch.tensor(self.edge_ptr_host, dtype=torch.int32).to(dev)
+            self.obs_ptr = torch.tensor(self.obs_ptr_host, dtype=torch.int32).to(dev)
+        else:
+            self.node_ptr, self.edge_ptr, self.obs_ptr = device_ptrs
         self.edge_free, self.edge_cost = edge_free.contiguous(), edge_cost.contiguous()
         self.obstacles = obstacles.contiguous()
         self.points64 = points64

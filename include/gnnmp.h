@@ -24,6 +24,8 @@
  *       train_env's replay with get_label's labels, and train()'s loss        train_next.py:25-68, 88-108
  *   gnnmp_smooth_replay_append / gnnmp_smooth_replay_gather / gnnmp_smooth_path_loss
  *       the smoother's replay, train()'s per-step batch and its loss          train_smoother.py:20-61, 91-99
+ *   gnnmp_episode_dataset_gather / gnnmp_episode_frontier_loss
+ *       the explorer's labelled-graph dataset, a step's batch and its loss    train_explorer.py:96-210, 172
  *   gnnmp_next_plan / gnnmp_next_plan_max_nodes                                       (ABI 9)
  *       NEXT_plan with a model, batched, one launch            algorithm/tsa.py:12-81, 141-220 (call eval_next.py:65)
  *   gnnmp_next3d_weights_floats / gnnmp_next3d_workspace_bytes / gnnmp_next3d_pb_forward / gnnmp_next3d_state_forward
@@ -1181,6 +1183,89 @@ int gnnmp_smooth_replay_append(const gnnmp_smooth_replay* store, const gnnmp_smo
 int gnnmp_smooth_replay_gather(const gnnmp_smooth_replay* store, int32_t n_group, int32_t n_samples, const int32_t* idx,
                                const gnnmp_smooth_batch* out, float* out_target, void* hip_stream);
 int gnnmp_smooth_path_loss(const gnnmp_smooth_path_loss_desc* desc, void* hip_stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The explorer's training loop around one optimizer step on maze problems (additive to ABI 9; explorer_replay_kernels.hip) --
+ * train_explorer.py:96-210 over the labelled graphs of algorithm/dijkstra.py:91-97: the batch of a group of problems gathered
+ * out of a device-resident dataset, and the policy loss of :172 with its gradient.
+ *
+ * The dataset is a struct of caller-owned device arrays: problem i is rows node_ptr[i] : node_ptr[i + 1] of v and points64,
+ * columns edge_ptr[i] : edge_ptr[i + 1] of edge_index (graph-local node ids), edge_free and edge_cost, and rows obs_ptr[i] :
+ * obs_ptr[i + 1] of obstacles.  C = config_size (2 .. 14), S = obs_size (1 .. 16).
+ *
+ *   gnnmp_episode_dataset_gather   ONE launch, one workgroup per group entry: the arrays of problems idx[0 .. G) in that order
+ *       (repeats allowed) and the three prefix arrays [G + 1] of the batch.  Wave 0 of every workgroup runs the same exclusive
+ *       scan over the G entries, so no workgroup reads what another writes.  The totals of `out` are the caller's (it mirrors
+ *       the prefix arrays).  An index outside [0, n_problems) is NOT clamped: that slot is empty (its prefix entries repeat
+ *       the previous ones, nothing is copied for it) and status bit 1 is set; the other slots are written as usual.  When the
+ *       prefix entries of a selected problem do not ascend inside the store's totals, or the totals the kernel finds differ
+ *       from out's, NOTHING is written but status bit 2.  status is accumulated (OR) and cleared by the caller.
+ *   gnnmp_episode_frontier_loss    what follows gnnmp_episode_frontier: one launch of one wave per problem plus a one-lane sum.
+ *       Problem b's frontier is frontier[2 edge_ptr[b] + b ...][0 .. frontier_len[b]) (edge ids of the batch), label[b] the
+ *       position of the next edge in it.  With m = the maximum of the listed scores and sum = sum over the LIST of exp(s - m)
+ *       in double (lane l of the wave adds the entries l, l + 64, ... in ascending order, the 64 partial sums meet in a fixed
+ *       butterfly; an edge listed twice counts twice, as policy[frontier] does), terms[b] = log(sum) - (s_label - m) rounded
+ *       to float32 once -- log_softmax's order --, counted[b] = 1, and dscores[e] = (count_e exp(s_e - m) / sum - [e is the
+ *       label's edge]) / divisor, evaluated in double and rounded once, exactly 0 for an edge of the problem that is not
+ *       listed.  A problem with status != 0, frontier_len == 0 or label < 0 is not counted: terms[b] = 0, counted[b] = 0,
+ *       dscores 0 over its whole edge range.  loss = (terms[0] + terms[1] + ..., ascending, in double) / divisor, rounded
+ *       once.  `bad` (accumulated by an integer OR, cleared by the caller): bit 1 a frontier entry outside its problem's edge
+ *       range (it contributes nothing), or frontier_len outside [0, 2 E + 1], label >= frontier_len or the label's entry
+ *       outside the range (the problem is not counted); bit 2 edge_ptr entries that do not ascend inside [0, total_edges]
+ *       (term 0, counted 0, no dscores written); bit 4 a problem of more than 16384 edges (not counted).
+ * No floating-point atomics, no scratch, no allocation, no synchronisation: two runs give the same bits.
+ *
+ * Checks, in this order, each before any HIP call: GNNMP_ERR_NULL (a struct), GNNMP_ERR_DIMS (gather: config_size outside
+ * 2 .. 14 or obs_size outside 1 .. 16), GNNMP_ERR_ARG (a negative count or total; out->n_problems != n_group; a divisor that
+ * is not a finite number above 0), GNNMP_ERR_NULL (an array: the store's first, then the call's own), then GNNMP_OK WITHOUT
+ * ANY HIP CALL AND WITHOUT WRITING ANYTHING when there is no work: n_group == 0 (gather), n_problems == 0 (loss).
+ * ---------------------------------------------------------------------------------------- */
+typedef struct {
+    int32_t n_problems, total_nodes, total_edges, total_obs, config_size, obs_size;
+    const float* v;                      /* [total_nodes, C]                                                               */
+    const double* points64;              /* [total_nodes, C]                                                               */
+    const int64_t* edge_index;           /* [2, total_edges]  graph-local node ids                                         */
+    const uint8_t* edge_free;            /* [total_edges]                                                                  */
+    const double* edge_cost;             /* [total_edges]                                                                  */
+    const float* obstacles;              /* [total_obs, S]                                                                 */
+    const int32_t* node_ptr;             /* [n_problems + 1]                                                               */
+    const int32_t* edge_ptr;             /* [n_problems + 1]                                                               */
+    const int32_t* obs_ptr;              /* [n_problems + 1]                                                               */
+    int32_t* status;                     /* [1]  bits 1 / 2, see above                                                     */
+} gnnmp_episode_dataset;
+
+typedef struct {
+    int32_t n_problems, total_nodes, total_edges, total_obs;     /* the group's size and the caller's totals               */
+    float* v;                            /* out [total_nodes, C]                                                           */
+    double* points64;                    /* out [total_nodes, C]                                                           */
+    int64_t* edge_index;                 /* out [2, total_edges]                                                           */
+    uint8_t* edge_free;                  /* out [total_edges]                                                              */
+    double* edge_cost;                   /* out [total_edges]                                                              */
+    float* obstacles;                    /* out [total_obs, S]                                                             */
+    int32_t* node_ptr;                   /* out [G + 1]                                                                    */
+    int32_t* edge_ptr;                   /* out [G + 1]                                                                    */
+    int32_t* obs_ptr;                    /* out [G + 1]                                                                    */
+} gnnmp_episode_dataset_batch;
+
+typedef struct {
+    int32_t n_problems, total_edges;
+    double divisor;
+    const int32_t* frontier;             /* [2 total_edges + B]  gnnmp_episode_frontier's                                  */
+    const int32_t* frontier_len;         /* [B]                                                                            */
+    const int32_t* label;                /* [B]                                                                            */
+    const int32_t* status;               /* [B]                                                                            */
+    const int32_t* edge_ptr;             /* [B + 1]                                                                        */
+    const float* scores;                 /* [total_edges]                                                                  */
+    float* terms;                        /* out [B]                                                                        */
+    int32_t* counted;                    /* out [B]                                                                        */
+    float* loss;                         /* out [1]                                                                        */
+    float* dscores;                      /* out [total_edges]                                                              */
+    int32_t* bad;                        /* [1]  bits 1 / 2 / 4, see above                                                 */
+} gnnmp_episode_frontier_loss_desc;
+
+int gnnmp_episode_dataset_gather(const gnnmp_episode_dataset* store, int32_t n_group, const int32_t* idx,
+                                 const gnnmp_episode_dataset_batch* out, void* hip_stream);
+int gnnmp_episode_frontier_loss(const gnnmp_episode_frontier_loss_desc* desc, void* hip_stream);
 
 /* ------------------------------------------------------------------------------------------
  * The NEXT planning network of the arm families (additive to ABI 9) -- the PPN of next_model/model3D.py:87-213 behind Model3D
