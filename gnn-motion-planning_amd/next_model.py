@@ -269,23 +269,72 @@ class NextNet:
     def check_status(self):
         """Read the status words of the ``state_forward`` calls issued so far (this waits for them).  Raises RuntimeError when
         a ``problem_of_state`` entry was outside ``[0, B)``."""
-        import torch
         pending, self._pending = self._pending, []
-        if not pending:
-            return
-        words = torch.stack(pending).cpu().numpy()
-        bad = np.flatnonzero(words[:, 0])
-        if bad.size:
-            raise RuntimeError('gnnmp_next_state_forward: %d state(s) with problem_of_state outside [0, B) (last offending row %d, '
-                               'call %d of %d checked); their rows of y are NaN'
-                               % (int(words[bad, 0].sum()), int(words[bad[0], 1]) - 1, int(bad[0]), len(pending)))
+        raise_bad_status(pending, 'gnnmp_next_state_forward')
 
 
-class Model2D:
+def raise_bad_status(pending, entry, noun='state', tail=''):
+    """The status words ``[count, last row + 1]`` that the calls of ``entry`` left, one device tensor a call (reading them
+    waits for the calls): RuntimeError when any counted a ``problem_of_state`` outside ``[0, B)``.  Shared by the inference
+    and the training networks of both families; ``noun`` is what they call a row, ``tail`` what else follows from one."""
+    import torch
+    if not pending:
+        return
+    words = torch.stack(pending).cpu().numpy()
+    bad = np.flatnonzero(words[:, 0])
+    if bad.size:
+        raise RuntimeError('%s: %d %s(s) with problem_of_state outside [0, B) (last offending row %d, call %d of %d checked); '
+                           'their rows of y are NaN%s'
+                           % (entry, int(words[bad, 0].sum()), noun, int(words[bad[0], 1]) - 1, int(bad[0]), len(pending), tail))
+
+
+class PlannerModel:
+    """What ``Model2D`` and ``Model3D`` share behind the reference's interface: ``net_forward`` once a class has built its input
+    rows (:meth:`_rows`), ``pred_value``, ``policy`` and ``check_status``.  ``policy`` samples on the host with torch's
+    ``MultivariateNormal`` from the global torch generator, call for call what the reference does, so the draw stream is the
+    reference's.  A subclass sets ``dim``, ``var``, ``device``, ``net`` and, in ``set_problem``, ``pb_rep``."""
+
+    def net_forward(self, states, use_np=True):
+        import torch
+        if self.pb_rep is None:
+            raise RuntimeError('%s: set_problem first' % type(self).__name__)
+        states = np.asarray(states)
+        if states.ndim == 1:
+            states = states.reshape(1, -1)
+        cur = self._rows(states)
+        of = torch.zeros(cur.shape[0], dtype=torch.int32, device=self.device)
+        y = self.net.state_forward(cur, of, self.pb_rep)
+        if not use_np:
+            return y[:, :self.dim], y[:, -1]
+        y = y.cpu().numpy()
+        actions, values = y[:, :self.dim], y[:, -1]
+        if actions.shape[0] == 1:
+            actions, values = actions[0], values[0]
+        return actions, values
+
+    def pred_value(self, states):
+        return self.net_forward(states)[1]
+
+    def policy(self, state, k=1):
+        import torch
+        from torch.distributions.multivariate_normal import MultivariateNormal
+        mean, _ = self.net_forward(state)
+        m = MultivariateNormal(torch.FloatTensor(mean), self.var)
+        actions, priors = [], []
+        for _ in range(k):
+            a = m.sample()
+            priors.append(torch.exp(m.log_prob(a)).item())
+            actions.append(a.cpu().numpy())
+        return actions, priors
+
+    def check_status(self):
+        self.net.check_status()
+
+
+class Model2D(PlannerModel):
     """The reference's ``Model2D`` interface (next_model/model2D.py:213-294) over :class:`NextNet`, so the reference's
     ``NEXT_plan`` and :func:`gnnmp.next_plan.plan_host` run on it unchanged: ``set_problem``, ``net_forward``, ``pred_value``,
-    ``policy``.  ``policy`` samples on the host with torch's ``MultivariateNormal`` from the global torch generator, call for
-    call what the reference does, so the draw stream is the reference's."""
+    ``policy`` (:class:`PlannerModel`)."""
 
     def __init__(self, env_or_problem=None, dim=2, std=None, device='cuda'):
         import torch
@@ -319,38 +368,6 @@ class Model2D:
         goal = torch.from_numpy(np.asarray(problem['goal_state'], dtype=np.float32).reshape(1, self.dim)).to(self.device)
         self.pb_rep = self.net.pb_forward(maps, goal, self.iters)
 
-    def net_forward(self, states, use_np=True):
+    def _rows(self, states):
         import torch
-        if self.pb_rep is None:
-            raise RuntimeError('Model2D: set_problem first')
-        states = np.asarray(states)
-        if states.ndim == 1:
-            states = states.reshape(1, -1)
-        cur = torch.from_numpy(np.ascontiguousarray(states, dtype=np.float32)).to(self.device)
-        of = torch.zeros(cur.shape[0], dtype=torch.int32, device=self.device)
-        y = self.net.state_forward(cur, of, self.pb_rep)
-        if not use_np:
-            return y[:, :self.dim], y[:, -1]
-        y = y.cpu().numpy()
-        actions, values = y[:, :self.dim], y[:, -1]
-        if actions.shape[0] == 1:
-            actions, values = actions[0], values[0]
-        return actions, values
-
-    def pred_value(self, states):
-        return self.net_forward(states)[1]
-
-    def policy(self, state, k=1):
-        import torch
-        from torch.distributions.multivariate_normal import MultivariateNormal
-        mean, _ = self.net_forward(state)
-        m = MultivariateNormal(torch.FloatTensor(mean), self.var)
-        actions, priors = [], []
-        for _ in range(k):
-            a = m.sample()
-            priors.append(torch.exp(m.log_prob(a)).item())
-            actions.append(a.cpu().numpy())
-        return actions, priors
-
-    def check_status(self):
-        self.net.check_status()
+        return torch.from_numpy(np.ascontiguousarray(states, dtype=np.float32)).to(self.device)

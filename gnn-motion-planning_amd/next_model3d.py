@@ -23,7 +23,7 @@ import ctypes
 
 import numpy as np
 
-from .next_model import _mfma_pack, _np_weights, _sigmoid
+from .next_model import PlannerModel, _mfma_pack, _np_weights, _sigmoid, raise_bad_status
 
 WIDTH, VOXELS, CAP, G, LATENT = 15, 3375, 8, 8, 64
 DEFAULT_ITERS = 20
@@ -292,24 +292,15 @@ class NextNet3D:
     def check_status(self):
         """Read the status words of the ``state_forward`` calls issued so far (this waits for them).  Raises RuntimeError when
         a ``problem_of_state`` entry was outside ``[0, B)``."""
-        import torch
         pending, self._pending = self._pending, []
-        if not pending:
-            return
-        words = torch.stack(pending).cpu().numpy()
-        bad = np.flatnonzero(words[:, 0])
-        if bad.size:
-            raise RuntimeError('gnnmp_next3d_state_forward: %d state(s) with problem_of_state outside [0, B) (last offending row '
-                               '%d, call %d of %d checked); their rows of y are NaN'
-                               % (int(words[bad, 0].sum()), int(words[bad[0], 1]) - 1, int(bad[0]), len(pending)))
+        raise_bad_status(pending, 'gnnmp_next3d_state_forward')
 
 
-class Model3D:
+class Model3D(PlannerModel):
     """The reference's ``Model3D`` interface (next_model/model3D.py:216-306) over :class:`NextNet3D`, so the reference's
-    ``NEXT_plan`` runs on it unchanged: ``set_problem``, ``net_forward``, ``pred_value``, ``policy``.  ``env`` supplies
-    ``RRT_EPS`` and ``get_robot_points(state)`` (the point part of every input row, computed on the host as the reference does).
-    ``policy`` samples on the host with torch's ``MultivariateNormal`` from the global torch generator, call for call what the
-    reference does, so the draw stream is the reference's."""
+    ``NEXT_plan`` runs on it unchanged: ``set_problem``, ``net_forward``, ``pred_value``, ``policy``
+    (:class:`gnnmp.next_model.PlannerModel`).  ``env`` supplies ``RRT_EPS`` and ``get_robot_points(state)`` (the point part of
+    every input row, computed on the host as the reference does)."""
 
     def __init__(self, env, dim, point_dim=3, std=None, device='cuda', UCB_type='kde'):
         import torch
@@ -341,39 +332,7 @@ class Model3D:
         self.goal_state = torch.FloatTensor(goal).to(self.device)
         self.pb_rep = self.net.pb_forward(self.maze_map, self.goal_state, self.iters)
 
-    def net_forward(self, states, use_np=True):
+    def _rows(self, states):
         import torch
-        if self.pb_rep is None:
-            raise RuntimeError('Model3D: set_problem first')
-        states = np.asarray(states)
-        if states.ndim == 1:
-            states = states.reshape(1, -1)
         positions = [np.concatenate((self.env.get_robot_points(state), state), axis=-1) for state in states]
-        cur = torch.FloatTensor(np.array(positions)).to(self.device)
-        of = torch.zeros(cur.shape[0], dtype=torch.int32, device=self.device)
-        y = self.net.state_forward(cur, of, self.pb_rep)
-        if not use_np:
-            return y[:, :self.dim], y[:, -1]
-        y = y.cpu().numpy()
-        actions, values = y[:, :self.dim], y[:, -1]
-        if actions.shape[0] == 1:
-            actions, values = actions[0], values[0]
-        return actions, values
-
-    def pred_value(self, states):
-        return self.net_forward(states)[1]
-
-    def policy(self, state, k=1):
-        import torch
-        from torch.distributions.multivariate_normal import MultivariateNormal
-        mean, _ = self.net_forward(state)
-        m = MultivariateNormal(torch.FloatTensor(mean), self.var)
-        actions, priors = [], []
-        for _ in range(k):
-            a = m.sample()
-            priors.append(torch.exp(m.log_prob(a)).item())
-            actions.append(a.cpu().numpy())
-        return actions, priors
-
-    def check_status(self):
-        self.net.check_status()
+        return torch.FloatTensor(np.array(positions)).to(self.device)

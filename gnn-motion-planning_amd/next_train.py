@@ -13,26 +13,30 @@ averaged over the problems of a step, with the gradient through the whole networ
     ``torch.autograd.Function`` over ``gnnmp_next_train_forward`` / ``gnnmp_next_state_backward`` / ``gnnmp_next_pb_backward``
     (``csrc/next_train_kernels.hip``), and ``train_step``, one optimizer step of ``train()``.
 
-The kernels are the only implementation: on a CPU tensor ``forward`` raises.  An empty call (no states) never reaches the
-library: the library's own no-work calls return before any HIP call and write nothing, so Python hands
-back the empty ``y`` and zero gradients itself.
+What is specific to the mazes lives here: the parameter shapes, the transposed packing, the labels' step, :data:`FAMILY`.  The
+body it describes the mazes to -- the packing index and its adjoint, the autograd function, the network's base class, the label
+loop -- is :mod:`gnnmp.next_train_core`, shared with :mod:`gnnmp.next_train3d`.
 """
-import ctypes
-
 import numpy as np
-import torch
 
-from .next_model import DEFAULT_ITERS, LATENT, WIDTH, _conv_pack, _mfma_pack, _np_weights, pack_weights
+from . import _lib, next_train_core as core
+from .next_model import DEFAULT_ITERS, WIDTH, _conv_pack, _mfma_pack, _np_weights, pack_weights
+from .next_train_core import loss_from_outputs  # noqa: F401  (one loss for both families; tests and tools take it from here)
 
 RRT_EPS = 5e-2                              # environment/env_config.py
 _SHARE = (0, 2, 4, 6, 8, 10)
 
 
+def _check_dims(dims, who):
+    dim, = (int(d) for d in dims)
+    if dim not in (2, 3):
+        raise ValueError('%s: dim is 2 (point robot) or 3 (stick robot)' % who)
+    return (dim,)
+
+
 def param_shapes(dim):
     """The reference's trainable parameters (``PPN.named_parameters()``: ``attention_s`` is ``attention_g``, listed once)."""
-    dim = int(dim)
-    if dim not in (2, 3):
-        raise ValueError('next_train: dim is 2 (point robot) or 3 (stick robot)')
+    dim, = _check_dims((dim,), 'next_train')
     shapes = {}
     for name, cin in (('hidden', 9), ('h0', 64), ('c0', 64), ('conv', 64)):
         shapes[name + '.weight'], shapes[name + '.bias'] = (64, cin, 3, 3), (64,)
@@ -44,9 +48,6 @@ def param_shapes(dim):
     for layer, (co, ci) in zip((0, 2, 4), ((128, 8), (64, 128), (dim + 1, 64))):
         shapes['policy.%d.weight' % layer], shapes['policy.%d.bias' % layer] = (co, ci), (co,)
     return shapes
-
-
-_INDEX = {}
 
 
 def pack_weights_t(weights, dim):
@@ -61,74 +62,32 @@ def pack_weights_t(weights, dim):
     return np.ascontiguousarray(np.concatenate([np.asarray(p, dtype=np.float32).reshape(-1) for p in parts]))
 
 
-def _index_of(packer, dim, names):
-    shapes = param_shapes(dim)
-    zeros = {k: np.zeros(s, dtype=np.float32) for k, s in shapes.items()}
-    index, total = {}, None
-    for name in names:
-        shape = shapes[name]
-        w = dict(zeros)
-        n = int(np.prod(shape))
-        w[name] = np.arange(1, n + 1, dtype=np.float32).reshape(shape)             # n < 2^24: exact in float32
-        packed = packer(w, dim)
-        total = packed.shape[0]
-        pos = np.flatnonzero(packed)
-        if pos.size != n:
-            raise RuntimeError('next_train: the packing is not a permutation of %s' % name)
-        idx = np.empty(n, dtype=np.int64)
-        idx[packed[pos].astype(np.int64) - 1] = pos
-        index[name] = idx.reshape(shape)
-    return index, total
+_T_NAMES = ('conv.weight', 'h0.weight', 'c0.weight', 'lstm.weight_ih', 'lstm.weight_hh')
+
+FAMILY = core.Family(
+    module='next_train', cls='NextNetTrain', noun='state', goal='goal', check=_check_dims,
+    param_shapes=param_shapes, pack=pack_weights, pack_t=pack_weights_t, t_names=_T_NAMES,
+    structs=(_lib.NextTrain, _lib.NextTrainBwd),
+    entries=('gnnmp_next_train_workspace_bytes', 'gnnmp_next_train_forward', 'gnnmp_next_state_backward', 'gnnmp_next_pb_backward'),
+    map_shape=(WIDTH, WIDTH))
 
 
 def _pack_index(dim):
     """name -> int64 array of the parameter's shape: where each element lands in the packed vector.  Read off
     ``pack_weights`` itself (one parameter at a time set to 1, 2, 3, ...), so the two cannot drift apart."""
-    if dim not in _INDEX:
-        _INDEX[dim], _INDEX[dim, 'n'] = _index_of(pack_weights, dim, list(param_shapes(dim)))
-    return _INDEX[dim]
-
-
-_T_NAMES = ('conv.weight', 'h0.weight', 'c0.weight', 'lstm.weight_ih', 'lstm.weight_hh')
-
-
-def _pack_t_index(dim):
-    if (dim, 't') not in _INDEX:
-        _INDEX[dim, 't'], _INDEX[dim, 'tn'] = _index_of(pack_weights_t, dim, _T_NAMES)
-    return _INDEX[dim, 't']
-
-
-_DEV_INDEX = {}
-
-
-def _dev_index(which, dim, device):
-    """The index arrays as flat int64 tensors on ``device``, uploaded once."""
-    key = (which, dim, str(device))
-    if key not in _DEV_INDEX:
-        index = _pack_t_index(dim) if which == 't' else _pack_index(dim)
-        _DEV_INDEX[key] = {k: torch.from_numpy(v.reshape(-1)).to(device) for k, v in index.items()}
-    return _DEV_INDEX[key]
-
-
-def _scatter(which, params, dim):
-    device = next(iter(params.values())).device
-    index = _dev_index(which, dim, device)      # fills _INDEX[dim, 'n' / 'tn'], the packed lengths
-    out = torch.zeros(_INDEX[dim, 'tn' if which == 't' else 'n'], dtype=torch.float32, device=device)
-    for name, idx in index.items():
-        out.index_add_(0, idx, params[name].detach().to(torch.float32).reshape(-1))
-    return out
+    return core.pack_index(FAMILY, (dim,))[0]
 
 
 def device_pack(params, dim):
     """:func:`gnnmp.next_model.pack_weights` on the tensors' own device: every reference-named parameter scattered through
-    :func:`_pack_index` with ``index_add_`` into zeros.  ``lstm.bias_ih`` and ``lstm.bias_hh`` land on the same positions, so
-    the one packed bias is ``(0 + bias_ih) + bias_hh``: the host packer's single rounding.  Bit-equal to ``pack_weights``."""
-    return _scatter('w', params, int(dim))
+    :func:`_pack_index` into zeros (:func:`gnnmp.next_train_core.scatter`).  Bit-equal to ``pack_weights``, the one packed
+    LSTM bias ``bias_ih + bias_hh`` included."""
+    return core.scatter(FAMILY, _check_dims((dim,), 'next_train.device_pack'), 'w', params)
 
 
 def device_pack_t(params, dim):
     """:func:`pack_weights_t` on the tensors' own device."""
-    return _scatter('t', params, int(dim))
+    return core.scatter(FAMILY, _check_dims((dim,), 'next_train.device_pack_t'), 't', params)
 
 
 def unpack_weight_grads(packed, dim):
@@ -136,28 +95,18 @@ def unpack_weight_grads(packed, dim):
     arrays (numpy in, numpy out; a torch tensor in, tensors on its device out).  The adjoint of ``pack_weights``: the MFMA and
     convolution permutations inverted, padding lanes dropped, and the one packed LSTM bias (``bias_ih + bias_hh``) giving the
     same gradient to both."""
-    index = _pack_index(int(dim))
-    n = max(int(v.max()) for v in index.values()) + 1
-    if hasattr(packed, 'detach'):
-        flat = packed.reshape(-1)
-        if flat.shape[0] < n:
-            raise ValueError('unpack_weight_grads: %d packed floats, need at least %d' % (flat.shape[0], n))
-        dev = _dev_index('w', int(dim), flat.device)
-        return {k: flat[dev[k]].reshape(v.shape) for k, v in index.items()}
-    flat = np.asarray(packed).reshape(-1)
-    if flat.shape[0] < n:
-        raise ValueError('unpack_weight_grads: %d packed floats, need at least %d' % (flat.shape[0], n))
-    return {k: flat[v] for k, v in index.items()}
+    return core.unpack(FAMILY, _check_dims((dim,), 'next_train.unpack_weight_grads'), packed)
 
 
 # --------------------------------------------------------------------------------------------------
-# labels (train_next.get_label)
+# labels (train_next.get_label) and the loss of train()
 # --------------------------------------------------------------------------------------------------
-def _interpolate(prev, nxt, ratio, dim):
+def _interpolate(dim):
+    """The environment's ``interpolate`` as the label loop's ``step(prev, nxt, ratio)``."""
     if dim == 3:
         from .maze2d import Maze3D
-        return Maze3D.interpolate(Maze3D, prev.copy(), nxt.copy(), ratio)
-    return prev + (nxt - prev) * ratio
+        return lambda prev, nxt, ratio: Maze3D.interpolate(Maze3D, prev.copy(), nxt.copy(), ratio)
+    return lambda prev, nxt, ratio: prev + (nxt - prev) * ratio
 
 
 def path_labels(paths, path_ptr, env_or_dim):
@@ -168,37 +117,7 @@ def path_labels(paths, path_ptr, env_or_dim):
     orientation), and zero for the last state."""
     dim = int(getattr(env_or_dim, 'dim', env_or_dim))
     eps = float(getattr(env_or_dim, 'RRT_EPS', RRT_EPS))
-    paths = np.asarray(paths, dtype=np.float64).reshape(-1, dim)
-    ptr = np.asarray(path_ptr, dtype=np.int64).reshape(-1)
-    if ptr.size < 1 or ptr[0] != 0 or ptr[-1] != paths.shape[0] or (np.diff(ptr) < 1).any():
-        raise ValueError('path_labels: path_ptr runs from 0 to the number of states, every path has a state')
-    actions = np.zeros_like(paths)
-    values = np.zeros(paths.shape[0], dtype=np.float64)
-    for a, b in zip(ptr[:-1], ptr[1:]):
-        cost = [0.]
-        for k in range(a, b - 1):
-            prev, nxt = paths[k], paths[k + 1]
-            edge = np.linalg.norm(nxt - prev)
-            cost.append(cost[-1] + edge)
-            if edge > eps:
-                actions[k] = _interpolate(prev, nxt, eps / edge, dim) - prev
-            else:
-                actions[k] = nxt - prev
-        values[a:b] = np.array(cost) - cost[-1]
-    return actions.astype(np.float32), values.astype(np.float32)
-
-
-# --------------------------------------------------------------------------------------------------
-# the loss of train()
-# --------------------------------------------------------------------------------------------------
-def loss_from_outputs(y, actions, values, ptr):
-    """The mean over the paths of ``MSE(value) + MSE(action)`` from ``y`` [N, dim + 1]: what ``train()`` calls ``.backward()``
-    on when a step holds 8 paths.  Differentiable in ``y``; shared with the tests' host oracle."""
-    total = 0.
-    for a, b in zip(ptr[:-1], ptr[1:]):
-        a, b = int(a), int(b)
-        total = total + ((values[a:b] - y[a:b, -1]) ** 2).mean() + ((actions[a:b] - y[a:b, :-1]) ** 2).mean()
-    return total / (len(ptr) - 1)
+    return core.path_labels(np.asarray(paths, dtype=np.float64).reshape(-1, dim), path_ptr, eps, _interpolate(dim))
 
 
 def training_loss(net, maps, goals, paths, path_ptr, iters=DEFAULT_ITERS):
@@ -206,183 +125,28 @@ def training_loss(net, maps, goals, paths, path_ptr, iters=DEFAULT_ITERS):
     ``maps[i]``, ``goals[i]`` (device tensors) with the path ``paths[path_ptr[i] : path_ptr[i + 1]]`` (host array, float64 as
     the planners return it).  ``net`` is a :class:`gnnmp.next_model.NextNet`; the states enter as float32, as in
     ``Model2D.net_forward``.  Evaluation only: the inference kernels keep no gradient history."""
-    ptr = np.asarray(path_ptr, dtype=np.int64).reshape(-1)
-    paths = np.asarray(paths, dtype=np.float64).reshape(-1, net.dim)
-    actions, values = path_labels(paths, ptr, net.dim)
-    dev = maps.device
-    of = torch.from_numpy(np.repeat(np.arange(ptr.size - 1, dtype=np.int32), np.diff(ptr))).to(dev)
-    y = net.state_forward(torch.from_numpy(paths.astype(np.float32)).to(dev), of, net.pb_forward(maps, goals, iters))
-    return loss_from_outputs(y, torch.from_numpy(actions).to(dev), torch.from_numpy(values).to(dev), ptr)
+    paths, ptr = core.sample_arrays(paths, path_ptr, net.dim)
+    return core.sample_loss(lambda states, of: net.state_forward(states, of, net.pb_forward(maps, goals, iters)),
+                            paths.astype(np.float32), ptr, path_labels(paths, ptr, net.dim), maps.device)
 
 
 # --------------------------------------------------------------------------------------------------
 # the trainable network on the device
 # --------------------------------------------------------------------------------------------------
-class _NextTrainFn(torch.autograd.Function):
-    """``y`` of :meth:`NextNetTrain.forward`.  The forward packs the parameters on the device and calls
-    ``gnnmp_next_train_forward``; the backward calls ``gnnmp_next_state_backward``, then ``gnnmp_next_pb_backward`` (which
-    completes the shared attention's gradient: DESIGN.md section 7), then :func:`unpack_weight_grads`."""
-
-    @staticmethod
-    def forward(ctx, net, maps, goals, states, of, iters, *params):
-        from . import _lib
-        dim, dev = net.dim, maps.device
-        B, S = int(maps.shape[0]), int(states.shape[0])
-        named = dict(zip(net._names, params))
-        ctx.net, ctx.meta = net, (B, S, int(iters))
-        y = torch.empty(S, dim + 1, dtype=torch.float32, device=dev)
-        if S == 0:                              # nothing to read out: the library is not called, the gradients are zero
-            ctx.empty = True
-            return y
-        ctx.empty = False
-        packed, packed_t = device_pack(named, dim), device_pack_t(named, dim)
-        pb_rep = torch.empty(B, LATENT, WIDTH, WIDTH, dtype=torch.float32, device=dev)
-        status = torch.zeros(2, dtype=torch.int32, device=dev)
-        ws = net._workspace(B, int(iters), S, dev)
-        d = _lib.NextTrain(B, S, dim, WIDTH, int(iters), maps.data_ptr(), goals.data_ptr(), states.data_ptr(), of.data_ptr(),
-                           packed.data_ptr(), pb_rep.data_ptr(), y.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel())
-        with torch.cuda.device(dev):
-            _lib.check(_lib.lib().gnnmp_next_train_forward(ctypes.byref(d), torch.cuda.current_stream(dev).cuda_stream),
-                       'gnnmp_next_train_forward')
-        net._pending.append(status)
-        net._generation += 1
-        ctx.generation = net._generation
-        ctx.held = (goals, states, of, packed, packed_t, pb_rep, ws)
-        net.pb_rep = pb_rep
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        from . import _lib
-        net = ctx.net
-        none = (None,) * 6
-        if ctx.empty:
-            return none + tuple(torch.zeros_like(p) for p in net._params.values())
-        if ctx.generation != net._generation:
-            raise RuntimeError('NextNetTrain: backward after a later forward -- the workspace holds one forward at a time')
-        B, S, iters = ctx.meta
-        goals, states, of, packed, packed_t, pb_rep, ws = ctx.held
-        dev = pb_rep.device
-        dy = dy.to(torch.float32).contiguous()
-        dpb = torch.empty_like(pb_rep)
-        dw = torch.empty_like(packed)
-        d = _lib.NextTrainBwd(B, S, net.dim, WIDTH, iters, goals.data_ptr(), states.data_ptr(), of.data_ptr(), packed.data_ptr(),
-                              packed_t.data_ptr(), pb_rep.data_ptr(), dy.data_ptr(), dpb.data_ptr(), dw.data_ptr(), ws.data_ptr(),
-                              ws.numel())
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            _lib.check(_lib.lib().gnnmp_next_state_backward(ctypes.byref(d), stream), 'gnnmp_next_state_backward')
-            _lib.check(_lib.lib().gnnmp_next_pb_backward(ctypes.byref(d), stream), 'gnnmp_next_pb_backward')
-        net.last_dweights = dw
-        grads = unpack_weight_grads(dw, net.dim)
-        return none + tuple(grads[k].to(p.dtype) for k, p in net._params.items())
-
-
-class NextNetTrain:
-    """The NEXT network with trainable parameters on the device.  ``load_state_dict`` / ``state_dict`` speak the reference's
-    names (``attention_s.*`` is written as copies of ``attention_g.*``, so :class:`gnnmp.next_model.NextNet` and ``Model2D``
-    load the result); ``parameters()`` / ``named_parameters()`` are torch Parameters an optimizer takes.  The workspace of the
-    saved activations belongs to the object and is reused across steps: run a forward's backward before the next forward."""
+class NextNetTrain(core.TrainNet):
+    """The NEXT network with trainable parameters on the device (:class:`gnnmp.next_train_core.TrainNet`; its ``state_dict`` is
+    what :class:`gnnmp.next_model.NextNet` and ``Model2D`` load).  ``forward(maps, goals, states, problem_of_state, iters)``:
+    ``maps`` [B, 15, 15], ``goals`` [B, dim], ``states`` [S, dim], ``problem_of_state`` [S] (any order, repeats) -> ``y``
+    [S, dim + 1] with a gradient history to the parameters."""
+    family = FAMILY
 
     def __init__(self, dim, device='cuda'):
-        if dim not in (2, 3):
-            raise ValueError('NextNetTrain: dim is 2 (point robot) or 3 (stick robot)')
-        self.dim = int(dim)
-        self.device = torch.device(device)
-        self._names = list(param_shapes(self.dim))
-        self._params = {}
-        self._pending = []
-        self._ws = None
-        self._generation = 0
-        self.pb_rep = None
-        self.last_dweights = None
-
-    def load_state_dict(self, state_dict):
-        w = _np_weights(state_dict, np.float32)
-        pack_weights(w, self.dim)               # its checks: a checkpoint of this dim, attention_s equal to attention_g
-        shapes = param_shapes(self.dim)
-        params = {}
-        for name in self._names:
-            if tuple(w[name].shape) != tuple(shapes[name]):
-                raise ValueError('NextNetTrain: %s has shape %s, expected %s' % (name, w[name].shape, shapes[name]))
-            params[name] = torch.nn.Parameter(torch.from_numpy(np.ascontiguousarray(w[name])).to(self.device))
-        self._params = params
-        return self
-
-    def state_dict(self):
-        if not self._params:
-            raise RuntimeError('NextNetTrain: load_state_dict first')
-        out = {k: p.detach().clone() for k, p in self._params.items()}
-        for k in list(out):
-            if k.startswith('attention_g.'):
-                out['attention_s.' + k[len('attention_g.'):]] = out[k].clone()
-        return out
-
-    def named_parameters(self):
-        return list(self._params.items())
-
-    def parameters(self):
-        return list(self._params.values())
-
-    def _workspace(self, B, iters, S, dev):
-        from . import _lib
-        n = ctypes.c_size_t()
-        _lib.check(_lib.lib().gnnmp_next_train_workspace_bytes(B, iters, S, ctypes.byref(n)), 'gnnmp_next_train_workspace_bytes')
-        if self._ws is None or self._ws.numel() < n.value or self._ws.device != dev:
-            self._ws = torch.empty(int(n.value), dtype=torch.uint8, device=dev)          # the allocator's blocks are 512-byte aligned
-        return self._ws
-
-    def forward(self, maps, goals, states, problem_of_state, iters=DEFAULT_ITERS):
-        """``maps`` [B, 15, 15], ``goals`` [B, dim], ``states`` [S, dim], ``problem_of_state`` [S] (any order, repeats) ->
-        ``y`` [S, dim + 1] with a gradient history to the parameters."""
-        if not self._params:
-            raise RuntimeError('NextNetTrain: load_state_dict first')
-        dev = maps.device
-        if dev.type != 'cuda':
-            raise RuntimeError('NextNetTrain.forward: device tensors only (the kernels are the only implementation)')
-        maps = maps.to(torch.float32).reshape(-1, WIDTH, WIDTH).contiguous()
-        goals = goals.to(device=dev, dtype=torch.float32).reshape(-1, self.dim).contiguous()
-        states = states.to(device=dev, dtype=torch.float32).reshape(-1, self.dim).contiguous()
-        of = problem_of_state.to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
-        if int(goals.shape[0]) != int(maps.shape[0]):
-            raise ValueError('NextNetTrain.forward: one goal per map')
-        if int(of.shape[0]) != int(states.shape[0]):
-            raise ValueError('NextNetTrain.forward: one problem_of_state per state')
-        if int(iters) < 0:
-            raise ValueError('NextNetTrain.forward: iters >= 0')
-        if int(states.shape[0]) > 0 and int(maps.shape[0]) == 0:
-            raise ValueError('NextNetTrain.forward: states without problems')
-        return _NextTrainFn.apply(self, maps, goals, states, of, int(iters), *self._params.values())
-
-    __call__ = forward
-
-    def check_status(self):
-        """Read the status words of the forwards issued so far (this waits for them).  Raises RuntimeError when a
-        ``problem_of_state`` entry was outside ``[0, B)``."""
-        pending, self._pending = self._pending, []
-        if not pending:
-            return
-        words = torch.stack(pending).cpu().numpy()
-        bad = np.flatnonzero(words[:, 0])
-        if bad.size:
-            raise RuntimeError('gnnmp_next_train_forward: %d state(s) with problem_of_state outside [0, B) (last offending row %d, '
-                               'call %d of %d checked); their rows of y are NaN and they take no part in the backward'
-                               % (int(words[bad, 0].sum()), int(words[bad[0], 1]) - 1, int(bad[0]), len(pending)))
+        super().__init__((dim,), device)
+        self.dim, = self.dims
 
     def train_step(self, optimizer, maps, goals, paths, path_ptr, iters=DEFAULT_ITERS):
         """One step of ``train_next.py:41-69`` on a batch of ``(problem, path)`` samples (as :func:`training_loss` takes them):
         the labels on the host, then forward, loss, backward and ``optimizer.step()`` on the device.  Returns the loss as a
         device scalar; nothing is copied back."""
-        ptr = np.asarray(path_ptr, dtype=np.int64).reshape(-1)
-        paths = np.asarray(paths, dtype=np.float64).reshape(-1, self.dim)
-        if ptr.size < 2 or paths.shape[0] == 0:
-            raise ValueError('NextNetTrain.train_step: no paths')
-        actions, values = path_labels(paths, ptr, self.dim)
-        dev = maps.device
-        of = torch.from_numpy(np.repeat(np.arange(ptr.size - 1, dtype=np.int32), np.diff(ptr))).to(dev)
-        y = self.forward(maps, goals, torch.from_numpy(paths.astype(np.float32)).to(dev), of, iters)
-        loss = loss_from_outputs(y, torch.from_numpy(actions).to(dev), torch.from_numpy(values).to(dev), ptr)
-        optimizer.zero_grad()
-        loss.backward()
-        optimizer.step()
-        return loss.detach()
+        paths, ptr = core.sample_arrays(paths, path_ptr, self.dim, 'NextNetTrain.train_step')
+        return self._step(optimizer, maps, goals, paths.astype(np.float32), ptr, path_labels(paths, ptr, self.dim), iters)

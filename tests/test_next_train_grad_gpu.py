@@ -5,7 +5,8 @@ recorded shapes: 2 problems with paths of 7 and 10 states at 20 rounds, 1 proble
   * train()'s loss against the reference's recorded losses (the bound of tests/test_next_train_gpu.py);
   * the gradients against the unmodified reference's recorded fp32 / .double() gradients through the project's gradient bar,
     next_train_host.check_bar: per tensor |g - g64| <= max(1e-4 max|g64|, 4 own) + 1e-6, own = max|g32 - g64|;
-  * indexing (problem_of_state in any order, a problem without states), run-to-run bits, the status words, the empty call.
+  * indexing (problem_of_state in any order, a problem without states), run-to-run bits, the status words, the empty call, a backward
+    after a later forward.
 Run with -s for error / bar per tensor."""
 import os
 
@@ -192,3 +193,13 @@ def test_empty_call_gives_an_empty_y_and_zero_gradients_without_the_library(dim)
     assert tuple(y.shape) == (0, dim + 1)
     with pytest.raises(ValueError):
         net.forward(c['maps'][:0], c['goals'][:0], c['states'], c['of'], 2)
+    # backward after a later forward (1 problem, 2 states, 1 round): the workspace holds the later one, whose backward still runs
+    one = (c['maps'], c['goals'], c['states'][:2], c['of'][:2], 1)
+    y_old = net.forward(*one)
+    y_new = net.forward(*one)
+    with pytest.raises(RuntimeError, match='later forward'):
+        y_old.sum().backward()
+    g = _grads(net, y_new.sum())
+    assert set(g) == set(next_train.param_shapes(dim)) and all(bool(torch.isfinite(v).all()) for v in g.values())
+    assert bool(g['policy.4.bias'].any()) and torch.equal(g['lstm.bias_ih'], g['lstm.bias_hh'])
+    net.check_status()

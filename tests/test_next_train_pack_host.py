@@ -1,5 +1,6 @@
 """The packing side of NEXT training, no GPU: device_pack / device_pack_t on CPU tensors against the host packers bit for bit
-(random parameters, both dims, the summed LSTM bias included), and NextNetTrain's state_dict through NextNet.load_state_dict."""
+(random parameters, both dims, the summed LSTM bias included), unpack_weight_grads on the packed position index (the identity,
+padding dropped) and on a tensor, and NextNetTrain's state_dict through NextNet.load_state_dict."""
 import os
 
 import numpy as np
@@ -53,6 +54,41 @@ def test_device_pack_t_is_bit_equal_to_pack_weights_t_and_holds_the_transposes(d
     torch.nn.functional.conv2d(x, wc, padding=1).backward(d)
     dx = torch.nn.functional.conv2d(d, torch.from_numpy(flipped['conv.weight']).double(), padding=1)
     assert torch.allclose(x.grad, dx, rtol=1e-12, atol=1e-12)
+
+
+@pytest.mark.parametrize('dim', [2, 3])
+def test_unpack_of_the_packed_index_is_the_identity_and_padding_is_dropped(dim):
+    index = next_train._pack_index(dim)
+    n = next_model.weights_floats(dim)
+    pos = np.arange(n, dtype=np.float64)
+    un = next_train.unpack_weight_grads(pos, dim)
+    assert set(un) == set(index) == set(next_train.param_shapes(dim))
+    for k, idx in index.items():
+        assert np.array_equal(un[k], idx.astype(np.float64)), k
+    used = np.zeros(n, dtype=np.int64)
+    for k, idx in index.items():
+        used[idx.reshape(-1)] += 1
+    # every position is hit once, the LSTM bias twice, the padding lanes never: the last attention bias's 3 zeros, columns
+    # dim .. 2 of the a3 MLP's first layer, rows dim + 1 .. 3 of the policy's last layer with their biases, and channels
+    # 9 .. 15 of the hidden convolution's 9 taps
+    assert set(np.unique(used)) <= {0, 1, 2} and int((used == 2).sum()) == 256
+    assert int((used == 0).sum()) == 3 + 64 * (3 - dim) + (3 - dim) * 65 + 9 * 7 * 64
+    # a gradient that lives only on padding lanes unpacks to zeros
+    g = (used == 0).astype(np.float64)
+    assert all(not v.any() for v in next_train.unpack_weight_grads(g, dim).values())
+    with pytest.raises(ValueError):
+        next_train.unpack_weight_grads(pos[:-1], dim)
+
+
+@pytest.mark.parametrize('dim', [2, 3])
+def test_unpack_of_a_tensor_gives_tensors_equal_to_the_numpy_path(dim):
+    g = np.random.default_rng(40 + dim).standard_normal(next_model.weights_floats(dim))
+    un = next_train.unpack_weight_grads(g, dim)
+    tu = next_train.unpack_weight_grads(torch.from_numpy(g), dim)
+    assert set(tu) == set(un) and all(isinstance(v, torch.Tensor) and v.dtype == torch.float64 for v in tu.values())
+    for k, shape in next_train.param_shapes(dim).items():
+        assert tuple(tu[k].shape) == tuple(shape) == un[k].shape and np.array_equal(tu[k].numpy(), un[k]), k
+    assert torch.equal(tu['lstm.bias_ih'], tu['lstm.bias_hh'])
 
 
 @pytest.mark.parametrize('dim', [2, 3])
